@@ -15,8 +15,10 @@ UNet's down / mid path on a second stream: kernels overlap, so per-kernel durati
 `kernel_times_s` therefore come from a SECOND pass over ONE chunk of the same inputs in the same process, on ONE stream with every MFMA
 kernel launch bracketed by HIP events on its launch stream ("kernel_pricing": "single-stream pass"; rank 0 only).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields + `roofline` (dominant kernel) + `cpu_baseline` (the fp32 oracle on the
-host cores, bounded sample).
+Prints ONE JSON line (rank 0) with the driver's contract fields.  A plain run does only what that line's headline needs: set-up, warm-up,
+the K timed steps, --dump-outputs DIR (what the timed path returned for its last step, float32) and the line.  --full adds the rest:
+`roofline` (dominant kernel) / `temporal_block` / `kernel_times_s` from the pricing pass, `cpu_baseline` (the fp32 oracle on the host cores,
+bounded sample), `power`, `host_to_host` and the committed `parity` summary.
 """
 import argparse
 import json
@@ -29,6 +31,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+from videovanish_amd.weights import SyntheticWeights  # noqa: E402
 
 MFMA_PEAK_TFLOPS = 2500.0     # dense bf16/fp16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md (chip-level parameters)
 HBM_PEAK_GBS = 8000.0
@@ -105,6 +108,8 @@ def strong_scaling(args, model, dist, rank, world, H, W, ucfg, vcfg):
     if rank != 0:
         return None
     assert all(o is not None and o.shape == (H, W, 3) and o.dtype == np.uint8 for o in out)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, np.stack(out[-args.chunk:]))
     digest = None
     if args.dry_run:
         import hashlib
@@ -190,6 +195,8 @@ def full_pipeline_c5(args, run, rank, world, dist, H, W, ucfg, vcfg):
     if rank != 0:
         return None
     assert len(out) == T and all(o is not None and o.shape == (H, W, 3) and o.dtype == np.uint8 for o in out)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, np.stack(out[-args.chunk:]))
     # ---- priced pass: one 32-frame clip through the same call on one stream
     prior_tab, prior_s, priced_s, dom = None, None, None, None
     if not args.no_kernel_events:
@@ -317,6 +324,96 @@ def synth_clip(T, H, W, seed=1234, t0=0):
     for t in range(T):
         prior[t][masks[t] > 0] = frames[t].reshape(-1, 3).mean(0).astype(np.uint8)
     return frames, masks, prior
+
+
+def host_threads():
+    """worker threads of this rank's host-side pools: up to 16 per node, shared by the node's ranks"""
+    return max(1, min(16, os.cpu_count() or 1) // int(os.environ.get("LOCAL_WORLD_SIZE", "1")))
+
+
+def synth_frames(t0, t1, H, W):
+    """synth_frame(t) for t in [t0, t1) on a thread pool (numpy releases the GIL; ~35 ms per 720p frame on one core): (frames, masks, prior)."""
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(host_threads()) as ex:
+        trip = list(ex.map(lambda t: synth_frame(t, H, W), range(t0, t1)))
+    return tuple(np.stack([x[i] for x in trip]) for i in range(3))
+
+
+def weight_draws(run):
+    """(name, shape, std, mean) of every draw DiffuEraserHIP(run) makes from its seeded weight source, in order: the same modules built on meta
+    tensors (modelhub's shape-only context: nothing is packed, nothing runs)."""
+    from videovanish_amd import modelhub
+    from videovanish_amd.unet import BrushNet, UNetMotion
+    from videovanish_amd.vae import VAE
+
+    class Record(SyntheticWeights):
+        def __init__(self):
+            super().__init__(run.weight_seed)
+            self.draws = []
+
+        def normal(self, name, shape, std=1.0, mean=0.0):
+            self.draws.append((name, tuple(int(d) for d in shape), std, mean))
+            return torch.empty(tuple(shape), device="meta")
+
+    ctx = modelhub._ShapeCtx()
+    ctx.src = Record()
+    text = ctx.src.normal("text_states", (1, run.unet.text_len, run.unet.cross_dim))[0]
+    UNetMotion(ctx, run.unet, text, precise_io=run.precise_io)
+    BrushNet(ctx, run.unet, text, precise_io=run.precise_io)
+    VAE(ctx, run.vae, precise_decoder=run.precise_decoder)
+    return ctx.src.draws
+
+
+class PrefetchedWeights(SyntheticWeights):
+    """SyntheticWeights whose draws are made ahead of the model build on a thread pool.  Each tensor is torch.randn from a CPU generator
+    seeded by (seed, name), which runs on one core; at full width those draws were most of the set-up time.  Same draws, same arithmetic:
+    bit-identical tensors.  A request that was not foreseen is drawn on the spot and counted in `unforeseen` (a draw list that no longer follows
+    the model's construction shows there; a repeated request of a listed draw -- the fused attention blocks ask twice -- is drawn on the spot
+    uncounted); at most `ahead_bytes` of draws wait to be taken."""
+
+    def __init__(self, seed, draws, ahead_bytes=2 << 30):
+        from collections import deque
+        from concurrent.futures import ThreadPoolExecutor
+        super().__init__(seed)
+        self._pool = ThreadPoolExecutor(host_threads())
+        self._todo, self._ahead, self._bytes, self._limit = deque(draws), {}, 0, ahead_bytes
+        self._listed, self.unforeseen = set(draws), 0
+        self._fill()
+
+    def _fill(self):
+        while self._todo and self._bytes < self._limit:
+            key = self._todo.popleft()
+            if key not in self._ahead:
+                self._ahead[key] = self._pool.submit(SyntheticWeights.normal, self, *key)
+                self._bytes += 4 * int(np.prod(key[1]))
+
+    def normal(self, name, shape, std=1.0, mean=0.0):
+        key = (name, tuple(int(d) for d in shape), std, mean)
+        fut = self._ahead.pop(key, None)
+        if fut is None:
+            self.unforeseen += key not in self._listed
+            return super().normal(name, shape, std, mean)
+        self._bytes -= 4 * int(np.prod(key[1]))
+        self._fill()
+        return fut.result()
+
+    def close(self):      # after the build: later requests (if any) are drawn on the spot
+        self._pool.shutdown(cancel_futures=True)
+        self._todo.clear()
+        self._ahead, self._bytes = {}, 0
+
+
+def dump_outputs(path, frames):
+    """--dump-outputs: the uint8 frames [F, H, W, 3] the timed path returned for its last step, as float32 `frames.npy`.  Above 8 M values a fixed,
+    seeded sample of pixel positions (the same for every frame) is kept: `frames.npy` is then [F, P, 3] with F * P * 3 <= 8 M (32 MB)."""
+    a = frames.cpu().numpy() if torch.is_tensor(frames) else np.asarray(frames)
+    F, H, W, C = a.shape
+    cap = 8 << 20
+    if a.size > cap:
+        pix = np.sort(np.random.default_rng(0).choice(H * W, cap // (F * C), replace=False))
+        a = a.reshape(F, H * W, C)[:, pix]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "frames.npy"), a.astype(np.float32))
 
 
 def cpu_baseline(H, W, steps, chunk, overlap, sample_hw=(256, 384), vae_hw=(192, 256), sample_frames=4):
@@ -459,7 +556,19 @@ def main():
     ap.add_argument("--dilate", type=int, default=8, help="--prior raft: mask_dilation_iter of the drop-in call (reference default 8)")
     ap.add_argument("--dump-kernels", default=None, help="write the raw per-kernel table (launches, seconds, flops, bytes) to this JSON file")
     ap.add_argument("--profile-shapes", action="store_true", help="per-kernel keys carry the GEMM / attention shapes (M, N, K): tools/shape_table.py")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the single-stream pricing pass (`roofline`, "
+                    "`temporal_block`, `kernel_times_s`; --prior raft: `prior`), `cpu_baseline`, the `power` trace, `host_to_host` and the committed "
+                    "`parity` summary (each still subject to its --no-* switch).  Without it the run sets up, warms up, times the --steps steps, "
+                    "writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the timed path returned for its last "
+                    "step (rank 0: the uint8 frames of its last chunk; a fixed, seeded sample of pixel positions above 8 M values) as float32 DIR/frames.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_kernels and not args.full:
+        ap.error("--dump-kernels needs --full (the per-kernel table comes from the pricing pass)")
+    if not args.full:
+        args.no_kernel_events = args.no_cpu_baseline = args.no_power_trace = True
     if args.one_stream:
         from videovanish_amd import unet as _unet
         _unet.Denoiser.OVERLAP = False
@@ -507,13 +616,15 @@ def main():
             import torch.distributed as td
             td.destroy_process_group()
         return
-    t_build = time.time()
+    t_build, src = time.time(), None
     if args.dry_run:
         from videovanish_amd.pipeline import DryRunEraser
         model = DryRunEraser(run, "cpu")
         args.no_kernel_events = args.no_cpu_baseline = args.no_power_trace = True      # no kernels run: nothing to price, nothing to compare
     else:
-        model = DiffuEraserHIP(run, f"cuda:{local_rank}")
+        src = PrefetchedWeights(run.weight_seed, weight_draws(run))
+        model = DiffuEraserHIP(run, f"cuda:{local_rank}", weights=src)
+        src.close()
         torch.cuda.synchronize()
     t_build = time.time() - t_build
     H, W = args.height, args.width
@@ -539,9 +650,7 @@ def main():
         mine = shard_chunks(len(plan), world)[rank]
         base, end = plan[mine[0]][0], plan[mine[-1]][1]
         # seeded per FRAME INDEX (synth_frame), so the video -- and with it every output frame -- does not depend on how many ranks share it
-        trip = [synth_frame(t, H, W) for t in range(base, end)]
-        fr, mk, pr = (np.stack([x[i] for x in trip]) for i in range(3))
-        del trip
+        fr, mk, pr = synth_frames(base, end, H, W)
         host_inputs[:] = [fr, pr, mk]
         return T, base, torch.from_numpy(fr).to(dev), torch.from_numpy(pr).to(dev), torch.from_numpy(mk).to(dev)
 
@@ -594,18 +703,22 @@ def main():
         assert len(frame_sha) == T, "dry run: the ranks' owned frames do not tile the video"
     distinct = stride * args.steps * world          # credited frames: every chunk contributes (chunk - overlap) new frames
     assert out is not None and out.dtype == torch.uint8 and out.shape[1:] == (H, W, 3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out[-args.chunk:])
     # SURVEY 8(d) defines the metric host memory -> host memory; `value` keeps the inputs resident (the driver contract), the copies this rank would add
     # are measured right here on the same tensors and reported beside it (`host_to_host`)
-    model._sync()
-    t_up = time.time()
-    ups = [torch.from_numpy(a).to(dev) for a in host_inputs]
-    model._sync()
-    t_up = time.time() - t_up
-    del ups
-    t_down = time.time()
-    out_host = out.cpu()
-    t_down = time.time() - t_down
-    del out_host
+    t_up = t_down = None
+    if args.full:
+        model._sync()
+        t_up = time.time()
+        ups = [torch.from_numpy(a).to(dev) for a in host_inputs]
+        model._sync()
+        t_up = time.time() - t_up
+        del ups
+        t_down = time.time()
+        out_host = out.cpu()
+        t_down = time.time() - t_down
+        del out_host
 
     if rank != 0:
         if multi:
@@ -669,17 +782,19 @@ def main():
         "config": {"workload": f"{ {480: 'c2', 720: 'c3', 1080: 'c4'}.get(H, 'custom') } chunk: {args.chunk}-frame {W}x{H} chunk, {args.denoise_steps} DDIM steps, {args.chunk}/{args.overlap} chunk/overlap, "
                                f"{args.arch} SD-1.5 UNet+BrushNet+motion / SD-VAE, random-init weights",
                    "frames_per_step": args.chunk, "credited_frames_per_step": stride, "chunks_per_rank": args.steps, "chunks_total": args.steps * world,
-                   "parallelism": f"chunk-dp{world}", "model_build_s": round(t_build, 1), "precise_decoder": bool(args.precise_decoder),
+                   "parallelism": f"chunk-dp{world}", "model_build_s": round(t_build, 1),
+                   "weights_unforeseen_draws": None if src is None else src.unforeseen, "precise_decoder": bool(args.precise_decoder),
                    "concurrent_chunks": min(model.run.concurrent_chunks, args.steps),
                    "streams_per_chunk": 2 if (min(model.run.concurrent_chunks, args.steps) == 1 and __import__("videovanish_amd.unet", fromlist=["x"]).Denoiser.OVERLAP) else 1,
-                   "parity": parity_summary()},
+                   "parity": parity_summary() if args.full else None},
         "kernel_pricing": None if not prof else {"how": "single-stream pass", "chunks": 1, "seconds": round(dt_priced, 3),
                                                  "kernel_seconds": round(sum(v[1] for v in kernels.values()), 3),
                                                  "note": "one chunk of the same resident inputs re-run after the timed region on ONE stream, every launch bracketed "
                                                          "by HIP events on its launch stream; the timed region itself overlaps kernels of several streams"},
-        "host_to_host": {"value": round(distinct / (dt + t_up + t_down), 5), "unit": "frames/s", "upload_s": round(t_up, 4), "download_s": round(t_down, 4),
-                         "note": "SURVEY 8(d) form of the metric: the same timed region plus this rank's synchronous upload of its uint8 frames / prior / masks and "
-                                 "download of its uint8 output (pageable host memory, measured on the same tensors right after the timed region)"},
+        "host_to_host": None if t_up is None else {
+            "value": round(distinct / (dt + t_up + t_down), 5), "unit": "frames/s", "upload_s": round(t_up, 4), "download_s": round(t_down, 4),
+            "note": "SURVEY 8(d) form of the metric: the same timed region plus this rank's synchronous upload of its uint8 frames / prior / masks and "
+                    "download of its uint8 output (pageable host memory, measured on the same tensors right after the timed region)"},
         "roofline": roof, "temporal_block": temporal, "cpu_baseline": cpu, "power": power.summary() if power is not None else None,
         "job_tflops": round(__import__("videovanish_amd.flops", fromlist=["x"]).per_output_frame(H, W, args.chunk, args.denoise_steps, ucfg, vcfg)
                             * args.chunk * args.steps * world / dt / 1e12, 1),

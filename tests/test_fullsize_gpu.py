@@ -210,11 +210,11 @@ def test_image_kernels_full_size_bit_exact(gpu):
 
 
 def test_bench_contract_line(gpu):
-    """bench.py prints ONE JSON line with the driver's contract fields + roofline (live HIP events) + cpu_baseline (tiny arch, 2 steps)."""
+    """bench.py --full prints ONE JSON line with the driver's contract fields + roofline (live HIP events) + cpu_baseline (tiny arch, 2 steps)."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--arch", "tiny", "--height", "128", "--width", "192", "--denoise-steps", "2",
-                        "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--steps", "2", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -229,6 +229,58 @@ def test_bench_contract_line(gpu):
     assert ro["bound"] in ("hbm", "mfma") and ro["peak"] > 0 and abs(ro["frac"] - ro["achieved"] / ro["peak"]) < 1e-3 and ro["launches"] > 0
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "sample" in cb
+
+
+def test_bench_plain_line_and_dumped_outputs(gpu, tmp_path):
+    """Without --full the line carries the headline figure only (no pricing pass, CPU baseline, power trace or host-to-host copies), --steps sets
+    the timed chunks, and --dump-outputs writes the last chunk's frames: float32, inside [0, 255], the same in two runs of the same command."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for i in range(2):
+        d_out = str(tmp_path / f"run{i}")
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--arch", "tiny", "--height", "128", "--width", "192",
+                            "--denoise-steps", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", d_out], capture_output=True, text=True, timeout=900, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["config"]["chunks_per_rank"] == 3 and d["per_rank"][0]["owned_frames"] == 3 * 24 + 8
+        assert d["value"] > 0 and abs(d["value"] - 24 * 1000.0 / d["ms_per_step"]) / d["value"] < 1e-3
+        for k in ("roofline", "temporal_block", "cpu_baseline", "power", "host_to_host", "kernel_pricing"):
+            assert d[k] is None, k
+        assert d["kernel_times_s"] == {} and d["config"]["weights_unforeseen_draws"] == 0
+        a = np.load(os.path.join(d_out, "frames.npy"))
+        assert a.dtype == np.float32 and a.shape == (32, 128, 192, 3) and a.min() >= 0 and a.max() <= 255 and a.std() > 0
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1])
+    # the dump is the last chunk of the timed path's output: the same seeded clip through forward_device in this process, with the model built
+    # the original way (SyntheticWeights drawn one at a time, not bench.py's prefetched draws), returns these frames bit for bit
+    import bench
+    from videovanish_amd.config import TINY_UNET, TINY_VAE, RunConfig
+    from videovanish_amd.pipeline import DiffuEraserHIP
+    run = RunConfig(steps=2, chunk=32, overlap=8, seed=42, weight_seed=0, dtype="fp16", unet=TINY_UNET, vae=TINY_VAE, precise_decoder=True)
+    model = DiffuEraserHIP(run, "cuda:0")
+    T = 24 * 3 + 8
+    fr, mk, pr = bench.synth_frames(0, T, 128, 192)
+    out, (lo, hi) = model.forward_device(*(torch.from_numpy(x).to(gpu) for x in (fr, pr, mk)), T, 0, steps=2, scheduler="ddim")
+    assert (lo, hi) == (0, T)
+    assert np.array_equal(dumps[0], out[-32:].cpu().numpy().astype(np.float32))
+
+
+def test_bench_weight_draw_list_foresees_the_full_width_build(gpu):
+    """bench.py draws the seeded weights ahead of the model build from a list made by a shape-only build; a request the list did not name is
+    drawn on the spot (still bit-identical, but the set-up time goes back to the serial draws).  At full width every request is foreseen."""
+    import bench
+    from videovanish_amd.config import RunConfig
+    from videovanish_amd.pipeline import DiffuEraserHIP
+    run = RunConfig(dtype="fp16")
+    src = bench.PrefetchedWeights(run.weight_seed, bench.weight_draws(run))
+    model = DiffuEraserHIP(run, "cuda:0", weights=src)
+    src.close()
+    assert src.unforeseen == 0
+    del model
+    torch.cuda.empty_cache()
 
 
 def test_bench_line_with_rccl_initialised(gpu):

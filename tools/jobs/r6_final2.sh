@@ -9,6 +9,6 @@ F=$(find $W/fetch -name "*counter_collection.csv" | head -1); WR=$(find $W/write
 python3 $ROOT/tools/pmc_summary.py $F $WR $ROOT/$O/traffic.json > $ROOT/$O/traffic_top.txt 2>&1
 cd $ROOT
 bash tools/jobs/r6_stage32_ab.sh
-python bench.py --steps 20 --warmup 5 > $O/bench_20steps_b.json 2> $O/bench_20steps_b.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_20steps_b.json 2> $O/bench_20steps_b.err
 python -c "
 import json; d=json.load(open('$O/bench_20steps_b.json')); print({k: d[k] for k in ('value','ms_per_step','temporal_block','job_tflops')}, d['roofline']['avg_launch_ms'], d['roofline']['frac'])"

@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 W=/tmp/vvprof_$TAG
 rm -rf $W; mkdir -p $W
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $W/stats -o bench -- python3 $ROOT/bench.py --steps 2 --warmup 1 --one-stream --no-cpu-baseline --no-power-trace > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $W/stats -o bench -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --one-stream --no-cpu-baseline --no-power-trace > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 find $W/stats -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
 P2="--steps 1 --warmup 0 --denoise-steps 2 --no-cpu-baseline --no-kernel-events --no-power-trace"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $W/fetch -o f -- python3 $ROOT/bench.py $P2 > $OUT/pmc_fetch.log 2>&1
