@@ -3,7 +3,7 @@
 with the hot path running on hand-written gfx950 HIP kernels (videovanish_amd/) instead of torch/cuDNN.
 
 Extra keyword-only knobs (old callers are unaffected): num_inference_steps, scheduler, chunk, overlap, dtype, seed,
-compat_reference_early_return.  There is no CPU fallback: without the HIP extension / a GPU this raises.
+compat_reference_early_return, roi (mask-region inference: videovanish_amd/roi.py; also configure(roi=...) and $VV_ROI).  There is no CPU fallback: without the HIP extension / a GPU this raises.
 """
 import argparse
 import os
@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from videovanish_amd import hip
+from videovanish_amd import roi as roi_plan
 from videovanish_amd.config import RunConfig
 from videovanish_amd.diffueraser import DiffuEraser
 from videovanish_amd.propainter import Propainter, get_device
@@ -27,9 +28,10 @@ _gather = "all"
 _prior_stages = {}      # configure(prior=...): optional learned stages of the ProPainter prior (flow_completion, generator)
 _weights = None         # configure(weights=...) / $VV_WEIGHTS_DIR: a local model store (videovanish_amd/modelhub.py) or a CheckpointWeights
 _loaded = None          # (CheckpointWeights, prior stages) resolved from _weights, cached until configure() is called again
+_roi = None             # configure(roi=...): mask-region inference for calls that do not pass roi= themselves
 
 
-def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False):
+def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -42,8 +44,10 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     forward): the pipeline's own temporal scheme (22-frame windows shifted on odd steps, value / count averaging, key-frame pre-inference:
     RunConfig.windowing="reference", one GPU), the 2-step TCD schedule of the "2-Step" checkpoint (already the default of this module), and the
     COMPLETE ProPainter prior (recurrent flow completion + inpainting generator) when no prior is handed over -- instead of this build's defaults
-    (independent 32 / 8 chunks that shard over GPUs; RAFT + propagation only).  `run` / `prior` given explicitly still win field by field."""
-    global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded
+    (independent 32 / 8 chunks that shard over GPUs; RAFT + propagation only).  `run` / `prior` given explicitly still win field by field.
+    roi = None / "static" / "follow" / a roi.RoiConfig: mask-region inference for calls that do not pass roi= (run_infill_on_frames)."""
+    global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi
+    roi_plan.as_config(roi)                 # validated now, kept as given: configure(roi="off") means the full frame whatever $VV_ROI says
     if reference_defaults:
         import dataclasses
         run = dataclasses.replace(run or RunConfig(), windowing="reference")
@@ -51,6 +55,7 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     _run_config, _dist, _gather, last_ckpt = run, dist, gather, None
     _prior_stages, propainter = dict(prior or {}), None
     _weights, _loaded = weights, None
+    _roi = roi
 
 
 def _resolve_weights(ckpt):
@@ -72,18 +77,40 @@ def _resolve_weights(ckpt):
     return w, stages
 
 
+def roi_config(roi=None):
+    """The mask-region setting a call runs with: its own roi= argument, else configure(roi=...), else $VV_ROI (static | follow | off).
+    None = full frame.  roi="off" (or False) asks for the full frame whatever configure() or the environment say."""
+    if roi is not None:
+        return roi_plan.as_config(roi)
+    if _roi is not None:
+        return roi_plan.as_config(_roi)
+    return roi_plan.as_config(os.environ.get("VV_ROI"))
+
+
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
-                         *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False):
+                         *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None):
+    """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
+    masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
+    the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame."""
     global device, last_ckpt, video_inpainting_sd, propainter
 
+    rcfg = roi_config(roi)
+    if rcfg is not None and compat_reference_early_return:
+        raise ValueError("roi= (mask-region inference) cannot be combined with compat_reference_early_return=True")
     H0, W0 = frames_rgb[0].shape[:2]
 
     if prog is not None: prog(5, "dilating frames")
     dev = get_device()
     m = torch.from_numpy(np.stack([mm if mm.ndim == 3 else mm[..., None] for mm in mask_frames])).to(dev)
     dil_t = hip.mask_collapse_dilate(m.contiguous(), mask_dilation_iter)       # reference :27-31
+    plan = roi_plan.plan_roi(hip.mask_bbox(dil_t).cpu().numpy(), H0, W0, feather_px, rcfg) if rcfg is not None else None
     dilated_mask_frames = list(dil_t.cpu().numpy())
+    full_frames = frames_rgb
+    if plan is not None:      # the model, and the prior when it is computed here, see only the windows
+        frames_rgb, dilated_mask_frames = plan.crop(frames_rgb), plan.crop(dilated_mask_frames)
+        if propainer_frames is not None:
+            propainer_frames = plan.crop(propainer_frames)
 
     if prog is not None: prog(10, "loading weights")
     if last_ckpt != ckpt or video_inpainting_sd is None:                        # reference :35-45 (ckpt forced to "2-Step")
@@ -113,6 +140,8 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
                                                    num_inference_steps=num_inference_steps, scheduler=scheduler)
 
     if prog is not None: prog(90, "resizing and merging finished frames")
+    if plan is not None:
+        return _paste_windows(inpainted_frames, full_frames, dil_t, plan, feather_px if keep_unmasked_original else -1.0, dev)
     # reference :69-112.  The reference returns from inside its loop (:114) so only frame 0 is post-processed; the
     # evident intent (all frames) is the default here, compat_reference_early_return=True reproduces the quirk.
     n_post = 1 if compat_reference_early_return else len(inpainted_frames)
@@ -130,6 +159,22 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     for j, i in enumerate(idx):
         inpainted_frames[i] = out[j]
     return inpainted_frames
+
+
+def _paste_windows(inpainted_frames, frames_rgb, dil_t, plan, feather_px, dev):
+    """The model's window frames back into the full-size originals (resize to the window, paste, feathered composite: one kernel)."""
+    idx = [i for i in range(len(inpainted_frames)) if inpainted_frames[i] is not None]       # multi-GPU "rank0" gather, as below
+    if not idx:
+        return inpainted_frames
+    h, w = plan.size
+    patch = torch.from_numpy(np.stack([inpainted_frames[i] for i in idx])).to(dev)
+    orig = torch.from_numpy(np.stack([frames_rgb[i] for i in idx])).to(dev)
+    offs = torch.from_numpy(np.ascontiguousarray(plan.offsets[idx])).to(dev)
+    out = hip.roi_paste_composite(patch.contiguous(), orig.contiguous(), dil_t[idx].contiguous(), offs, h, w, float(feather_px)).cpu().numpy()
+    res = list(inpainted_frames)
+    for j, i in enumerate(idx):
+        res[i] = out[j]
+    return res
 
 
 def _frame_io():
@@ -158,6 +203,9 @@ def main():
     ap.add_argument("--start_frame", type=int, default=0, help="Index of first frame to process (default: 0).")
     ap.add_argument("--max_frames", type=int, default=-1, help="Max number of frames to process after start_frame.")
     ap.add_argument("--out", type=str, default=None, help="Output video path (default: <input>_vanished.mkv)")
+    ap.add_argument("--roi", choices=roi_plan.MODES, default=None,
+                    help="Mask-region inference: run the model only on a window around the masks (static: one window per clip; follow: "
+                         "a window that follows the mask).  Pixels outside the window stay the original ones.")
     args = ap.parse_args()
 
     assert os.path.isfile(args.color_video), "input video missing"
@@ -172,7 +220,8 @@ def main():
         Hp, Wp = prior_frames[0].shape[:2]
         assert (H0 == Hp and W0 == Wp), "prior and color video are diffrent sizes"
     assert (H0 == Hm and W0 == Wm), "mask and color video are diffrent sizes"
-    out_frames = run_infill_on_frames(frames, mask_frames, propainer_frames=prior_frames)
+    kw = {"roi": args.roi} if args.roi is not None else {}      # pass roi= only when asked for: a default call stays the reference's call
+    out_frames = run_infill_on_frames(frames, mask_frames, propainer_frames=prior_frames, **kw)
     tools.write_video_frames_to_path(out_video, out_frames, fps, H0, W0)
 
 

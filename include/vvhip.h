@@ -299,6 +299,15 @@ int vv_feather_composite(const uint8_t* inpainted, const uint8_t* orig, const ui
 /* windowed 5x5 chamfer distance transform: distance to the nearest ZERO pixel where it is <= R, else a large
  * constant ((INT_MAX>>2)/65536); fp32 */
 int vv_chamfer_dt(const uint8_t* bin, int T, int H, int W, int R, float* out, void* stream);
+/* mask-region inference (videovanish_amd/roi.py; kernels in vv_roi.hip).
+ * vv_mask_bbox: bbox [T][4] = half-open (y0, x0, y1, x1) of the non-zero bytes of each [H][W] mask; (0, 0, 0, 0) for a frame without one.
+ * Deterministic (integer min / max). */
+int vv_mask_bbox(const uint8_t* mask2d, int T, int H, int W, int* bbox, void* stream);
+/* vv_roi_paste_composite: out [T][H0][W0][3] = orig outside frame t's window [oy, oy+h) x [ox, ox+w) (offsets [T][2] = (oy, ox), device);
+ * inside it the model output patch [T][Hm][Wm][3] resized to h x w (as vv_resize_bilinear_u8) at the offset, then feathered against orig with
+ * the full-frame mask2d [T][H0][W0] (as vv_feather_composite).  Byte-identical to that chain.  feather_px < 0: plain paste (mask2d may be NULL). */
+int vv_roi_paste_composite(const uint8_t* patch, int Hm, int Wm, const uint8_t* orig, const uint8_t* mask2d, const int* offsets, int T, int H0, int W0,
+                           int h, int w, float feather_px, uint8_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K9/K10  RAFT correlation lookup + recurrent-update pieces + convex upsampling, bilinear warp, forward/backward

@@ -1,7 +1,7 @@
 // K11: uint8 image steps of the in-tree part of the path (reference diffuerase.py:27-31, 69-112) and the
 // third-party compose.  Integer / fixed-point work: results are bit-exact against oracle/.
 // HBM-bound byte kernels: one thread per pixel, coalesced along x.
-#include "vv_common.h"
+#include "vv_image_px.h"
 #pragma clang fp contract(off)
 
 namespace {
@@ -45,33 +45,12 @@ __global__ void copy_u8_kernel(const uint8_t* in, uint8_t* out, int64_t n) {
 }
 
 // ---- cv2.resize on uint8 (legacy fixed-point INTER_LINEAR; INTER_NEAREST) -------------------------------------
-__device__ __forceinline__ void lin_coef(int d, int ssize, int dsize, int& s0, int& s1, int& a0, int& a1) {
-    const double scale = (double)ssize / (double)dsize;
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { f = 0.f; s = 0; }
-    if (s >= ssize - 1) { f = 0.f; s = ssize - 1; }
-    a0 = __float2int_rn((1.0f - f) * 2048.0f);
-    a1 = __float2int_rn(f * 2048.0f);
-    s0 = s; s1 = min(s + 1, ssize - 1);
-}
+using namespace vvpx;
 __global__ void resize_bilinear_kernel(const uint8_t* src, int T, int Hs, int Ws, int ch, uint8_t* dst, int Hd, int Wd) {
     const int64_t n = (int64_t)T * Hd * Wd;
     for (int64_t i = blockIdx.x * (int64_t)EB + threadIdx.x; i < n; i += (int64_t)gridDim.x * EB) {
         const int x = (int)(i % Wd); const int y = (int)((i / Wd) % Hd); const int t = (int)(i / ((int64_t)Wd * Hd));
-        int x0, x1, ax0, ax1, y0, y1, by0, by1;
-        lin_coef(x, Ws, Wd, x0, x1, ax0, ax1);
-        lin_coef(y, Hs, Hd, y0, y1, by0, by1);
-        const uint8_t* r0 = src + ((int64_t)t * Hs + y0) * Ws * ch;
-        const uint8_t* r1 = src + ((int64_t)t * Hs + y1) * Ws * ch;
-        for (int c = 0; c < ch; ++c) {
-            const int h0 = r0[x0 * ch + c] * ax0 + r0[x1 * ch + c] * ax1;
-            const int h1 = r1[x0 * ch + c] * ax0 + r1[x1 * ch + c] * ax1;
-            int v = (((by0 * (h0 >> 4)) >> 16) + ((by1 * (h1 >> 4)) >> 16) + 2) >> 2;
-            v = v < 0 ? 0 : (v > 255 ? 255 : v);
-            dst[i * ch + c] = (uint8_t)v;
-        }
+        bilinear_px(src + (int64_t)t * Hs * Ws * ch, Hs, Ws, ch, x, y, Hd, Wd, dst + i * ch);
     }
 }
 __global__ void resize_nearest_kernel(const uint8_t* src, int T, int Hs, int Ws, int ch, uint8_t* dst, int Hd, int Wd) {
@@ -84,30 +63,7 @@ __global__ void resize_nearest_kernel(const uint8_t* src, int T, int Hs, int Ws,
     }
 }
 
-// ---- 5x5 chamfer distance (16.16 fixed point; a=1, b=1.4, c=2.1969), windowed closed form ---------------------
-constexpr int C_HV = 65536, C_DIAG = 91750, C_LONG = 143976;
-constexpr int DIST_BIG = (0x7fffffff >> 2);
-__device__ __forceinline__ int chamfer_fixed(int dx, int dy) {
-    dx = dx < 0 ? -dx : dx; dy = dy < 0 ? -dy : dy;
-    if (dx < dy) { const int tmp = dx; dx = dy; dy = tmp; }
-    return dx >= 2 * dy ? dy * C_LONG + (dx - 2 * dy) * C_HV : (dx - dy) * C_LONG + (2 * dy - dx) * C_DIAG;
-}
-// distance (fixed) from (x,y) to the nearest pixel whose "is-zero" predicate holds, searched in a (2R+1)^2 window.
-// want_nonzero=false: nearest pixel with bin==0; true: nearest pixel with bin!=0 (== zero pixel of the inverse)
-__device__ __forceinline__ int window_dist(const uint8_t* img, int H, int W, int x, int y, int R, bool want_nonzero) {
-    int best = DIST_BIG;
-    for (int dy = -R; dy <= R; ++dy) {
-        const int yy = y + dy;
-        if (yy < 0 || yy >= H) continue;
-        for (int dx = -R; dx <= R; ++dx) {
-            const int xx = x + dx;
-            if (xx < 0 || xx >= W) continue;
-            const bool nz = img[(int64_t)yy * W + xx] > 0;
-            if (nz == want_nonzero) { const int d = chamfer_fixed(dx, dy); best = d < best ? d : best; }
-        }
-    }
-    return best;
-}
+// ---- windowed 5x5 chamfer distance (vv_image_px.h) and the feathered composite -------------------------------
 __global__ void chamfer_dt_kernel(const uint8_t* bin, int T, int H, int W, int R, float* out) {
     const int64_t n = (int64_t)T * H * W;
     for (int64_t i = blockIdx.x * (int64_t)EB + threadIdx.x; i < n; i += (int64_t)gridDim.x * EB) {
@@ -124,26 +80,8 @@ __global__ void feather_composite_kernel(const uint8_t* inp, const uint8_t* orig
     const int64_t n = (int64_t)T * H * W;
     for (int64_t i = blockIdx.x * (int64_t)EB + threadIdx.x; i < n; i += (int64_t)gridDim.x * EB) {
         const int x = (int)(i % W); const int y = (int)((i / W) % H); const int64_t t = i / ((int64_t)W * H);
-        const uint8_t* img = mask + t * H * W;
-        const bool inside = img[(int64_t)y * W + x] > 0;
-        float alpha;
-        if (feather > 0.f) {
-            // d_in: distance of masked pixels to the nearest unmasked one; d_out: the converse (0 on the own side)
-            const int d = window_dist(img, H, W, x, y, R, !inside);
-            const float df = (float)d * (1.0f / 65536.0f);
-            const float d_in = inside ? df : 0.f, d_out = inside ? 0.f : df;
-            alpha = 0.5f + (d_in - d_out) / (2.0f * feather);
-            alpha = fminf(fmaxf(alpha, 0.f), 1.f);
-        } else alpha = inside ? 1.f : 0.f;
-        const float om = 1.0f - alpha;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float a = alpha * (float)inp[i * 3 + c];
-            const float b = om * (float)orig[i * 3 + c];
-            float v = rintf(a + b);
-            v = fminf(fmaxf(v, 0.f), 255.f);
-            out[i * 3 + c] = (uint8_t)v;
-        }
+        const float alpha = feather_alpha(mask + t * H * W, H, W, x, y, feather, R);
+        feather_blend(alpha, inp + i * 3, orig + i * 3, out + i * 3);
     }
 }
 

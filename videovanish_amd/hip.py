@@ -105,7 +105,7 @@ class AttnParams(C.Structure):
 
 EXPORTS = ["vv_abi_version", "vv_last_error", "vv_device_count", "vv_device_name", "vv_conv_gemm", "vv_groupnorm_nsplit",
            "vv_groupnorm", "vv_layernorm", "vv_attention", "vv_axpby_f32", "vv_silu_f32", "vv_sched_step", "vv_add_inplace",
-           "vv_mask_collapse_dilate", "vv_resize_bilinear_u8", "vv_resize_nearest_u8", "vv_feather_composite", "vv_chamfer_dt",
+           "vv_mask_collapse_dilate", "vv_resize_bilinear_u8", "vv_resize_nearest_u8", "vv_feather_composite", "vv_chamfer_dt", "vv_mask_bbox", "vv_roi_paste_composite",
            "vv_preprocess", "vv_brushnet_input", "vv_pad_channels", "vv_decode_blend", "vv_blur_compose",
            "vv_avgpool2_f32", "vv_corr_lookup", "vv_raft_ctx_split", "vv_raft_flow_prep", "vv_gru_rh", "vv_gru_update", "vv_add_flow",
            "vv_add_relu_f32", "vv_convex_upsample", "vv_fb_valid", "vv_deform_im2col", "vv_fc_input", "vv_upsample2x_bilinear", "vv_flow_combine", "vv_gather_rows", "vv_fold_patches", "vv_flow_down4", "vv_gen_compose", "vv_gen_input", "vv_prop_fill", "vv_prop_combine", "vv_masked_sum_u8", "vv_u8_to_f32", "vv_u8_is_zero",
@@ -499,6 +499,32 @@ def feather_composite(inpainted, orig, mask2d, feather_px):
     out = torch.empty_like(inpainted)
     with _Prof("feather_composite", 0.0, T * H * W * (3 + 3 + 1 + 3)):
         _check(lib().vv_feather_composite(_p(inpainted), _p(orig), _p(mask2d), T, H, W, C.c_float(feather_px), _p(out), _stream()), "vv_feather_composite")
+    return out
+
+
+def mask_bbox(mask2d):
+    """mask2d [T,H,W] u8 -> [T,4] int32 on the device: half-open (y0, x0, y1, x1) of each frame's non-zero bytes, (0, 0, 0, 0) when there is none."""
+    _need_cuda(mask2d)
+    T, H, W = mask2d.shape
+    bbox = torch.empty((T, 4), dtype=torch.int32, device=mask2d.device)
+    with _Prof("mask_bbox", 0.0, T * H * W + T * 16):
+        _check(lib().vv_mask_bbox(_p(mask2d), T, H, W, _p(bbox), _stream()), "vv_mask_bbox")
+    return bbox
+
+
+def roi_paste_composite(patch, orig, mask2d, offsets, h, w, feather_px):
+    """patch [T,Hm,Wm,3] u8 (model output of the window), orig [T,H0,W0,3] u8, mask2d [T,H0,W0] u8, offsets [T,2] int32 (oy, ox) -> [T,H0,W0,3]:
+    resize_u8(patch -> h, w) pasted at each frame's offset into orig, then feather_composite(., orig, mask2d, feather_px) -- in one pass.
+    feather_px < 0: plain paste (mask2d may be None)."""
+    _need_cuda(patch, orig, mask2d, offsets)
+    T, Hm, Wm, _ = patch.shape
+    _, H0, W0, _ = orig.shape
+    if offsets.dtype != torch.int32 or tuple(offsets.shape) != (T, 2) or orig.shape[0] != T or patch.shape[3] != 3 or orig.shape[3] != 3 or (mask2d is not None and tuple(mask2d.shape) != (T, H0, W0)):
+        raise RuntimeError("roi_paste_composite: shapes / dtypes do not match")
+    out = torch.empty_like(orig)
+    with _Prof("roi_paste_composite", 0.0, T * H0 * W0 * (3 + 1 + 3) + patch.numel()):
+        _check(lib().vv_roi_paste_composite(_p(patch), Hm, Wm, _p(orig), _p(mask2d), _p(offsets), T, H0, W0, int(h), int(w), C.c_float(feather_px), _p(out),
+                                            _stream()), "vv_roi_paste_composite")
     return out
 
 
