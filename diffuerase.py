@@ -45,7 +45,8 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     RunConfig.windowing="reference", one GPU), the 2-step TCD schedule of the "2-Step" checkpoint (already the default of this module), and the
     COMPLETE ProPainter prior (recurrent flow completion + inpainting generator) when no prior is handed over -- instead of this build's defaults
     (independent 32 / 8 chunks that shard over GPUs; RAFT + propagation only).  `run` / `prior` given explicitly still win field by field.
-    roi = None / "static" / "follow" / a roi.RoiConfig: mask-region inference for calls that do not pass roi= (run_infill_on_frames)."""
+    roi = None / "static" / "follow" / "static-regions" / "follow-regions" / a roi.RoiConfig: mask-region inference for calls that do not pass
+    roi= (run_infill_on_frames)."""
     global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi
     roi_plan.as_config(roi)                 # validated now, kept as given: configure(roi="off") means the full frame whatever $VV_ROI says
     if reference_defaults:
@@ -78,7 +79,8 @@ def _resolve_weights(ckpt):
 
 
 def roi_config(roi=None):
-    """The mask-region setting a call runs with: its own roi= argument, else configure(roi=...), else $VV_ROI (static | follow | off).
+    """The mask-region setting a call runs with: its own roi= argument, else configure(roi=...), else $VV_ROI (static | follow | static-regions |
+    follow-regions | off).
     None = full frame.  roi="off" (or False) asks for the full frame whatever configure() or the environment say."""
     if roi is not None:
         return roi_plan.as_config(roi)
@@ -92,9 +94,9 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
-    the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame."""
-    global device, last_ckpt, video_inpainting_sd, propainter
-
+    the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
+    "static-regions" / "follow-regions" (RoiConfig.max_regions > 1): one window per separate masked region (roi.plan_regions), each region an
+    ordinary clip call on its crop, the windows pasted one after another; with one region left this is the single-window path."""
     rcfg = roi_config(roi)
     if rcfg is not None and compat_reference_early_return:
         raise ValueError("roi= (mask-region inference) cannot be combined with compat_reference_early_return=True")
@@ -104,7 +106,14 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     dev = get_device()
     m = torch.from_numpy(np.stack([mm if mm.ndim == 3 else mm[..., None] for mm in mask_frames])).to(dev)
     dil_t = hip.mask_collapse_dilate(m.contiguous(), mask_dilation_iter)       # reference :27-31
-    plan = roi_plan.plan_roi(hip.mask_bbox(dil_t).cpu().numpy(), H0, W0, feather_px, rcfg) if rcfg is not None else None
+    if rcfg is not None and rcfg.max_regions > 1:
+        plans = _region_plans(dil_t, H0, W0, feather_px, rcfg)
+        if plans is not None and len(plans) > 1:
+            return _run_regions(frames_rgb, dil_t, plans, propainer_frames, ckpt, dev, max_img_size, feather_px if keep_unmasked_original else -1.0,
+                                prog, num_inference_steps, scheduler)
+        plan = None if plans is None else plans[0]          # one region (or none): the single-window (or full-frame) path below
+    else:
+        plan = roi_plan.plan_roi(hip.mask_bbox(dil_t).cpu().numpy(), H0, W0, feather_px, rcfg) if rcfg is not None else None
     dilated_mask_frames = list(dil_t.cpu().numpy())
     full_frames = frames_rgb
     if plan is not None:      # the model, and the prior when it is computed here, see only the windows
@@ -113,31 +122,15 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
             propainer_frames = plan.crop(propainer_frames)
 
     if prog is not None: prog(10, "loading weights")
-    if last_ckpt != ckpt or video_inpainting_sd is None:                        # reference :35-45 (ckpt forced to "2-Step")
-        device = dev
-        ckpt = "2-Step"
-        last_ckpt = ckpt
-        video_inpainting_sd = DiffuEraser(device, "stable-diffusion-v1-5/stable-diffusion-v1-5", "stabilityai/sd-vae-ft-mse",
-                                          "lixiaowen/diffuEraser", ckpt=ckpt, run=_run_config, dist=_dist, gather=_gather,
-                                          weights=_resolve_weights(ckpt)[0])
+    _load_model(dev, ckpt)
 
     if propainer_frames is None:                                                # reference :47-57
-        if propainter is None:
-            w, stages = _resolve_weights("2-Step")
-            propainter = Propainter("ruffy369/propainter", device=device, weights=w if (w is not None and "raft" in w.components) else None, **stages)
+        _load_prior()
         if prog is not None: prog(20, "running propainter prior")
-        prev_tag, hip.PROFILE_TAG = hip.PROFILE_TAG, "prior:"                   # bench.py --prior raft prices the prior's kernels under this prefix
-        try:
-            propainer_frames = propainter.forward(frames_rgb, dilated_mask_frames, ref_stride=10, neighbor_length=10,
-                                                  subvideo_length=50, mask_dilation=0, progress=prog)
-        finally:
-            hip.PROFILE_TAG = prev_tag
+        propainer_frames = _run_prior(frames_rgb, dilated_mask_frames, prog)
 
     if prog is not None: prog(50, "running DiffuEraser")
-    guidance_scale = None
-    inpainted_frames = video_inpainting_sd.forward(frames_rgb, dilated_mask_frames, propainer_frames, max_img_size=max_img_size,
-                                                   mask_dilation_iter=0, guidance_scale=guidance_scale, progress=prog,
-                                                   num_inference_steps=num_inference_steps, scheduler=scheduler)
+    inpainted_frames = _run_model(frames_rgb, dilated_mask_frames, propainer_frames, max_img_size, prog, num_inference_steps, scheduler)
 
     if prog is not None: prog(90, "resizing and merging finished frames")
     if plan is not None:
@@ -159,6 +152,108 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     for j, i in enumerate(idx):
         inpainted_frames[i] = out[j]
     return inpainted_frames
+
+
+def _load_model(dev, ckpt):
+    global device, last_ckpt, video_inpainting_sd
+    if last_ckpt != ckpt or video_inpainting_sd is None:                        # reference :35-45 (ckpt forced to "2-Step")
+        device = dev
+        ckpt = "2-Step"
+        last_ckpt = ckpt
+        video_inpainting_sd = DiffuEraser(device, "stable-diffusion-v1-5/stable-diffusion-v1-5", "stabilityai/sd-vae-ft-mse",
+                                          "lixiaowen/diffuEraser", ckpt=ckpt, run=_run_config, dist=_dist, gather=_gather,
+                                          weights=_resolve_weights(ckpt)[0])
+
+
+def _load_prior():
+    global propainter
+    if propainter is None:
+        w, stages = _resolve_weights("2-Step")
+        propainter = Propainter("ruffy369/propainter", device=device, weights=w if (w is not None and "raft" in w.components) else None, **stages)
+
+
+def _run_prior(frames_rgb, dilated_mask_frames, prog):
+    prev_tag, hip.PROFILE_TAG = hip.PROFILE_TAG, "prior:"                       # bench.py --prior raft prices the prior's kernels under this prefix
+    try:
+        return propainter.forward(frames_rgb, dilated_mask_frames, ref_stride=10, neighbor_length=10, subvideo_length=50, mask_dilation=0,
+                                  progress=prog)
+    finally:
+        hip.PROFILE_TAG = prev_tag
+
+
+def _run_model(frames_rgb, dilated_mask_frames, propainer_frames, max_img_size, prog, num_inference_steps, scheduler):
+    guidance_scale = None
+    return video_inpainting_sd.forward(frames_rgb, dilated_mask_frames, propainer_frames, max_img_size=max_img_size, mask_dilation_iter=0,
+                                       guidance_scale=guidance_scale, progress=prog, num_inference_steps=num_inference_steps, scheduler=scheduler)
+
+
+REGION_TILE = 16        # px: the occupancy grid the regions are labelled on (roi.label_tiles coarsens it for salt-like masks)
+
+
+def _region_plans(dil_t, H0, W0, feather_px, cfg):
+    """roi.plan_regions for the dilated masks: tile occupancy on the device, its components on the host, then one box per (frame, component)
+    from the occupied tiles only (T * K * 16 bytes come back)."""
+    occ = hip.mask_tile_union(dil_t, REGION_TILE).cpu().numpy()
+    labels, K, tile = roi_plan.label_tiles(occ, tile=REGION_TILE)
+    if K == 0:
+        return None
+    ty, tx = np.nonzero(labels >= 0)
+    tiles = torch.from_numpy(np.stack([ty, tx, labels[ty, tx]], axis=1).astype(np.int32)).to(dil_t.device)
+    return roi_plan.plan_regions(hip.mask_bbox_tiles(dil_t, tile, tiles, K).cpu().numpy(), H0, W0, feather_px, cfg)
+
+
+def _region_progress(prog, k, n, lo, hi):
+    """Progress of region k's sub-call (its own values in [lo, hi]) mapped into region k's share of (lo, hi), never onto lo or hi themselves,
+    so the caller still sees each of 5 / 10 / 20 / 50 / 90 once and non-decreasing values."""
+    if prog is None:
+        return None
+
+    def cb(v, s):
+        f = min(max((v - lo) / (hi - lo), 0.0), 1.0)
+        prog(min(max(lo + int((hi - lo) * (k + f) / n), lo + 1), hi - 1), f"region {k + 1}/{n}: {s}" if s else f"region {k + 1}/{n}")
+    return cb
+
+
+def _run_regions(frames_rgb, dil_t, plans, propainer_frames, ckpt, dev, max_img_size, feather_px, prog, num_inference_steps, scheduler):
+    """Several pairwise disjoint windows (roi.plan_regions): every region's prior, then every region's model, each an ordinary clip call on
+    that region's crop, one region after another; then the windows are pasted into the originals one after another."""
+    n = len(plans)
+    dil = list(dil_t.cpu().numpy())
+    crops = [(p.crop(frames_rgb), p.crop(dil)) for p in plans]
+    priors = [None if propainer_frames is None else p.crop(propainer_frames) for p in plans]
+    if prog is not None: prog(10, "loading weights")
+    _load_model(dev, ckpt)
+    if propainer_frames is None:
+        _load_prior()
+        if prog is not None: prog(20, "running propainter prior")
+        priors = [_run_prior(f, m, _region_progress(prog, k, n, 20, 50)) for k, (f, m) in enumerate(crops)]
+    if prog is not None: prog(50, "running DiffuEraser")
+    outs = [_run_model(f, m, priors[k], max_img_size, _region_progress(prog, k, n, 50, 90), num_inference_steps, scheduler)
+            for k, (f, m) in enumerate(crops)]
+    if prog is not None: prog(90, "resizing and merging finished frames")
+    return _paste_regions(outs, frames_rgb, dil_t, plans, feather_px, dev)
+
+
+def _paste_regions(outs, frames_rgb, dil_t, plans, feather_px, dev):
+    """Each region's window frames into the originals: roi_paste_composite once per region, the output of region k the original of region
+    k + 1 (two buffers, one upload, one download).  Exact because the windows are disjoint: inside window k the mask holds only region k's
+    pixels and no other region has touched the bytes."""
+    idx = [i for i in range(len(outs[0])) if outs[0][i] is not None]          # multi-GPU "rank0" gather, as in _paste_windows
+    if not idx:
+        return outs[0]
+    bufs = [torch.from_numpy(np.stack([frames_rgb[i] for i in idx])).to(dev).contiguous()]
+    bufs.append(torch.empty_like(bufs[0]))
+    mask = dil_t[idx].contiguous()
+    for k, (plan, o) in enumerate(zip(plans, outs)):
+        h, w = plan.size
+        patch = torch.from_numpy(np.stack([o[i] for i in idx])).to(dev)
+        offs = torch.from_numpy(np.ascontiguousarray(plan.offsets[idx])).to(dev)
+        hip.roi_paste_composite(patch.contiguous(), bufs[k % 2], mask, offs, h, w, float(feather_px), out=bufs[(k + 1) % 2])
+    out = bufs[len(plans) % 2].cpu().numpy()
+    res = list(outs[0])
+    for j, i in enumerate(idx):
+        res[i] = out[j]
+    return res
 
 
 def _paste_windows(inpainted_frames, frames_rgb, dil_t, plan, feather_px, dev):
@@ -203,9 +298,10 @@ def main():
     ap.add_argument("--start_frame", type=int, default=0, help="Index of first frame to process (default: 0).")
     ap.add_argument("--max_frames", type=int, default=-1, help="Max number of frames to process after start_frame.")
     ap.add_argument("--out", type=str, default=None, help="Output video path (default: <input>_vanished.mkv)")
-    ap.add_argument("--roi", choices=roi_plan.MODES, default=None,
+    ap.add_argument("--roi", choices=roi_plan.SPELLINGS, default=None,
                     help="Mask-region inference: run the model only on a window around the masks (static: one window per clip; follow: "
-                         "a window that follows the mask).  Pixels outside the window stay the original ones.")
+                         "a window that follows the mask; static-regions / follow-regions: one such window per separate masked region).  "
+                         "Pixels outside the windows stay the original ones.")
     args = ap.parse_args()
 
     assert os.path.isfile(args.color_video), "input video missing"

@@ -308,6 +308,15 @@ int vv_mask_bbox(const uint8_t* mask2d, int T, int H, int W, int* bbox, void* st
  * the full-frame mask2d [T][H0][W0] (as vv_feather_composite).  Byte-identical to that chain.  feather_px < 0: plain paste (mask2d may be NULL). */
 int vv_roi_paste_composite(const uint8_t* patch, int Hm, int Wm, const uint8_t* orig, const uint8_t* mask2d, const int* offsets, int T, int H0, int W0,
                            int h, int w, float feather_px, uint8_t* out, void* stream);
+/* vv_mask_tile_union: occ [ceil(H/tile)][ceil(W/tile)] = 1 where any of the T frames of mask2d [T][H][W] has a non-zero byte in that tile x tile
+ * cell, else 0 (the launcher zeroes occ; every writer stores the same byte: deterministic).  Bad arguments (NULL, T <= 0 or > 65535, tile <= 0,
+ * H <= 0, W <= 0) -> VV_E_ARG before any device work. */
+int vv_mask_tile_union(const uint8_t* mask2d, int T, int H, int W, int tile, uint8_t* occ, void* stream);
+/* vv_mask_bbox_tiles: bbox [T][K][4] = half-open (y0, x0, y1, x1) of the non-zero bytes of label k in frame t, (0, 0, 0, 0) when there is none;
+ * tiles [n][3] = (ty, tx, label) on the device: the occupied tile x tile cells and their labels.  Only the listed tiles are read; an entry
+ * outside the grid or with a label outside [0, K) is skipped.  Deterministic (integer min / max).  NULL, T <= 0 or > 65535, tile <= 0,
+ * H <= 0, W <= 0, n < 0, K <= 0 -> VV_E_ARG. */
+int vv_mask_bbox_tiles(const uint8_t* mask2d, int T, int H, int W, int tile, const int* tiles, int n, int K, int* bbox, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K9/K10  RAFT correlation lookup + recurrent-update pieces + convex upsampling, bilinear warp, forward/backward

@@ -106,6 +106,7 @@ class AttnParams(C.Structure):
 EXPORTS = ["vv_abi_version", "vv_last_error", "vv_device_count", "vv_device_name", "vv_conv_gemm", "vv_groupnorm_nsplit",
            "vv_groupnorm", "vv_layernorm", "vv_attention", "vv_axpby_f32", "vv_silu_f32", "vv_sched_step", "vv_add_inplace",
            "vv_mask_collapse_dilate", "vv_resize_bilinear_u8", "vv_resize_nearest_u8", "vv_feather_composite", "vv_chamfer_dt", "vv_mask_bbox", "vv_roi_paste_composite",
+           "vv_mask_tile_union", "vv_mask_bbox_tiles",
            "vv_preprocess", "vv_brushnet_input", "vv_pad_channels", "vv_decode_blend", "vv_blur_compose",
            "vv_avgpool2_f32", "vv_corr_lookup", "vv_raft_ctx_split", "vv_raft_flow_prep", "vv_gru_rh", "vv_gru_update", "vv_add_flow",
            "vv_add_relu_f32", "vv_convex_upsample", "vv_fb_valid", "vv_deform_im2col", "vv_fc_input", "vv_upsample2x_bilinear", "vv_flow_combine", "vv_gather_rows", "vv_fold_patches", "vv_flow_down4", "vv_gen_compose", "vv_gen_input", "vv_prop_fill", "vv_prop_combine", "vv_masked_sum_u8", "vv_u8_to_f32", "vv_u8_is_zero",
@@ -512,16 +513,45 @@ def mask_bbox(mask2d):
     return bbox
 
 
-def roi_paste_composite(patch, orig, mask2d, offsets, h, w, feather_px):
+def mask_tile_union(mask2d, tile):
+    """mask2d [T,H,W] u8 -> [ceil(H/tile), ceil(W/tile)] u8 on the device: 1 where any frame has a non-zero byte in that tile, else 0."""
+    _need_cuda(mask2d)
+    T, H, W = mask2d.shape
+    occ = torch.empty(((H + tile - 1) // tile, (W + tile - 1) // tile), dtype=torch.uint8, device=mask2d.device)
+    with _Prof("mask_tile_union", 0.0, T * H * W + occ.numel()):
+        _check(lib().vv_mask_tile_union(_p(mask2d), T, H, W, int(tile), _p(occ), _stream()), "vv_mask_tile_union")
+    return occ
+
+
+def mask_bbox_tiles(mask2d, tile, tiles, K):
+    """mask2d [T,H,W] u8, tiles [n,3] int32 (ty, tx, label) on the device -> [T,K,4] int32: half-open (y0, x0, y1, x1) of label k's non-zero bytes in
+    frame t, (0, 0, 0, 0) when there is none.  Reads only the listed tiles; entries outside the grid or with a label outside [0, K) are ignored."""
+    _need_cuda(mask2d, tiles)
+    T, H, W = mask2d.shape
+    if tiles.dtype != torch.int32 or tiles.dim() != 2 or tiles.shape[1] != 3 or not tiles.is_contiguous():
+        raise RuntimeError("mask_bbox_tiles: tiles must be a contiguous [n,3] int32 tensor")
+    n = tiles.shape[0]
+    if n == 0:                                   # no tile to read (an empty tensor has no address to hand over)
+        return torch.zeros((T, K, 4), dtype=torch.int32, device=mask2d.device)
+    bbox = torch.empty((T, K, 4), dtype=torch.int32, device=mask2d.device)
+    with _Prof("mask_bbox_tiles", 0.0, n * T * tile * tile + bbox.numel() * 4):
+        _check(lib().vv_mask_bbox_tiles(_p(mask2d), T, H, W, int(tile), _p(tiles), n, int(K), _p(bbox), _stream()), "vv_mask_bbox_tiles")
+    return bbox
+
+
+def roi_paste_composite(patch, orig, mask2d, offsets, h, w, feather_px, out=None):
     """patch [T,Hm,Wm,3] u8 (model output of the window), orig [T,H0,W0,3] u8, mask2d [T,H0,W0] u8, offsets [T,2] int32 (oy, ox) -> [T,H0,W0,3]:
     resize_u8(patch -> h, w) pasted at each frame's offset into orig, then feather_composite(., orig, mask2d, feather_px) -- in one pass.
-    feather_px < 0: plain paste (mask2d may be None)."""
-    _need_cuda(patch, orig, mask2d, offsets)
+    feather_px < 0: plain paste (mask2d may be None).  out: an optional [T,H0,W0,3] u8 buffer to write (not orig)."""
+    _need_cuda(patch, orig, mask2d, offsets, out)
     T, Hm, Wm, _ = patch.shape
     _, H0, W0, _ = orig.shape
     if offsets.dtype != torch.int32 or tuple(offsets.shape) != (T, 2) or orig.shape[0] != T or patch.shape[3] != 3 or orig.shape[3] != 3 or (mask2d is not None and tuple(mask2d.shape) != (T, H0, W0)):
         raise RuntimeError("roi_paste_composite: shapes / dtypes do not match")
-    out = torch.empty_like(orig)
+    if out is None:
+        out = torch.empty_like(orig)
+    elif out.shape != orig.shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.data_ptr() == orig.data_ptr():
+        raise RuntimeError("roi_paste_composite: out must be a contiguous u8 buffer of orig's shape, not orig itself")
     with _Prof("roi_paste_composite", 0.0, T * H0 * W0 * (3 + 1 + 3) + patch.numel()):
         _check(lib().vv_roi_paste_composite(_p(patch), Hm, Wm, _p(orig), _p(mask2d), _p(offsets), T, H0, W0, int(h), int(w), C.c_float(feather_px), _p(out),
                                             _stream()), "vv_roi_paste_composite")
