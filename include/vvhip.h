@@ -83,7 +83,7 @@ typedef struct {
     int32_t out_dtype;    /* VV_F32 or h16 */
     int32_t ldo;
     int32_t epilogue;     /* VV_EPI_* ; GEGLU expects weight rows interleaved in blocks of 16: [v0..15 g0..15 v16..] */
-    float out_scale;      /* multiplies the accumulated product+bias before residuals (1.0f = none) */
+    float out_scale;      /* multiplies the accumulated product+bias before rowvec and residuals (1.0f = none; GEGLU: must be 1.0f) */
     int32_t ksize_w;      /* kernel width (0 = same as ksize); k = (ky*ksize_w + kx)*Cin + c */
     int32_t act;          /* VV_ACT_NONE, VV_ACT_RELU or VV_ACT_LRELU (slope act_slope) applied last (after residuals) */
     int32_t split_heads;  /* > 0: head-major store for a fused QKV projection (h16 out, no residuals): column n = (which, head, d) with
@@ -93,8 +93,10 @@ typedef struct {
     int32_t split_tokens; /* rows per batch element: row m = b*split_tokens + token; NEGATIVE: -split_tokens tokens per batch element
                              with token-major rows, m = token*(M/tokens) + b (temporal attention: token = frame, b = pixel) */
     int32_t tile_hint;    /* 0 = automatic tiling; 1 = 128-row tiles only; 2 / 3 = the 256-row tile kernel (2-phase / 8-phase form) whenever
-                             the shape is eligible (h16 sources with channel counts % 64 == 0, <= 9 taps, no fused resize,
-                             Npad % 320 or % 256 == 0; 8-phase: Npad % 256 == 0) */
+                             the shape is eligible (h16 sources with channel counts % 64 == 0, <= 9 taps, no fused resize, no scatter,
+                             Npad % 320 or % 256 == 0; 8-phase: Npad % 256 == 0); 4 = the 8-phase form with inline-asm LDS-DMA (what
+                             automatic tiling picks for it).  An ineligible shape silently takes the automatic choice among the 128-row
+                             kernels: vv_conv_gemm_route tells which kernel runs */
     float act_slope;      /* VV_ACT_LRELU: negative-side slope (ProPainter: 0.1 in the alignment offset stacks, 0.2 in the encoders) */
     /* ABI 9 -- output scatter (sc_oh > 0): row m = (f, y, x) of this launch's Hout x Wout grid is stored at (and its residuals are read from) row
        (f * sc_oh + y * sc_sy + sc_oy) * sc_ow + x * sc_sx + sc_ox of an [F][sc_oh][sc_ow][ldo] tensor.  One 3x3 convolution over a nearest-2x
@@ -112,6 +114,28 @@ typedef struct {
     float* gn_partials;
 } vv_conv_params;
 int vv_conv_gemm(const vv_conv_params* host_p, int dtype, void* stream);
+/* The kernel vv_conv_gemm would launch for these parameters, as a VV_ROUTE_* code (> 0), or the negative VV_E_* code it would refuse the launch
+   with (message in vv_last_error()).  Host only: the pointer fields are read as null / non-null flags and never dereferenced, no device is touched.
+   The launch path takes its decision from the same host functions, so the answer is the kernel that runs.
+   128-row kernels: route = loader + tile, tile = VV_ROUTE_TILE_* (the 128 x 320 tile: lab build only). */
+enum { VV_ROUTE_TILE_128x160 = 0, VV_ROUTE_TILE_128x128 = 1, VV_ROUTE_TILE_128x16 = 2, VV_ROUTE_TILE_128x320 = 3 };
+enum {
+    VV_ROUTE_GENERIC     = 0x10,   /* register-staged h16 im2col: channel counts not % 64, Kpad != K */
+    VV_ROUTE_GENERIC_F32 = 0x20,   /* register-staged fp32 source (channel counts not % 64, Kpad != K) */
+    VV_ROUTE_FAST        = 0x30,   /* LDS-DMA im2col, full gather state: fused resize or more than 9 taps */
+    VV_ROUTE_FAST32      = 0x40,   /* LDS-DMA of an fp32 source, rounded to h16 when the operand is read */
+    VV_ROUTE_HALO        = 0x50,   /* 8 x 16-pixel halo tile: 3x3 pad 1 / 2x2 pad 0-1, stride 1, no resize */
+    VV_ROUTE_LIN         = 0x60,   /* plain [M][K] rows: linear layers, 1x1 stride-1 convolutions of one source */
+    VV_ROUTE_FAST9       = 0x70,   /* LDS-DMA im2col, at most 9 taps, no resize */
+    VV_ROUTE_HALO_GN     = 0x80,   /* the 128 x 160 halo tile that also writes gn_partials (always VV_ROUTE_TILE_128x160) */
+    /* 256-row kernels (vv_gemm256.hip); LIN = plain rows (as VV_ROUTE_LIN), CONV = im2col gather (<= 9 taps, stride 1/2, concat, no resize) */
+    VV_ROUTE_256x320_LIN = 0x100, VV_ROUTE_256x320_CONV = 0x101,   /* 2-phase, 256 x 320 tile */
+    VV_ROUTE_256x256_LIN = 0x102, VV_ROUTE_256x256_CONV = 0x103,   /* 2-phase, 256 x 256 tile (Npad % 320 != 0, or GEGLU) */
+    VV_ROUTE_256P8_LIN   = 0x104, VV_ROUTE_256P8_CONV   = 0x105,   /* 8-phase, 256 x 256, builtin LDS-DMA (tile_hint 3) */
+    VV_ROUTE_256P8A_LIN  = 0x106, VV_ROUTE_256P8A_CONV  = 0x107,   /* 8-phase, 256 x 256, inline-asm LDS-DMA (automatic choice, tile_hint 4) */
+    VV_ROUTE_HALO256     = 0x200   /* lab build only: the opt-in 256-pixel halo kernel (vv_conv3.hip) */
+};
+int vv_conv_gemm_route(const vv_conv_params* host_p, int dtype);
 int vv_conv_gn_partial_blocks(int Hout, int Wout);
 /* (mean, rstd) [F][groups][2] -- the layout vv_gn_affine / vv_gn_affine_frames and vv_groupnorm_apply_fin read -- from per-channel partials [F][nblk][C][2];
    pool_frames = 1: one (mean, rstd) per group over the whole clip, replicated per frame.  Double accumulation in a fixed order. */

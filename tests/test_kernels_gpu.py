@@ -60,7 +60,7 @@ def test_conv_gemm(gpu, dname, td, ulp, case, monkeypatch):
     if case.get("halo256"):
         # the 256-pixel halo kernel (vv_conv3.hip) exists only in the lab build (VV_AB=1 build.sh); in the product library these cases would
         # silently repeat the generic path
-        if not hasattr(hip.lib(), "vv_conv3_halo_try"):
+        if not hasattr(hip.lib(), "vv_conv3_halo_launch"):
             pytest.skip("lab build only: vv_conv3.hip is not part of the product library")
         monkeypatch.setenv("VV_CONV3_HALO256", "1")
     out = hip.conv_gemm(dt, xin, wp.to(gpu), cout, K, F=Fr, Hin=H, Win=W, Hout=Ho, Wout=Wo, ksize=k, stride=stride, pad_t=k // 2,
@@ -273,8 +273,14 @@ def test_gemm_tile_forms_agree_on_every_epilogue(gpu, dname, td, ulp, M, K, N, f
         kw.update(split_heads=N // 3 // 80, split_dim=80, split_tokens=M // 2)      # two batch elements
     xg = x.to(td).to(gpu)
     outs = {}
+    # the kernel each hint names is the kernel that runs (vv_conv_gemm_route): an ineligible case would silently compare the 128-row tile with itself
+    want = {1: lambda r: 0 < r < hip.ROUTE_256x320_LIN,
+            2: lambda r: r == (hip.ROUTE_256x320_LIN if (N % 320 == 0 and not geglu) else hip.ROUTE_256x256_LIN),
+            3: lambda r: r == hip.ROUTE_256P8_LIN}
     for hint in (1, 2) + ((3,) if (N % 256 == 0 and ("p8" in flags or geglu)) else ()):
         out = torch.zeros(M, N // 2 if geglu else N, dtype=torch.float32 if f32out else td, device=gpu)
+        route = hip.conv_gemm_route(dt, xg, wp, N, K, out=out, tile_hint=hint, **kw)
+        assert route > 0 and want[hint](route), f"tile_hint {hint} runs {hip.route_name(route) if route > 0 else route}"
         hip.conv_gemm(dt, xg, wp, N, K, out=out, tile_hint=hint, **kw)
         outs[hint] = out.float().cpu()
     for hint, o in outs.items():

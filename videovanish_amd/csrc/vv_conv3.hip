@@ -231,9 +231,9 @@ int launch(const vv_conv_params& p, hipStream_t st) {
 
 }  // namespace
 
-// Internal entry (called by vv_conv_gemm's dispatcher, not exported in include/vvhip.h): returns VV_OK after launching, or
-// a negative value < -1000 when the shape is not eligible (caller falls through to the generic kernels).
-extern "C" int vv_conv3_halo_try(const vv_conv_params* pp, int dtype, void* stream) {
+// Internal entries (vv_conv_gemm's dispatcher, not exported in include/vvhip.h).  vv_conv3_halo_eligible (host only, reads the fields of p): 1 when
+// the dispatcher takes this kernel (vv_conv_gemm_route reports it as VV_ROUTE_HALO256), else 0; vv_conv3_halo_launch launches it.
+extern "C" int vv_conv3_halo_eligible(const vv_conv_params* pp) {
     const vv_conv_params& p = *pp;
     // measured slower than the 128-pixel halo tile of vv_conv_gemm at 3 blocks per CU (profiles/r1_gemm_ab.txt, seventh A/B): the
     // eight waves of the single resident block run in lockstep behind the barrier, LDS reads and MFMAs do not overlap -> opt-in
@@ -241,11 +241,16 @@ extern "C" int vv_conv3_halo_try(const vv_conv_params* pp, int dtype, void* stre
     const bool off = !(e && e[0] == '1');
     const int kw = p.ksize_w > 0 ? p.ksize_w : p.ksize;
     if (off || p.in_dtype == VV_F32 || p.ksize != 3 || kw != 3 || p.stride != 1 || p.pad_t != 1 || p.pad_l != 1 || p.Hv != p.Hin || p.Wv != p.Win ||
-        p.Hout != p.Hin || p.Wout != p.Win || p.epilogue == VV_EPI_GEGLU || p.C0 % 64 || p.C1 % 64 || p.Kpad != p.K) return -2000;
-    if (p.Npad % 160 != 0 && p.Npad % 128 != 0) return -2000;
+        p.Hout != p.Hin || p.Wout != p.Win || p.epilogue == VV_EPI_GEGLU || p.C0 % 64 || p.C1 % 64 || p.Kpad != p.K) return 0;
+    if (p.Npad % 160 != 0 && p.Npad % 128 != 0) return 0;
     const int64_t cover = (int64_t)((p.Hin + 15) / 16) * 16 * ((p.Win + 15) / 16) * 16;
-    if (cover * 10 > (int64_t)p.Hin * p.Win * 11) return -2000;                      // patch grid wastes > 10 %
-    if ((int64_t)p.F * p.Hin * p.Win > 0x7fffffff) return -2000;
+    if (cover * 10 > (int64_t)p.Hin * p.Win * 11) return 0;                          // patch grid wastes > 10 %
+    if ((int64_t)p.F * p.Hin * p.Win > 0x7fffffff) return 0;
+    return 1;
+}
+
+extern "C" int vv_conv3_halo_launch(const vv_conv_params* pp, int dtype, void* stream) {
+    const vv_conv_params& p = *pp;
     hipStream_t st = (hipStream_t)stream;
     if (p.Npad % 160 == 0) return dtype == VV_BF16 ? launch<BF16, 5>(p, st) : launch<F16, 5>(p, st);
     return dtype == VV_BF16 ? launch<BF16, 4>(p, st) : launch<F16, 4>(p, st);

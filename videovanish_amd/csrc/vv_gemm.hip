@@ -19,14 +19,16 @@
 #include "vv_common.h"
 #include "vv_gemm_epilogue.h"
 
-extern "C" int vv_gemm256_try(const vv_conv_params* pp, int dtype, int force, void* stream);
+extern "C" int vv_gemm256_route(const vv_conv_params* pp, int force);
+extern "C" int vv_gemm256_launch(const vv_conv_params* pp, int dtype, int route, void* stream);
 
 // A/B switches of the lab build (-DVV_AB: environment variables read once per process).  The product build takes the measured
 // defaults (profiles/r1_gemm_ab.txt) with no getenv in any launch path.
 #ifdef VV_AB
 #define VV_AB_ENV(name) (getenv(name) != nullptr)
 #define VV_AB_INT(name, dflt) (getenv(name) ? atoi(getenv(name)) : (dflt))
-extern "C" int vv_conv3_halo_try(const vv_conv_params* pp, int dtype, void* stream);
+extern "C" int vv_conv3_halo_eligible(const vv_conv_params* pp);
+extern "C" int vv_conv3_halo_launch(const vv_conv_params* pp, int dtype, void* stream);
 #else
 #define VV_AB_ENV(name) false
 #define VV_AB_INT(name, dflt) (dflt)
@@ -441,70 +443,112 @@ int launch_cfg(const vv_conv_params& p, int M, hipStream_t st) {
     return VV_OK;
 }
 
-template <typename T, int MODE>
-int launch_t(const vv_conv_params& p, int M, hipStream_t st) {
+// ---- dispatch.  The choice of kernel is made on the host, from the fields of the parameters alone, by conv_route (loader, tile, the 256-row forms of
+// vv_gemm256_route): vv_conv_gemm launches the route it returns and vv_conv_gemm_route reports it -- one copy of the rules.
+
+// tile of the 128-row kernels for a loader: VV_ROUTE_TILE_*, or a VV_E_* code
+int tile_of(const vv_conv_params& p, int mode, int M) {
     // tile choice: GEGLU needs an even number of N tiles per wave; N % 160 == 0 -> 128x160; tiny N -> 128x16
 #ifdef VV_AB      // lab: 128 x 320 tile (wave tile 64 x 160: 14 operand fragments per 40 MFMAs instead of 9 per 20; 2 blocks per CU), profiles/r3_gemm_n320_ab.txt
     static const bool n320 = VV_AB_ENV("VV_GEMM_N320");
-    if constexpr (MODE != MODE_H16 && MODE != MODE_F32) {
-        if (n320 && p.Npad % 320 == 0 && M >= 4096) return launch_cfg<T, 2, 2, 4, 10, MODE>(p, M, st);
-    }
+    if (mode != MODE_H16 && mode != MODE_F32 && n320 && p.Npad % 320 == 0 && M >= 4096) return VV_ROUTE_TILE_128x320;
 #endif
-    if (p.epilogue == VV_EPI_GEGLU) return launch_cfg<T, 2, 2, 4, 4, MODE>(p, M, st);
+    if (p.epilogue == VV_EPI_GEGLU) {
+        if (p.Npad % 128 != 0) VV_FAIL(VV_E_ARG, "vv_conv_gemm: Npad %d not a multiple of tile N %d", p.Npad, 128);
+        return VV_ROUTE_TILE_128x128;
+    }
     // N a multiple of both: the 128x128 tile runs 4 blocks per CU (128 VGPRs) against 3 for 128x160 -> +2..8 % on the LDS-DMA
     // loaders when there are enough row tiles (profiles/r1_gemm_ab.txt, eighth A/B)
     // (opt-in: in the pipeline the 3x3 convs lose 2-3 % with it, and the linear layers now run 128x160 at 4 blocks through LIN)
     static const bool pref128 = VV_AB_ENV("VV_GEMM_PREF128") && !VV_AB_ENV("VV_GEMM_NO_OCC4");
-    if (pref128 && p.Npad % 128 == 0 && (MODE == MODE_FAST || MODE == MODE_HALO) && M >= 16384) return launch_cfg<T, 2, 2, 4, 4, MODE>(p, M, st);
-    if (p.Npad % 160 == 0) return launch_cfg<T, 2, 2, 4, 5, MODE>(p, M, st);   // (a 256x160 4-wave tile measured the same: profiles/r1_gemm_ab.txt)
-    if (p.Npad % 128 == 0) return launch_cfg<T, 2, 2, 4, 4, MODE>(p, M, st);
-    if (p.Npad % 16 == 0 && p.Npad <= 64) return launch_cfg<T, 4, 1, 2, 1, MODE>(p, M, st);
+    if (pref128 && p.Npad % 128 == 0 && (mode == MODE_FAST || mode == MODE_HALO) && M >= 16384) return VV_ROUTE_TILE_128x128;
+    if (p.Npad % 160 == 0) return VV_ROUTE_TILE_128x160;   // (a 256x160 4-wave tile measured the same: profiles/r1_gemm_ab.txt)
+    if (p.Npad % 128 == 0) return VV_ROUTE_TILE_128x128;
+    if (p.Npad % 16 == 0 && p.Npad <= 64) return VV_ROUTE_TILE_128x16;
     VV_FAIL(VV_E_ARG, "vv_conv_gemm: unsupported Npad %d (need %%160, %%128 or 16..64 %%16)", p.Npad);
 }
 
-template <typename T>
-int launch_mode(const vv_conv_params& p, int M, hipStream_t st) {
+constexpr int kLoaderRoute[] = {VV_ROUTE_GENERIC, VV_ROUTE_GENERIC_F32, VV_ROUTE_FAST, VV_ROUTE_FAST32, VV_ROUTE_HALO, VV_ROUTE_LIN, VV_ROUTE_FAST9};   // [MODE_*]
+
+// route of a launch whose arguments conv_validate accepted: a VV_ROUTE_* code, or the VV_E_* code the launch is refused with
+int conv_route(const vv_conv_params& p) {
+    const int M = (int)((int64_t)p.F * p.Hout * p.Wout);
     const bool fast = (p.C0 % 64 == 0) && (p.C1 % 64 == 0) && p.Kpad == p.K;
-    static const bool no32 = VV_AB_ENV("VV_GEMM_NO_FAST32");
-    constexpr int dt = std::is_same<T, BF16>::value ? VV_BF16 : VV_F16;
     if (p.gn_partials) {      // GroupNorm partials out of the epilogue: only the 128 x 160 halo-tile kernel with the staged fp32 epilogue writes them (vvhip.h)
         const bool ok = fast && p.in_dtype != VV_F32 && p.ksize == 3 && (p.ksize_w == 0 || p.ksize_w == 3) && p.pad_t == 1 && p.pad_l == 1 && p.stride == 1 && p.sc_oh == 0 &&
                         p.Hv == p.Hin && p.Wv == p.Win && p.Hout == p.Hin && p.Wout == p.Win && p.epilogue != VV_EPI_GEGLU && p.Npad % 160 == 0 && (p.N & 3) == 0 && (p.ldo & 3) == 0 &&
                         p.out_dtype == VV_F32 && p.split_heads <= 0 && !p.rowvec && !p.res1 && p.act == VV_ACT_NONE && (!p.res0 || p.res_dtype == VV_F32);
         if (!ok) VV_FAIL(VV_E_UNSUPPORTED, "vv_conv_gemm: gn_partials needs the 128 x 160 halo-tile 3x3 kernel with the staged fp32 epilogue (see vvhip.h)");
+        return VV_ROUTE_HALO_GN;
+    }
+    if (p.tile_hint != 1) {   // compute-bound shapes: the 256-row tile kernel (vv_gemm256.hip)
+        const int r = vv_gemm256_route(&p, p.tile_hint >= 2 ? p.tile_hint - 1 : 0);
+        if (r) return r;
+    }
+#ifdef VV_AB
+    if (p.sc_oh == 0 && vv_conv3_halo_eligible(&p)) return VV_ROUTE_HALO256;   // opt-in 256-pixel halo kernel (vv_conv3.hip; measured slower than the 128-row halo tile); it has no output scatter
+#endif
+    static const bool no32 = VV_AB_ENV("VV_GEMM_NO_FAST32");
+    static const bool nohalo = VV_AB_ENV("VV_GEMM_NO_HALO");
+    static const bool nolin = VV_AB_ENV("VV_GEMM_NO_LIN");
+    static const bool no9 = VV_AB_ENV("VV_GEMM_NO_FAST9");
+    int mode;
+    // 3x3 / pad 1, and (round 5) the 2x2 / pad 0 or 1 parity convolutions of nn.UpConv2x with their scattered store: the 10 x 18 halo of an 8 x 16 patch starts
+    // at (y0 - pad_t, x0 - pad_l) and holds every tap of both kernel sizes
+    const bool halo3 = p.ksize == 3 && (p.ksize_w == 0 || p.ksize_w == 3) && p.pad_t == 1 && p.pad_l == 1 && p.sc_oh == 0;
+    const bool halo2 = p.ksize == 2 && (p.ksize_w == 0 || p.ksize_w == 2) && p.pad_t >= 0 && p.pad_t <= 1 && p.pad_l >= 0 && p.pad_l <= 1;
+    // patch grid waste <= 15 % (the halo tile is worth 17-25 %)
+    const int64_t cover = (int64_t)((p.Hin + 7) / 8) * 8 * ((p.Win + 15) / 16) * 16;
+    if (fast && !nohalo && p.in_dtype != VV_F32 && (halo3 || halo2) && p.stride == 1 &&
+        p.Hv == p.Hin && p.Wv == p.Win && p.Hout == p.Hin && p.Wout == p.Win && p.epilogue != VV_EPI_GEGLU && (p.Npad % 160 == 0 || p.Npad % 128 == 0 || (p.Npad % 16 == 0 && p.Npad <= 64)) &&      // (the narrow tile: conv_out layers, 4 MFMAs per k tile -- all data movement, the halo saves 3/4 of it)
+        cover * 100 <= (int64_t)p.Hin * p.Win * 115) mode = MODE_HALO;
+    else if (fast && !nolin && p.in_dtype != VV_F32 && p.ksize == 1 && p.ksize_w <= 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.C1 == 0 &&
+             p.Hv == p.Hin && p.Wv == p.Win && p.Hout == p.Hin && p.Wout == p.Win) mode = MODE_LIN;
+    else if (p.in_dtype == VV_F32) mode = (fast && !no32) ? MODE_FAST32 : MODE_F32;
+    else if (fast && !no9 && p.Hv == p.Hin && p.Wv == p.Win && p.ksize * (p.ksize_w > 0 ? p.ksize_w : p.ksize) <= 9) mode = MODE_FAST9;
+    else mode = fast ? MODE_FAST : MODE_H16;
+    const int tile = tile_of(p, mode, M);
+    if (tile < 0) return tile;
+    return kLoaderRoute[mode] + tile;
+}
+
+template <typename T, int MODE>
+int launch_t(const vv_conv_params& p, int M, int tile, hipStream_t st) {
+    switch (tile) {
+#ifdef VV_AB
+    case VV_ROUTE_TILE_128x320: if constexpr (MODE != MODE_H16 && MODE != MODE_F32) return launch_cfg<T, 2, 2, 4, 10, MODE>(p, M, st); break;
+#endif
+    case VV_ROUTE_TILE_128x160: return launch_cfg<T, 2, 2, 4, 5, MODE>(p, M, st);
+    case VV_ROUTE_TILE_128x128: return launch_cfg<T, 2, 2, 4, 4, MODE>(p, M, st);
+    case VV_ROUTE_TILE_128x16: return launch_cfg<T, 4, 1, 2, 1, MODE>(p, M, st);
+    }
+    VV_FAIL(VV_E_ARG, "vv_conv_gemm: tile %d of route", tile);
+}
+
+template <typename T>
+int launch_mode(const vv_conv_params& p, int M, int route, hipStream_t st) {
+    constexpr int dt = std::is_same<T, BF16>::value ? VV_BF16 : VV_F16;
+    if (route == VV_ROUTE_HALO_GN) {
         const int tilesM = p.F * ((p.Hin + 7) / 8) * ((p.Win + 15) / 16), tilesN = p.Npad / 160;
         hipLaunchKernelGGL((conv_gemm_kernel<T, 2, 2, 4, 5, MODE_HALO, 2, 64, 2, true>), dim3(tilesM * tilesN), dim3(256), 0, st, p, M, tilesM, tilesN);      // its own instantiation: the
         VV_CHECK_LAUNCH("vv_conv_gemm");                                                                                                                          // plain kernel keeps its registers
         return VV_OK;
     }
-    if (p.tile_hint != 1) {   // compute-bound shapes: the 256-row tile kernel (vv_gemm256.hip)
-        const int r = vv_gemm256_try(&p, dt, p.tile_hint >= 2 ? p.tile_hint - 1 : 0, (void*)st);
-        if (r > -1000) return r;
-    }
+    if (route >= VV_ROUTE_256x320_LIN && route <= VV_ROUTE_256P8A_CONV) return vv_gemm256_launch(&p, dt, route, (void*)st);
 #ifdef VV_AB
-    if (p.sc_oh == 0) {   // opt-in 256-pixel halo kernel (vv_conv3.hip; measured slower than the 128-row halo tile); it has no output scatter
-        const int r = vv_conv3_halo_try(&p, dt, (void*)st);
-        if (r > -1000) return r;
-    }
+    if (route == VV_ROUTE_HALO256) return vv_conv3_halo_launch(&p, dt, (void*)st);
 #endif
-    static const bool nohalo = VV_AB_ENV("VV_GEMM_NO_HALO");
-    // 3x3 / pad 1, and (round 5) the 2x2 / pad 0 or 1 parity convolutions of nn.UpConv2x with their scattered store: the 10 x 18 halo of an 8 x 16 patch starts
-    // at (y0 - pad_t, x0 - pad_l) and holds every tap of both kernel sizes
-    const bool halo3 = p.ksize == 3 && (p.ksize_w == 0 || p.ksize_w == 3) && p.pad_t == 1 && p.pad_l == 1 && p.sc_oh == 0;
-    const bool halo2 = p.ksize == 2 && (p.ksize_w == 0 || p.ksize_w == 2) && p.pad_t >= 0 && p.pad_t <= 1 && p.pad_l >= 0 && p.pad_l <= 1;
-    if (fast && !nohalo && p.in_dtype != VV_F32 && (halo3 || halo2) && p.stride == 1 &&
-        p.Hv == p.Hin && p.Wv == p.Win && p.Hout == p.Hin && p.Wout == p.Win && p.epilogue != VV_EPI_GEGLU && (p.Npad % 160 == 0 || p.Npad % 128 == 0 || (p.Npad % 16 == 0 && p.Npad <= 64))) {      // (the narrow tile: conv_out layers, 4 MFMAs per k tile -- all data movement, the halo saves 3/4 of it)
-        // patch grid waste <= 15 % (the halo tile is worth 17-25 %)
-        const int64_t cover = (int64_t)((p.Hin + 7) / 8) * 8 * ((p.Win + 15) / 16) * 16;
-        if (cover * 100 <= (int64_t)p.Hin * p.Win * 115) return launch_t<T, MODE_HALO>(p, M, st);
+    const int tile = route & 15;
+    switch (route & ~15) {
+    case VV_ROUTE_GENERIC: return launch_t<T, MODE_H16>(p, M, tile, st);
+    case VV_ROUTE_GENERIC_F32: return launch_t<T, MODE_F32>(p, M, tile, st);
+    case VV_ROUTE_FAST: return launch_t<T, MODE_FAST>(p, M, tile, st);
+    case VV_ROUTE_FAST32: return launch_t<T, MODE_FAST32>(p, M, tile, st);
+    case VV_ROUTE_HALO: return launch_t<T, MODE_HALO>(p, M, tile, st);
+    case VV_ROUTE_LIN: return launch_t<T, MODE_LIN>(p, M, tile, st);
+    case VV_ROUTE_FAST9: return launch_t<T, MODE_FAST9>(p, M, tile, st);
     }
-    static const bool nolin = VV_AB_ENV("VV_GEMM_NO_LIN");
-    if (fast && !nolin && p.in_dtype != VV_F32 && p.ksize == 1 && p.ksize_w <= 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.C1 == 0 &&
-        p.Hv == p.Hin && p.Wv == p.Win && p.Hout == p.Hin && p.Wout == p.Win) return launch_t<T, MODE_LIN>(p, M, st);
-    if (p.in_dtype == VV_F32) return (fast && !no32) ? launch_t<T, MODE_FAST32>(p, M, st) : launch_t<T, MODE_F32>(p, M, st);
-    static const bool no9 = VV_AB_ENV("VV_GEMM_NO_FAST9");
-    if (fast && !no9 && p.Hv == p.Hin && p.Wv == p.Win && p.ksize * (p.ksize_w > 0 ? p.ksize_w : p.ksize) <= 9) return launch_t<T, MODE_FAST9>(p, M, st);
-    return fast ? launch_t<T, MODE_FAST>(p, M, st) : launch_t<T, MODE_H16>(p, M, st);
+    VV_FAIL(VV_E_ARG, "vv_conv_gemm: unknown route %d", route);
 }
 
 }  // namespace
@@ -512,14 +556,14 @@ int launch_mode(const vv_conv_params& p, int M, hipStream_t st) {
 // Build split (build.sh): compiled twice, -DVV_DT_ONLY=0 = the BF16 instantiations behind vv_conv_gemm_launch_bf16, -DVV_DT_ONLY=1 = the F16 ones plus
 // the entry point (see vv_gemm256.hip).
 #if defined(VV_DT_ONLY) && VV_DT_ONLY == 0
-extern "C" int vv_conv_gemm_launch_bf16(const vv_conv_params* pp, int M, void* stream) { return launch_mode<BF16>(*pp, M, (hipStream_t)stream); }
+extern "C" int vv_conv_gemm_launch_bf16(const vv_conv_params* pp, int M, int route, void* stream) { return launch_mode<BF16>(*pp, M, route, (hipStream_t)stream); }
 #else
 #if defined(VV_DT_ONLY)
-extern "C" int vv_conv_gemm_launch_bf16(const vv_conv_params* pp, int M, void* stream);
+extern "C" int vv_conv_gemm_launch_bf16(const vv_conv_params* pp, int M, int route, void* stream);
 #endif
 extern "C" int vv_conv_gn_partial_blocks(int Hout, int Wout) { return ((Hout + 7) / 8) * ((Wout + 15) / 16) * 2; }      // 8 x 16 patches x 2 wave rows
 
-extern "C" int vv_conv_gemm(const vv_conv_params* pp, int dtype, void* stream) {
+extern "C" int vv_conv_gemm_route(const vv_conv_params* pp, int dtype) {
     if (!pp) VV_FAIL(VV_E_ARG, "vv_conv_gemm: null params");
     const vv_conv_params& p = *pp;
     if (dtype != VV_BF16 && dtype != VV_F16) VV_FAIL(VV_E_ARG, "vv_conv_gemm: dtype must be VV_BF16 or VV_F16");
@@ -535,7 +579,9 @@ extern "C" int vv_conv_gemm(const vv_conv_params* pp, int dtype, void* stream) {
     if (p.in_dtype != VV_F32 && p.in_dtype != dtype) VV_FAIL(VV_E_ARG, "vv_conv_gemm: in_dtype mismatch");
     if (p.out_dtype != VV_F32 && p.out_dtype != dtype) VV_FAIL(VV_E_ARG, "vv_conv_gemm: out_dtype mismatch");
     if ((p.res0 || p.res1) && p.res_dtype != VV_F32 && p.res_dtype != dtype) VV_FAIL(VV_E_ARG, "vv_conv_gemm: res_dtype mismatch");
-    if (p.epilogue == VV_EPI_GEGLU && (p.N % 32 || p.rowvec || p.res0 || p.res1 || (p.ldo & 3))) VV_FAIL(VV_E_ARG, "vv_conv_gemm: GEGLU needs N%%32==0, ldo%%4==0 and no residual/rowvec");
+    // (GEGLU and out_scale: the GEGLU epilogue has no scale step, so a scale != 1 is refused rather than dropped)
+    if (p.epilogue == VV_EPI_GEGLU && (p.N % 32 || p.rowvec || p.res0 || p.res1 || (p.ldo & 3) || p.out_scale != 1.0f))
+        VV_FAIL(VV_E_ARG, "vv_conv_gemm: GEGLU needs N%%32==0, ldo%%4==0, out_scale 1 and no residual/rowvec");
     const int64_t stok_ = p.split_tokens < 0 ? -(int64_t)p.split_tokens : p.split_tokens;
     if (p.split_heads > 0 && (p.split_dim <= 0 || (p.split_dim & 3) || stok_ <= 0 || p.N != 3 * p.split_heads * p.split_dim || p.out_dtype == VV_F32 ||
                               p.res0 || p.res1 || p.epilogue == VV_EPI_GEGLU || ((int64_t)p.F * p.Hout * p.Wout) % stok_ ||
@@ -552,12 +598,18 @@ extern "C" int vv_conv_gemm(const vv_conv_params* pp, int dtype, void* stream) {
         if ((int64_t)p.F * p.sc_oh * p.sc_ow > 0x7fffffff) VV_FAIL(VV_E_ARG, "vv_conv_gemm: more than 2^31 pixels");
     }
     if (M64 > 0x7fffffff || (int64_t)p.F * p.Hin * p.Win > 0x7fffffff) VV_FAIL(VV_E_ARG, "vv_conv_gemm: more than 2^31 pixels");
-    const int M = (int)M64;
-    hipStream_t st = (hipStream_t)stream;
+    return conv_route(p);
+}
+
+extern "C" int vv_conv_gemm(const vv_conv_params* pp, int dtype, void* stream) {
+    const int route = vv_conv_gemm_route(pp, dtype);
+    if (route < 0) return route;
+    const vv_conv_params& p = *pp;
+    const int M = (int)((int64_t)p.F * p.Hout * p.Wout);
 #if defined(VV_DT_ONLY)
-    return dtype == VV_BF16 ? vv_conv_gemm_launch_bf16(&p, M, stream) : launch_mode<F16>(p, M, st);
+    return dtype == VV_BF16 ? vv_conv_gemm_launch_bf16(&p, M, route, stream) : launch_mode<F16>(p, M, route, (hipStream_t)stream);
 #else
-    return dtype == VV_BF16 ? launch_mode<BF16>(p, M, st) : launch_mode<F16>(p, M, st);
+    return dtype == VV_BF16 ? launch_mode<BF16>(p, M, route, (hipStream_t)stream) : launch_mode<F16>(p, M, route, (hipStream_t)stream);
 #endif
 }
 #endif

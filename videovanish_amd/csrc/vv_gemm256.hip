@@ -381,39 +381,45 @@ int launch256p(const vv_conv_params& p, int M, hipStream_t st) {
 }
 
 template <typename T>
-int launch256_t(const vv_conv_params& p, int M, bool lin, int form, hipStream_t st) {
-    if (form == 2) return lin ? launch256p<T, G256_LIN, false>(p, M, st) : launch256p<T, G256_CONV, false>(p, M, st);
-    if (form == 3) return lin ? launch256p<T, G256_LIN, true>(p, M, st) : launch256p<T, G256_CONV, true>(p, M, st);
-    const bool n5 = p.Npad % 320 == 0 && p.epilogue != VV_EPI_GEGLU;     // GEGLU pairs value/gate tiles: needs an even NT
-    if (n5) return lin ? launch256<T, 5, G256_LIN>(p, M, st) : launch256<T, 5, G256_CONV>(p, M, st);
-    return lin ? launch256<T, 4, G256_LIN>(p, M, st) : launch256<T, 4, G256_CONV>(p, M, st);
+int launch256_t(const vv_conv_params& p, int M, int route, hipStream_t st) {
+    switch (route) {
+    case VV_ROUTE_256x320_LIN:  return launch256<T, 5, G256_LIN>(p, M, st);
+    case VV_ROUTE_256x320_CONV: return launch256<T, 5, G256_CONV>(p, M, st);
+    case VV_ROUTE_256x256_LIN:  return launch256<T, 4, G256_LIN>(p, M, st);
+    case VV_ROUTE_256x256_CONV: return launch256<T, 4, G256_CONV>(p, M, st);
+    case VV_ROUTE_256P8_LIN:    return launch256p<T, G256_LIN, false>(p, M, st);
+    case VV_ROUTE_256P8_CONV:   return launch256p<T, G256_CONV, false>(p, M, st);
+    case VV_ROUTE_256P8A_LIN:   return launch256p<T, G256_LIN, true>(p, M, st);
+    case VV_ROUTE_256P8A_CONV:  return launch256p<T, G256_CONV, true>(p, M, st);
+    }
+    VV_FAIL(VV_E_ARG, "vv_conv_gemm: route %d is not a 256-row tile form", route);
 }
 
 }  // namespace
 
-// Eligibility + launch.  Returns VV_OK / an error after launching, or -1000 when the shape is not eligible (caller falls back
-// to the 128-row kernels).  `force`: 0 = only where the heuristic expects a win; 1 = the 2-phase kernel whenever the shape is
-// ELIGIBLE; 2 = the 8-phase kernel whenever eligible (needs Npad % 256 == 0).
 // Build split (build.sh): this source is compiled twice, -DVV_DT_ONLY=0 holds the BF16 instantiations behind vv_gemm256_launch_bf16, -DVV_DT_ONLY=1 the
-// F16 ones plus the entry point below (two translation units of ~50 s instead of one of ~100 s: the longest pole of a clean build).  Without the
+// F16 ones plus the entry points below (two translation units of ~50 s instead of one of ~100 s: the longest pole of a clean build).  Without the
 // macro everything lives in one unit.
 #if defined(VV_DT_ONLY) && VV_DT_ONLY == 0
-extern "C" int vv_gemm256_launch_bf16(const vv_conv_params* pp, int M, int lin, int form, void* stream) {
-    return launch256_t<BF16>(*pp, M, lin != 0, form, (hipStream_t)stream);
+extern "C" int vv_gemm256_launch_bf16(const vv_conv_params* pp, int M, int route, void* stream) {
+    return launch256_t<BF16>(*pp, M, route, (hipStream_t)stream);
 }
 #else
 #if defined(VV_DT_ONLY)
-extern "C" int vv_gemm256_launch_bf16(const vv_conv_params* pp, int M, int lin, int form, void* stream);
+extern "C" int vv_gemm256_launch_bf16(const vv_conv_params* pp, int M, int route, void* stream);
 #endif
-extern "C" int vv_gemm256_try(const vv_conv_params* pp, int dtype, int force, void* stream) {
+// Eligibility + form choice (host only: reads the fields of p, dereferences none of its pointers).  Returns the VV_ROUTE_256* code of the kernel, or 0
+// when the shape is not eligible (the caller falls back to the 128-row kernels).  `force`: 0 = only where the heuristic expects a win; 1 = the 2-phase
+// kernel whenever the shape is ELIGIBLE; 2 / 3 = the 8-phase kernel (builtin / inline-asm LDS-DMA) whenever eligible (needs Npad % 256 == 0).
+// vv_conv_gemm launches through vv_gemm256_launch and vv_conv_gemm_route reports through this function: one copy of the rules.
+extern "C" int vv_gemm256_route(const vv_conv_params* pp, int force) {
     const vv_conv_params& p = *pp;
     const int kw = p.ksize_w > 0 ? p.ksize_w : p.ksize;
-    if (p.in_dtype == VV_F32 || p.Kpad != p.K || (p.C0 & 63) || (p.C1 & 63) || p.sc_oh > 0) return -1000;      // (the scattered store lives in the 128-row kernels)
-    if (p.Hv != p.Hin || p.Wv != p.Win || p.ksize * kw > 9) return -1000;
-    if (!(p.Npad % 320 == 0 && p.epilogue != VV_EPI_GEGLU) && p.Npad % 256 != 0) return -1000;
-    if (force >= 2 && p.Npad % 256 != 0) return -1000;
+    if (p.in_dtype == VV_F32 || p.Kpad != p.K || (p.C0 & 63) || (p.C1 & 63) || p.sc_oh > 0) return 0;      // (the scattered store lives in the 128-row kernels)
+    if (p.Hv != p.Hin || p.Wv != p.Win || p.ksize * kw > 9) return 0;
+    if (!(p.Npad % 320 == 0 && p.epilogue != VV_EPI_GEGLU) && p.Npad % 256 != 0) return 0;
+    if (force >= 2 && p.Npad % 256 != 0) return 0;
     const int64_t M64 = (int64_t)p.F * p.Hout * p.Wout;
-    const int M = (int)M64;
     const bool lin = p.ksize == 1 && kw == 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.C1 == 0 && p.Hout == p.Hin && p.Wout == p.Win;
     int form = force >= 2 ? force : 1;
     if (!force) {
@@ -442,13 +448,22 @@ extern "C" int vv_gemm256_try(const vv_conv_params* pp, int dtype, int force, vo
             else if (p.K >= 640) { win = true; form = 1; }
         } else if (p.ksize == 3 && p.stride == 1 && p.K >= 5760 && M64 <= 65536 && BN == 320) { win = true; form = 1; }      // (the 256x256 form lost on every VAE shape)
         const int64_t tiles = ((M64 + 255) / 256) * (p.Npad / (form == 3 ? 256 : BN));
-        if (!win || tiles < 400) return -1000;
+        if (!win || tiles < 400) return 0;
     }
-    hipStream_t st = (hipStream_t)stream;
+    if (form == 2) return lin ? VV_ROUTE_256P8_LIN : VV_ROUTE_256P8_CONV;
+    if (form == 3) return lin ? VV_ROUTE_256P8A_LIN : VV_ROUTE_256P8A_CONV;
+    const bool n5 = p.Npad % 320 == 0 && p.epilogue != VV_EPI_GEGLU;     // GEGLU pairs value/gate tiles: needs an even NT
+    if (n5) return lin ? VV_ROUTE_256x320_LIN : VV_ROUTE_256x320_CONV;
+    return lin ? VV_ROUTE_256x256_LIN : VV_ROUTE_256x256_CONV;
+}
+
+// Launch of a route vv_gemm256_route returned.
+extern "C" int vv_gemm256_launch(const vv_conv_params* pp, int dtype, int route, void* stream) {
+    const int M = (int)((int64_t)pp->F * pp->Hout * pp->Wout);
 #if defined(VV_DT_ONLY)
-    return dtype == VV_BF16 ? vv_gemm256_launch_bf16(&p, M, lin ? 1 : 0, form, stream) : launch256_t<F16>(p, M, lin, form, st);
+    return dtype == VV_BF16 ? vv_gemm256_launch_bf16(pp, M, route, stream) : launch256_t<F16>(*pp, M, route, (hipStream_t)stream);
 #else
-    return dtype == VV_BF16 ? launch256_t<BF16>(p, M, lin, form, st) : launch256_t<F16>(p, M, lin, form, st);
+    return dtype == VV_BF16 ? launch256_t<BF16>(*pp, M, route, (hipStream_t)stream) : launch256_t<F16>(*pp, M, route, (hipStream_t)stream);
 #endif
 }
 #endif

@@ -103,7 +103,7 @@ class AttnParams(C.Structure):
                 ("scale", C.c_float), ("q_hs", C.c_int64), ("k_hs", C.c_int64), ("v_hs", C.c_int64), ("q_prescaled", C.c_int32), ("lse", C.c_void_p), ("o_hs", C.c_int64)]
 
 
-EXPORTS = ["vv_abi_version", "vv_last_error", "vv_device_count", "vv_device_name", "vv_conv_gemm", "vv_groupnorm_nsplit",
+EXPORTS = ["vv_abi_version", "vv_last_error", "vv_device_count", "vv_device_name", "vv_conv_gemm", "vv_conv_gemm_route", "vv_groupnorm_nsplit",
            "vv_groupnorm", "vv_layernorm", "vv_attention", "vv_axpby_f32", "vv_silu_f32", "vv_sched_step", "vv_add_inplace",
            "vv_mask_collapse_dilate", "vv_resize_bilinear_u8", "vv_resize_nearest_u8", "vv_feather_composite", "vv_chamfer_dt", "vv_mask_bbox", "vv_roi_paste_composite",
            "vv_mask_tile_union", "vv_mask_bbox_tiles",
@@ -179,16 +179,68 @@ def _need_cuda(*ts):
                                "(one process per GPU: torch.cuda.set_device(LOCAL_RANK) before building the model)")
 
 
+# vv_conv_gemm_route codes (vvhip.h VV_ROUTE_*): 128-row kernels = loader + tile
+ROUTE_TILE_128x160, ROUTE_TILE_128x128, ROUTE_TILE_128x16, ROUTE_TILE_128x320 = 0, 1, 2, 3
+ROUTE_GENERIC, ROUTE_GENERIC_F32, ROUTE_FAST, ROUTE_FAST32, ROUTE_HALO, ROUTE_LIN, ROUTE_FAST9, ROUTE_HALO_GN = 0x10, 0x20, 0x30, 0x40, 0x50, 0x60, 0x70, 0x80
+ROUTE_256x320_LIN, ROUTE_256x320_CONV, ROUTE_256x256_LIN, ROUTE_256x256_CONV = 0x100, 0x101, 0x102, 0x103
+ROUTE_256P8_LIN, ROUTE_256P8_CONV, ROUTE_256P8A_LIN, ROUTE_256P8A_CONV = 0x104, 0x105, 0x106, 0x107
+ROUTE_HALO256 = 0x200
+_ROUTE_LOADERS = {ROUTE_GENERIC: "generic", ROUTE_GENERIC_F32: "generic-f32", ROUTE_FAST: "fast", ROUTE_FAST32: "fast32", ROUTE_HALO: "halo",
+                  ROUTE_LIN: "lin", ROUTE_FAST9: "fast9", ROUTE_HALO_GN: "halo+gn"}
+_ROUTE_TILES = {ROUTE_TILE_128x160: "128x160", ROUTE_TILE_128x128: "128x128", ROUTE_TILE_128x16: "128x16", ROUTE_TILE_128x320: "128x320"}
+_ROUTE_256 = {ROUTE_256x320_LIN: ("256x320", "lin"), ROUTE_256x320_CONV: ("256x320", "conv"), ROUTE_256x256_LIN: ("256x256", "lin"),
+              ROUTE_256x256_CONV: ("256x256", "conv"), ROUTE_256P8_LIN: ("256x256p8", "lin"), ROUTE_256P8_CONV: ("256x256p8", "conv"),
+              ROUTE_256P8A_LIN: ("256x256p8", "lin"), ROUTE_256P8A_CONV: ("256x256p8", "conv")}
+
+
+def route_tile(code):
+    """Output tile of a route (the profile label): "128x160", "256x320", "256x256p8" (both 8-phase forms), ..."""
+    if code in _ROUTE_256:
+        return _ROUTE_256[code][0]
+    if code == ROUTE_HALO256:
+        return "halo256"
+    if code >= 0x10 and (code & ~15) in _ROUTE_LOADERS and (code & 15) in _ROUTE_TILES:
+        return _ROUTE_TILES[code & 15]
+    raise ValueError(f"not a vv_conv_gemm route: {code}")
+
+
+def route_name(code):
+    """Readable name of a route: "fast9 128x160", "256x320 conv", "256x256p8a lin", ..."""
+    if code in _ROUTE_256:
+        t, m = _ROUTE_256[code]
+        return f"{t}{'a' if code in (ROUTE_256P8A_LIN, ROUTE_256P8A_CONV) else ''} {m}"
+    if code == ROUTE_HALO256:
+        return "halo256"
+    return f"{_ROUTE_LOADERS[code & ~15]} {route_tile(code)}"
+
+
+def _meta(v, dt):
+    """conv_gemm_route operand: a tensor (any device, `meta` included) or a shape, taken as a tensor of dtype dt"""
+    if v is None or isinstance(v, torch.Tensor):
+        return v
+    return torch.empty(tuple(v), dtype=dt, device="meta")
+
+
 # ----------------------------------------------------------------------------------------------------------------
 def conv_gemm(dtype, x0, weight, N, K, *, x1=None, F=1, Hin=1, Win=1, Hv=None, Wv=None, Hout=None, Wout=None, ksize=1,
               stride=1, pad_t=0, pad_l=0, bias=None, rowvec=None, res0=None, res1=None, out=None, out_dtype=None,
               epilogue=EPI_NONE, out_scale=1.0, C0=None, C1=0, ksize_w=0, act=ACT_NONE, out_col=0, split_heads=0, split_dim=0, split_tokens=0, tile_hint=0,
-              act_slope=0.0, scatter=None, gn_partials=False):
+              act_slope=0.0, scatter=None, gn_partials=False, _route=False):
     """Launch vv_conv_gemm.  gn_partials: the layer also leaves per-channel (sum, sum of squares) partials of its output for the GroupNorm that reads it next
     (vv_conv_params.gn_partials; only the 128 x 160 halo-tile 3x3 kernel can): the returned tensor carries them as `out.vv_gn`.  x0/x1: NHWC activations ([F,Hin,Win,C] or any shape with C last); weight: [Npad,Kpad] h16.
     scatter = (OH, OW, sy, sx, oy, ox): row (f, y, x) of this launch goes to row (f*OH + y*sy + oy)*OW + x*sx + ox of `out` (required; residuals
     are read at the same rows) -- the four parity launches of a convolution over a nearest-2x upsampled image (nn.UpConv2x)."""
-    _need_cuda(x0, x1, weight, bias, rowvec, res0, res1, out)      # out_col: write into columns [out_col, out_col+N) of `out`
+    if _route:      # conv_gemm_route: nothing is launched, pointers are passed as null / non-null flags
+        x0, x1, weight, res0, res1 = _meta(x0, h16(dtype)), _meta(x1, h16(dtype)), _meta(weight, h16(dtype)), _meta(res0, torch.float32), _meta(res1, torch.float32)
+        bias, rowvec, out = _meta(bias, torch.float32), _meta(rowvec, torch.float32), _meta(out, h16(dtype) if out_dtype is None else out_dtype)
+
+        def ptr(t, ofs=0):
+            return 0 if t is None else 1
+    else:
+        _need_cuda(x0, x1, weight, bias, rowvec, res0, res1, out)      # out_col: write into columns [out_col, out_col+N) of `out`
+
+        def ptr(t, ofs=0):
+            return 0 if t is None else t.data_ptr() + ofs
     Hv = Hin if Hv is None else Hv
     Wv = Win if Wv is None else Wv
     Hout = Hv if Hout is None else Hout
@@ -206,46 +258,28 @@ def conv_gemm(dtype, x0, weight, N, K, *, x1=None, F=1, Hin=1, Win=1, Hv=None, W
         raise RuntimeError("vv_conv_gemm: a scattered store needs the caller's [F*OH*OW, N] output tensor")
     if out is None:
         od = h16(dtype) if out_dtype is None else out_dtype
-        out = torch.empty((M, nout), dtype=od, device=x0.device)
-    p = ConvParams(in0=x0.data_ptr(), in1=x1.data_ptr() if x1 is not None else 0, in_dtype=dt_of(x0), C0=C0, C1=C1, F=F, Hin=Hin,
+        out = torch.empty((M, nout), dtype=od, device="meta" if _route else x0.device)
+    p = ConvParams(in0=ptr(x0), in1=ptr(x1), in_dtype=dt_of(x0), C0=C0, C1=C1, F=F, Hin=Hin,
                    Win=Win, Hv=Hv, Wv=Wv, Hout=Hout, Wout=Wout, ksize=ksize, stride=stride, pad_t=pad_t, pad_l=pad_l,
-                   weight=weight.data_ptr(), N=N, K=K, Kpad=weight.shape[1], Npad=weight.shape[0],
-                   bias=bias.data_ptr() if bias is not None else 0, rowvec=rowvec.data_ptr() if rowvec is not None else 0,
-                   res0=res0.data_ptr() if res0 is not None else 0, res1=res1.data_ptr() if res1 is not None else 0,
-                   res_dtype=res_dt, out=out.data_ptr() + out_col * out.element_size(), out_dtype=dt_of(out),
+                   weight=ptr(weight), N=N, K=K, Kpad=weight.shape[1], Npad=weight.shape[0],
+                   bias=ptr(bias), rowvec=ptr(rowvec), res0=ptr(res0), res1=ptr(res1),
+                   res_dtype=res_dt, out=ptr(out, out_col * out.element_size()), out_dtype=dt_of(out),
                    ldo=out.shape[-1],
                    epilogue=epilogue, out_scale=out_scale, ksize_w=ksize_w, act=act, split_heads=split_heads, split_dim=split_dim,
                    split_tokens=split_tokens, tile_hint=tile_hint, act_slope=act_slope,
                    sc_oh=sc[0], sc_ow=sc[1], sc_sy=sc[2], sc_sx=sc[3], sc_oy=sc[4], sc_ox=sc[5])
+    if _route:
+        p.gn_partials = 1 if gn_partials else 0
+        return lib().vv_conv_gemm_route(C.byref(p), dtype)
     if gn_partials:
         nblk = lib().vv_conv_gn_partial_blocks(Hout, Wout)
         part = torch.empty((F, nblk, N, 2), dtype=torch.float32, device=x0.device)
         p.gn_partials = part.data_ptr()
         out.vv_gn = GNPartials(part, nblk, F, Hout * Wout, N)
     if PROFILE is not None:
-        Npad = weight.shape[0]
-        # mirror of launch_t() in vv_gemm.hip (label only): LDS-DMA loaders prefer the 128x128 tile (4 blocks per CU) when N allows
-        dma = x0.dtype != torch.float32 and C0 % 64 == 0 and C1 % 64 == 0 and weight.shape[1] == K
-        lin = dma and ksize == 1 and stride == 1 and C1 == 0 and Hv == Hin and Wv == Win and Hout == Hin and Wout == Win
-        tile = "128x128" if epilogue == EPI_GEGLU else (
-            "128x160" if Npad % 160 == 0 else ("128x128" if Npad % 128 == 0 else "128x16"))
-        # mirror of vv_gemm256_try() in vv_gemm256.hip (label only): the long-k / wide-N shapes run on the 256-row kernels
-        if tile_hint != 1 and dma and Hv == Hin and Wv == Win and ksize * (ksize_w or ksize) <= 9 and (
-                (Npad % 320 == 0 and epilogue != EPI_GEGLU) or Npad % 256 == 0):
-            n256 = Npad % 256 == 0
-            form = 0
-            if lin:
-                if K >= 5120 and Npad % 320 == 0 and Npad < 3840 and epilogue != EPI_GEGLU:
-                    form = 1
-                elif n256 and ((epilogue == EPI_GEGLU and K >= 1280) or (K >= 1280 and Npad >= 3840) or K >= 5120):
-                    form = 3
-                elif K >= 640:
-                    form = 1
-            elif ksize == 3 and stride == 1 and K >= 5760 and M <= 65536 and Npad % 320 == 0:
-                form = 1
-            bn = 256 if form == 3 else (320 if (Npad % 320 == 0 and epilogue != EPI_GEGLU) else 256)
-            if form and ((M + 255) // 256) * (Npad // bn) >= 400:
-                tile = f"256x{bn}" + ("p8" if form == 3 else "")
+        # the tile of the kernel that runs, from the dispatcher itself (vv_conv_gemm_route)
+        route = lib().vv_conv_gemm_route(C.byref(p), dtype)
+        tile = route_tile(route) if route > 0 else "refused"
         if PROFILE_SHAPES:
             tile = f"M{M},N{N},K{K}|" + tile
         key = f"conv_gemm[{tile},{'f32in' if x0.dtype == torch.float32 else 'h16in'},k{ksize}{'x%d' % ksize_w if ksize_w and ksize_w != ksize else ''}]"
@@ -257,6 +291,14 @@ def conv_gemm(dtype, x0, weight, N, K, *, x1=None, F=1, Hin=1, Win=1, Hv=None, W
         return out
     _check(lib().vv_conv_gemm(C.byref(p), dtype, _stream()), "vv_conv_gemm")
     return out
+
+
+def conv_gemm_route(dtype, x0, weight, N, K, **kw):
+    """The kernel vv_conv_gemm would launch for conv_gemm(dtype, x0, weight, N, K, **kw) (same arguments), as a ROUTE_* code (route_name / route_tile),
+    or the negative VV_E_* code the launch would be refused with (vv_last_error() holds the message).  Nothing is launched and no GPU is needed: tensors
+    may live on any device (`meta` included), and any tensor argument may be given as its shape instead (activations and weight: h16 of `dtype`;
+    bias, rowvec, residuals: fp32; out: out_dtype)."""
+    return conv_gemm(dtype, x0, weight, N, K, _route=True, **kw)
 
 
 class GNPartials:
