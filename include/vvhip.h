@@ -117,8 +117,8 @@ int vv_conv_gemm(const vv_conv_params* host_p, int dtype, void* stream);
 /* The kernel vv_conv_gemm would launch for these parameters, as a VV_ROUTE_* code (> 0), or the negative VV_E_* code it would refuse the launch
    with (message in vv_last_error()).  Host only: the pointer fields are read as null / non-null flags and never dereferenced, no device is touched.
    The launch path takes its decision from the same host functions, so the answer is the kernel that runs.
-   128-row kernels: route = loader + tile, tile = VV_ROUTE_TILE_* (the 128 x 320 tile: lab build only). */
-enum { VV_ROUTE_TILE_128x160 = 0, VV_ROUTE_TILE_128x128 = 1, VV_ROUTE_TILE_128x16 = 2, VV_ROUTE_TILE_128x320 = 3 };
+   128-row kernels: route = loader + tile, tile = VV_ROUTE_TILE_*. */
+enum { VV_ROUTE_TILE_128x160 = 0, VV_ROUTE_TILE_128x128 = 1, VV_ROUTE_TILE_128x16 = 2 };
 enum {
     VV_ROUTE_GENERIC     = 0x10,   /* register-staged h16 im2col: channel counts not % 64, Kpad != K */
     VV_ROUTE_GENERIC_F32 = 0x20,   /* register-staged fp32 source (channel counts not % 64, Kpad != K) */
@@ -132,8 +132,7 @@ enum {
     VV_ROUTE_256x320_LIN = 0x100, VV_ROUTE_256x320_CONV = 0x101,   /* 2-phase, 256 x 320 tile */
     VV_ROUTE_256x256_LIN = 0x102, VV_ROUTE_256x256_CONV = 0x103,   /* 2-phase, 256 x 256 tile (Npad % 320 != 0, or GEGLU) */
     VV_ROUTE_256P8_LIN   = 0x104, VV_ROUTE_256P8_CONV   = 0x105,   /* 8-phase, 256 x 256, builtin LDS-DMA (tile_hint 3) */
-    VV_ROUTE_256P8A_LIN  = 0x106, VV_ROUTE_256P8A_CONV  = 0x107,   /* 8-phase, 256 x 256, inline-asm LDS-DMA (automatic choice, tile_hint 4) */
-    VV_ROUTE_HALO256     = 0x200   /* lab build only: the opt-in 256-pixel halo kernel (vv_conv3.hip) */
+    VV_ROUTE_256P8A_LIN  = 0x106, VV_ROUTE_256P8A_CONV  = 0x107    /* 8-phase, 256 x 256, inline-asm LDS-DMA (automatic choice, tile_hint 4) */
 };
 int vv_conv_gemm_route(const vv_conv_params* host_p, int dtype);
 int vv_conv_gn_partial_blocks(int Hout, int Wout);
@@ -200,8 +199,8 @@ int vv_motion_module_c320(const vv_motion_params* host_p, int dtype, void* strea
  * replaces 9 launches of vv_conv_gemm / vv_layernorm / vv_attention and their intermediates in HBM.  o: h16 [M][320] (the self-attention core's
  * output), t_in: fp32 [M][320] (proj_in output = the block's residual stream), x: fp32 [M][320] (the Transformer2D input), res1: optional fp32.
  * stream / params: packing.pack_chain_stream (462 slabs of [64][64] h16 incl. the per-head text K and V^T; 5120 floats).
- * ABI 10 -- `layout` names the ORDER of the slabs inside the stream; it must be the one the library's kernel consumes (VV_CHAIN_LAYOUT_ROWSPLIT for
- * the product build), else VV_E_ARG: the three orders have the same slab and parameter counts, so a size check cannot tell them apart (a stream packed
+ * ABI 10 -- `layout` names the ORDER of the slabs inside the stream; it must be the one the library's kernel consumes (VV_CHAIN_LAYOUT_ROWSPLIT),
+ * else VV_E_ARG: the row-split and the retired token order have the same slab and parameter counts, so a size check cannot tell them apart (a stream packed
  * the pre-round-5 way would compute wrong activations silently).  Order of VV_CHAIN_LAYOUT_ROWSPLIT, every slab [64 rows][64 k] h16, k pre-permuted
  * (packing._permute_k) and pre-swizzled for the LDS ring:
  *   25 slabs  Wo1 (5 row blocks x 5 k tiles)
@@ -212,9 +211,9 @@ int vv_motion_module_c320(const vv_motion_params* host_p, int dtype, void* strea
  *   25 slabs  Wout (proj_out)
  * params (fp32): bo1 | ln2.g | ln2.b | bo2 | ln3.g | ln3.b | b1 in the W1 row order above (2560) | b2 | bout.
  * ------------------------------------------------------------------------------------------------------------ */
-#define VV_CHAIN_LAYOUT_TOKENS   0   /* lab kernels only (-DVV_CHAIN_FORM=0): per head q K V^T Wo, GEGLU row tiles (0, 1, 2, 3) -- the order of ABI <= 9 before round 5 */
-#define VV_CHAIN_LAYOUT_ROWSPLIT 1   /* the product kernel */
-#define VV_CHAIN_LAYOUT_COLUMNS  2   /* lab kernel only (-DVV_CHAIN_FORM=2): per-wave fragment streams, 3480 slabs */
+#define VV_CHAIN_LAYOUT_TOKENS   0   /* retired, refused: per head q K V^T Wo, GEGLU row tiles (0, 1, 2, 3) -- the order of ABI <= 9 before round 5, and what such a caller's zeroed field says */
+#define VV_CHAIN_LAYOUT_ROWSPLIT 1   /* the order the kernel consumes */
+#define VV_CHAIN_LAYOUT_COLUMNS  2   /* retired, refused: per-wave fragment streams, 3480 slabs */
 typedef struct {
     const void* o; const float* t_in; const float* x; const float* res1;
     void* out; int32_t out_dtype;

@@ -117,16 +117,41 @@ def test_chain_stream_layout_is_part_of_the_abi(lib):
 
 
 def test_product_sources_carry_no_timing_probes():
-    """VERDICT r5 hygiene 10: switches that make a kernel compute wrong results (timing probes) live in lab headers / tools/lab/*.patch, never in a
-    translation unit of the product library."""
+    """VERDICT r5 hygiene 10: switches that make a kernel compute wrong results (timing probes) live in tools/lab/*.patch, never in csrc/.  Since the lab
+    build was retired the same holds for every A/B switch it carried: one form per kernel, no environment variable read, in EVERY file of the directory."""
     csrc = os.path.join(ROOT, "videovanish_amd", "csrc")
-    product = [f for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".c")) and "_lab" not in f and f != "vv_conv3.hip"]
-    assert "vv_chain.hip" in product and "vv_motion.hip" in product
-    for f in product:
+    sources = [f for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".c"))]
+    assert "vv_chain.hip" in sources and "vv_motion.hip" in sources
+    assert not [f for f in sources if f.endswith(("lab.hip", "lab.h"))]      # no lab-only translation unit or header comes back
+    retired = ("VV_AB", "VV_AB_ENV", "VV_AB_INT", "getenv", "VV_ATTN_VARIANT", "VV_CHAIN_FORM", "VV_CHAIN_TT", "VV_CHAIN_LAG", "VV_CHAIN_AHEAD", "VV_CHAIN_PIN",
+               "VV_FRONT_FORM", "VV_FRONT_BURST", "VV_MOTION_FORM", "VV_GELU_SCALAR", "VV_GELU_ERFF", "VV_GELU2", "VV_GELU2_POLY", "VV_NO_STAGE_F32",
+               "VV_ROUTE_HALO256", "VV_ROUTE_TILE_128x320")
+    for f in sources:
         txt = open(os.path.join(csrc, f)).read()
         for tok in ("VV_PROBE_", "VV_CHAIN_PROBE_", "VV_MOTION_NO_PIN"):
             assert tok not in txt, (f, tok)
+        for tok in retired:      # whole words: VV_ABI_VERSION is not VV_AB
+            assert not re.search(rf"\b{tok}\b", txt), (f, tok)
+    hdr = open(os.path.join(ROOT, "include", "vvhip.h")).read()
+    assert "VV_ROUTE_HALO256" not in hdr and "VV_ROUTE_TILE_128x320" not in hdr and "lab build" not in hdr
     assert os.path.isfile(os.path.join(ROOT, "tools", "lab", "r5_chain_probes.patch"))
+
+
+def test_one_build_recipe():
+    """The library's sources and per-file flags are listed once, in csrc/build.sh: the variant recipe of the A/B tools (tools/build_variant.sh) is a call of
+    it and names no source or compiler of its own, so a variant cannot miss a translation unit (it once lacked vv_roi).  Text only: nothing is compiled."""
+    csrc = os.path.join(ROOT, "videovanish_amd", "csrc")
+    code = lambda p: "\n".join(l.split("#", 1)[0] for l in open(p).read().splitlines()[1:])      # without comments
+    recipe, variant = code(os.path.join(csrc, "build.sh")), code(os.path.join(ROOT, "tools", "build_variant.sh"))
+    listed = set(re.findall(r"\bvv_[a-z0-9]+\b", recipe)) - {"vv_ffv1"}
+    units = {f[:-4] for f in os.listdir(csrc) if f.endswith(".hip")}
+    assert listed == units, (sorted(listed - units), sorted(units - listed))      # every translation unit in the directory is in the one list, and nothing else
+    assert "build.sh" in variant and "--out" in variant
+    assert not re.search(r"\bvv_[a-z0-9]+\b", variant) and "hipcc" not in variant and ".hip" not in variant
+    assert "--out" in recipe and "--src" in recipe
+    for f in os.listdir(os.path.join(ROOT, "tools")):      # and no other tool compiles the library's sources itself
+        if f.endswith(".sh") and f != "build_variant.sh":
+            assert not re.search(r"hipcc[^\n]*csrc", open(os.path.join(ROOT, "tools", f)).read()), f
 
 
 def test_struct_layouts_match_header(tmp_path):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """SAM 2 memory attention core at the published size: one head of d = 256, 4096 queries, self (4096 keys) and cross (7 x 4096 + 64 keys).
-   python tools/bench_attn_d256.py      (VV_LIB_PATH: another build of the library; VV_ATTN_VARIANT: lab variants 71-78)"""
+   python tools/bench_attn_d256.py      (VV_LIB_PATH: another build of the library)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -28,4 +28,4 @@ for Nk in (4096, 7 * 4096 + 64):
     t = e0.elapsed_time(e1) / 5 * 1e-3
     ref = torch.nn.functional.scaled_dot_product_attention(q[None, None, :256].float(), k[None, None].float(), v[None, None].float())[0, 0]
     err = float((o[:256].float() - ref).abs().max() / ref.abs().max())
-    print(f"variant {os.environ.get('VV_ATTN_VARIANT', '-')}: d256 Nq {Nq} Nkv {Nk}: {t * 1e3:.3f} ms = {4.0 * Nq * Nk * D / t / 1e12:.1f} TFLOP/s (rel err {err:.1e})", flush=True)
+    print(f"d256 Nq {Nq} Nkv {Nk}: {t * 1e3:.3f} ms = {4.0 * Nq * Nk * D / t / 1e12:.1f} TFLOP/s (rel err {err:.1e})", flush=True)

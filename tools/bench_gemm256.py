@@ -10,7 +10,7 @@ import torch
 
 from videovanish_amd import hip, packing
 if os.environ.get("VV_LIB_PATH"):
-    hip._LIB_PATH = os.environ["VV_LIB_PATH"]          # lab: another build of the library (e.g. the VV_AB build with its VV_GEMM_* switches)
+    hip._LIB_PATH = os.environ["VV_LIB_PATH"]          # another build of the library (tools/build_variant.sh), for an A/B of two builds on one device
 
 dev = torch.device("cuda:0")
 dname = sys.argv[1] if len(sys.argv) > 1 else "bf16"

@@ -6,7 +6,6 @@
 // exchanges, and the accumulator registers of S^T are -- after exp2 and packing -- directly the B operand of
 // O^T = V^T P^T.  V^T operands come from the row-major V tile through ds_read_b64_tr_b16 (hardware transpose).
 // Head dims that are not MFMA multiples are zero-padded in LDS only (K-dim to 32, V-dim to 16).
-#include <stdlib.h>
 #include <type_traits>
 #include "vv_attn_common.h"
 #ifndef VV_ATTN_PART
@@ -437,9 +436,6 @@ extern "C" int vv_attention_merge(const void* o_parts, const float* lse, int S, 
 
 extern "C" int vv_attention_large_d(const vv_attn_params* pp, int dtype, void* stream);
 extern "C" int vv_attention_mfma32(const vv_attn_params* pp, int dtype, void* stream);
-#ifdef VV_AB      // lab build: VV_ATTN_VARIANT selects an experimental variant / timing probe of vv_attn_lab.hip
-extern "C" int vv_attention_lab(const vv_attn_params* pp, int dtype, void* stream);
-#endif
 
 extern "C" int vv_attention(const vv_attn_params* pp, int dtype, void* stream) {
     if (!pp) VV_FAIL(VV_E_ARG, "vv_attention: null params");
@@ -451,9 +447,6 @@ extern "C" int vv_attention(const vv_attn_params* pp, int dtype, void* stream) {
     if (p.o_hs & 3) VV_FAIL(VV_E_ARG, "vv_attention: o_hs must be a multiple of 4 elements");
     if (dtype != VV_BF16 && dtype != VV_F16) VV_FAIL(VV_E_ARG, "vv_attention: bad dtype");
     if (p.lse && p.D == 40) VV_FAIL(VV_E_UNSUPPORTED, "vv_attention: lse output is not available at D = 40");
-#ifdef VV_AB
-    if (getenv("VV_ATTN_VARIANT")) return vv_attention_lab(pp, dtype, stream);
-#endif
     if (p.D == 40 || p.D == 80) {      // vv_attn32.hip: the 32x32x16 kernels with an optimistic softmax reference take the spatial self-attention shapes
         const int r = vv_attention_mfma32(pp, dtype, stream);
         if (r != -1000) return r;

@@ -6,8 +6,8 @@
 //   out = x + [res1 +] Wout t + bout                      (proj_out + the block's residual)
 // The unfused path (nn.SpatialTransformer) runs these as 9 launches around 8 fp32 / h16 [M, 320 .. 2560] intermediates in HBM: at K = 320 every one of
 // those GEMMs is bandwidth bound (AI 53-64 FLOP/B with the fp32 trunk read and written around each layer).
-// One wave owns 32 consecutive tokens end to end (fp32 trunk in 160 registers, h16 activations in 80 as MFMA B fragments); a block = 4 waves = 128
-// tokens shares the weight stream: 462 pre-swizzled [64 x 64] h16 slabs (packing.pack_chain_stream) through the 10-slot LDS ring by LDS-DMA.
+// A block = 128 tokens shares the weight stream: 462 pre-swizzled [64 x 64] h16 slabs (packing.pack_chain_stream) through the 10-slot LDS ring by LDS-DMA;
+// a pair of waves owns 32 consecutive tokens end to end (chain_rs_c320_kernel below).
 // Fragment conventions, PERM32 and the ring protocol: vv_motion.hip.
 #include <type_traits>
 #include "vv_common.h"
@@ -44,24 +44,13 @@ __device__ __forceinline__ vv_f32x2 gelu2(vv_f32x2 x) {
     const vv_f32x2 erfc = q * e;
     return __builtin_elementwise_fma(ax * 0.5f, (vv_f32x2){1.0f, 1.0f} - erfc, x * 0.5f);
 }
-// which GELU the fused kernel evaluates: the A&S form above.  gelu_poly2 (vv_common.h: packed fp32 polynomial, no v_rcp / v_exp -- the GEMM kernels' GEGLU epilogue since
-// round 6, +4.5..6.6 % there) was measured here too (-DVV_GELU2_POLY, lab): the motion module LOSES 3 % (3.04 -> 3.13 ms), the chain tail is unchanged -- these kernels
+// The fused kernels evaluate this A&S form.  gelu_poly2 (vv_common.h: packed fp32 polynomial, no v_rcp / v_exp -- the GEMM kernels' GEGLU epilogue since
+// round 6, +4.5..6.6 % there) was measured here too: the motion module LOSES 3 % (3.04 -> 3.13 ms), the chain tail is unchanged -- these kernels
 // run one or two waves per SIMD beside the matrix pipe, the transcendental unit is otherwise idle and the polynomial's 14 extra packed FMAs are not (profiles/r6_gelu_ab.txt)
-#ifdef VV_GELU2_POLY
-#define VV_GELU2 gelu_poly2
-#else
-#define VV_GELU2 gelu2
-#endif
-
-#ifndef VV_CHAIN_FORM
-#define VV_CHAIN_FORM 1    // 1 = row-split pairs (chain_rs_c320_kernel, packing layout "rowsplit": the product form); lab builds: 2 = column-split (layout "columns"), 0 = token-split forms (layout "tokens")
-#endif
-#if VV_CHAIN_FORM != 1
-#include "vv_chain_lab.h"      // the lab forms (token-split, column-split): not part of the product library
-#endif
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// ROW-SPLIT form of the same tail (round 5).  What the counters said about the forms above (profiles/r5_chain_forms.txt): the kernel is not at the
+// ROW-SPLIT form of the tail (round 5), the only one built.  What the counters said about the token-split forms it replaced (4 waves x 32 tokens,
+// 8 waves x 16 tokens; a column-split form was measured too -- profiles/r5_chain_forms.txt, sources in history): the kernel is not at the
 // board's power limit (2.39 GHz), its LDS pipe is 16 % busy in the 4-wave form -- the matrix pipe idles because ONE wave per SIMD cannot overlap its
 // own VALU phases (GELU, LayerNorm, softmax, the AGPR copies of a 512-register kernel) and waits (barrier, LDS round trips) with MFMAs; and the
 // 8 x 16-token form needs one ds_read_b128 per 16-cycle MFMA per wave = exactly the LDS pipe's 256 B/clk when the matrix pipe is full.
@@ -172,9 +161,6 @@ __global__ __launch_bounds__(512, 2) void chain_rs_c320_kernel(const vv_chain_pa
             fma_rs(f[i & 1], acc_of(i), x0_of(i), x1_of(i));
             if (i + 1 < N) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
             __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-#ifdef VV_CHAIN_PIN
-            __builtin_amdgcn_sched_barrier(0);
-#endif
         }
     };
     using N5 = std::integral_constant<int, 5>; using N10 = std::integral_constant<int, 10>; using N25 = std::integral_constant<int, 25>;
@@ -432,8 +418,8 @@ __global__ __launch_bounds__(512, 2) void chain_rs_c320_kernel(const vv_chain_pa
             for (int i = 0; i < 2; ++i) {
                 const float* bp = prm + Q_B1 + c * 128 + i * 64 + hf * 32 + 4 * lg;
                 const float4 bv = *(const float4*)bp, bg = *(const float4*)(bp + 16);
-                const vv_f32x2 g01 = VV_GELU2((vv_f32x2){g[2 * i + 1][tt][0] + bg.x, g[2 * i + 1][tt][1] + bg.y});
-                const vv_f32x2 g23 = VV_GELU2((vv_f32x2){g[2 * i + 1][tt][2] + bg.z, g[2 * i + 1][tt][3] + bg.w});
+                const vv_f32x2 g01 = gelu2((vv_f32x2){g[2 * i + 1][tt][0] + bg.x, g[2 * i + 1][tt][1] + bg.y});
+                const vv_f32x2 g23 = gelu2((vv_f32x2){g[2 * i + 1][tt][2] + bg.z, g[2 * i + 1][tt][3] + bg.w});
                 hv[i][0] = (g[2 * i][tt][0] + bv.x) * g01.x; hv[i][1] = (g[2 * i][tt][1] + bv.y) * g01.y;
                 hv[i][2] = (g[2 * i][tt][2] + bv.z) * g23.x; hv[i][3] = (g[2 * i][tt][3] + bv.w) * g23.y;
             }
@@ -910,36 +896,7 @@ __global__ __launch_bounds__(512, 2) void chain_front_rs_c320_kernel(const vv_ch
     }
     // Stores of the QKV phase: block by block (4 stores per wave and 64-channel block).  The kernel writes 1.574 GB per 32-frame launch against 1.475 GB algorithmic (t fp32 0.590 GB +
     // qkv 0.885 GB): 1.07x -- round 5's "1.78x" divided by the QKV bytes alone.  Round 6 built a one-burst form anyway (one `which` = q, k or v = 5 blocks held packed in 40 registers
-    // and stored together; lab form, -DVV_FRONT_BURST) and measured it 3 % SLOWER with no fewer bytes written (profiles/r6_front_store_ab.txt): the product keeps this form.
-#ifdef VV_FRONT_BURST
-    auto qkv_which = [&](const int which, auto tail) {
-        uint2 hold[5][2][2];
-#pragma unroll
-        for (int b5 = 0; b5 < 5; ++b5) {
-            f32x4 acc[2][2] = {{z4, z4}, {z4, z4}};
-            if (b5 < 2) group_rs(N5{}, [&](int) { return &acc[0][0]; }, BODY{});      // (the stream's last 3 blocks are the only ones that can run out of slabs)
-            else group_rs(N5{}, [&](int) { return &acc[0][0]; }, tail);
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt) hold[b5][rt][tt] = make_uint2(pack2<T>(acc[rt][tt][0], acc[rt][tt][1]), pack2<T>(acc[rt][tt][2], acc[rt][tt][3]));
-        }
-        const int64_t wbase = (int64_t)which * CC * p.HW;
-#pragma unroll
-        for (int b5 = 0; b5 < 5; ++b5)
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt) {
-                const int cc = 64 * b5 + 32 * hf + 16 * rt + 4 * lg, head = cc / CD, d = cc - head * CD;
-                const int64_t off = wbase + (int64_t)head * CD * p.HW + d;
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt)
-                    if (row0 + tt * 16 + li < p.M) *(uint2*)(qkv + tokbase[tt] + off) = hold[b5][rt][tt];
-            }
-    };
-#pragma unroll 1
-    for (int which = 0; which < 2; ++which) qkv_which(which, BODY{});
-    qkv_which(2, TAIL{});
-#else
+    // and stored together) and measured it 3 % SLOWER with no fewer bytes written (profiles/r6_front_store_ab.txt): this form stays.
     auto qkv_block = [&](const int rb, auto tail) {
         f32x4 acc[2][2] = {{z4, z4}, {z4, z4}};
         group_rs(N5{}, [&](int) { return &acc[0][0]; }, tail);
@@ -957,7 +914,6 @@ __global__ __launch_bounds__(512, 2) void chain_front_rs_c320_kernel(const vv_ch
 #pragma unroll 1
     for (int rb = 0; rb < 12; ++rb) qkv_block(rb, BODY{});
     qkv_block(12, TAIL{}); qkv_block(13, TAIL{}); qkv_block(14, TAIL{});
-#endif
 }
 
 // per-frame GroupNorm affine: out[f][0][c] = rstd * gamma[c], out[f][1][c] = beta[c] - mean * rstd * gamma[c]
@@ -979,34 +935,14 @@ extern "C" int vv_spatial_chain_c320(const vv_chain_params* pp, int dtype, void*
     if (p.C != CC || p.heads != CH || p.text_len != NKEY) VV_FAIL(VV_E_UNSUPPORTED, "vv_spatial_chain_c320: built for C = 320, 8 heads, 77 text tokens (got %d, %d, %d)", p.C, p.heads, p.text_len);
     if (p.M <= 0) VV_FAIL(VV_E_ARG, "vv_spatial_chain_c320: empty input");
     if (p.out_dtype != VV_F32 && p.out_dtype != dtype) VV_FAIL(VV_E_ARG, "vv_spatial_chain_c320: out_dtype mismatch");
-    const int want_slabs = VV_CHAIN_FORM == 2 ? 4 * 870 : N_SLABS;
-    if (VV_CHAIN_FORM != 1 && p.o_hw) VV_FAIL(VV_E_UNSUPPORTED, "vv_spatial_chain_c320: the lab forms read o row-major only");
     if (p.o_hw < 0 || (p.o_hw > 0 && p.M % p.o_hw)) VV_FAIL(VV_E_ARG, "vv_spatial_chain_c320: o_hw must be 0 (row-major o) or divide M (head-major o)");
-    if (p.layout != VV_CHAIN_FORM) VV_FAIL(VV_E_ARG, "vv_spatial_chain_c320: weight stream packed in layout %d, this library's kernel consumes layout %d (VV_CHAIN_LAYOUT_*)", p.layout, (int)VV_CHAIN_FORM);
-    if (p.n_slabs != want_slabs || p.n_params != Q_TOTAL) VV_FAIL(VV_E_ARG, "vv_spatial_chain_c320: stream / parameter block size mismatch (%d slabs, %d floats)", p.n_slabs, p.n_params);
+    if (p.layout != VV_CHAIN_LAYOUT_ROWSPLIT) VV_FAIL(VV_E_ARG, "vv_spatial_chain_c320: weight stream packed in layout %d, this library's kernel consumes layout %d (VV_CHAIN_LAYOUT_*)", p.layout, VV_CHAIN_LAYOUT_ROWSPLIT);
+    if (p.n_slabs != N_SLABS || p.n_params != Q_TOTAL) VV_FAIL(VV_E_ARG, "vv_spatial_chain_c320: stream / parameter block size mismatch (%d slabs, %d floats)", p.n_slabs, p.n_params);
     const int64_t nblk = (p.M + 127) / 128;
     if (nblk > 0x7fffffff) VV_FAIL(VV_E_ARG, "vv_spatial_chain_c320: grid too large");
     hipStream_t st = (hipStream_t)stream;
-#ifndef VV_CHAIN_TT
-#define VV_CHAIN_TT 1      // token tiles per wave: 1 = 8 waves x 16 tokens, two per SIMD, staggered (round 5); 2 = the round-3 form (lab A/B: -DVV_CHAIN_TT=2)
-#endif
-#ifndef VV_CHAIN_LAG
-#define VV_CHAIN_LAG 0     // slab pairs the second half of the block runs behind the first
-#endif
-#ifndef VV_CHAIN_AHEAD
-#define VV_CHAIN_AHEAD 6
-#endif
-#if VV_CHAIN_FORM == 2
-    if (dtype == VV_BF16) hipLaunchKernelGGL((chain_cs_c320_kernel<BF16>), dim3((unsigned)nblk), dim3(256), 0, st, p);
-    else if (dtype == VV_F16) hipLaunchKernelGGL((chain_cs_c320_kernel<F16>), dim3((unsigned)nblk), dim3(256), 0, st, p);
-#elif VV_CHAIN_FORM == 1
     if (dtype == VV_BF16) hipLaunchKernelGGL((chain_rs_c320_kernel<BF16>), dim3((unsigned)nblk), dim3(512), 0, st, p);
     else if (dtype == VV_F16) hipLaunchKernelGGL((chain_rs_c320_kernel<F16>), dim3((unsigned)nblk), dim3(512), 0, st, p);
-#else
-    constexpr int TT = VV_CHAIN_TT, LAG = TT == 2 ? 0 : VV_CHAIN_LAG, NT = 128 / (16 * TT) * 64, AH = VV_CHAIN_AHEAD;
-    if (dtype == VV_BF16) hipLaunchKernelGGL((chain_c320_kernel<BF16, TT, LAG, AH>), dim3((unsigned)nblk), dim3(NT), 0, st, p);
-    else if (dtype == VV_F16) hipLaunchKernelGGL((chain_c320_kernel<F16, TT, LAG, AH>), dim3((unsigned)nblk), dim3(NT), 0, st, p);
-#endif
     else VV_FAIL(VV_E_ARG, "vv_spatial_chain_c320: bad dtype");
     VV_CHECK_LAUNCH("vv_spatial_chain_c320");
     return VV_OK;
@@ -1029,10 +965,6 @@ extern "C" int vv_spatial_chain_front_c320(const vv_chain_front_params* pp, int 
     const int64_t nblk = (p.M + 127) / 128;
     if (nblk > 0x7fffffff) VV_FAIL(VV_E_ARG, "vv_spatial_chain_front_c320: grid too large");
     hipStream_t st = (hipStream_t)stream;
-#ifndef VV_FRONT_FORM
-#define VV_FRONT_FORM 1      // 1 = row-split pairs (chain_front_rs_c320_kernel); 0 = 4 waves x 32 tokens (round 3; same stream)
-#endif
-#if VV_FRONT_FORM == 1
     if (127 / p.HW + 2 <= 16) {      // the block's per-frame affine rows fit the staging buffer (always, beyond toy frame sizes)
         if (dtype == VV_BF16) hipLaunchKernelGGL(chain_front_rs_c320_kernel<BF16>, dim3((unsigned)nblk), dim3(512), 0, st, p);
         else if (dtype == VV_F16) hipLaunchKernelGGL(chain_front_rs_c320_kernel<F16>, dim3((unsigned)nblk), dim3(512), 0, st, p);
@@ -1042,10 +974,6 @@ extern "C" int vv_spatial_chain_front_c320(const vv_chain_front_params* pp, int 
     }
     if (dtype == VV_BF16) hipLaunchKernelGGL(chain_front_c320_kernel<BF16>, dim3((unsigned)nblk), dim3(256), 0, st, p);
     else if (dtype == VV_F16) hipLaunchKernelGGL(chain_front_c320_kernel<F16>, dim3((unsigned)nblk), dim3(256), 0, st, p);
-#else
-    if (dtype == VV_BF16) hipLaunchKernelGGL(chain_front_c320_kernel<BF16>, dim3((unsigned)nblk), dim3(256), 0, st, p);
-    else if (dtype == VV_F16) hipLaunchKernelGGL(chain_front_c320_kernel<F16>, dim3((unsigned)nblk), dim3(256), 0, st, p);
-#endif
     else VV_FAIL(VV_E_ARG, "vv_spatial_chain_front_c320: bad dtype");
     VV_CHECK_LAUNCH("vv_spatial_chain_front_c320");
     return VV_OK;

@@ -54,10 +54,7 @@ __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)
 // exact (erf) GELU, matching torch.nn.functional.gelu default.  erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, far below the h16 rounding
 // that follows: one v_rcp + one v_exp + 6 FMAs instead of ocml's two-branch erff) -- the form the fused kernels (vv_motion.hip, vv_chain.hip) have
 // used since round 2, the product default everywhere since round 4 (the GEGLU GEMMs gain 5-10 %: profiles/r3_gelu_as_ab.txt; parity re-validated
-// against the 1e-3 asserts: profiles/r4_parity_gpu.txt).  -DVV_GELU_ERFF (lab) brings ocml's erff back.
-#ifdef VV_GELU_ERFF
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
-#else
+// against the 1e-3 asserts: profiles/r4_parity_gpu.txt).
 __device__ __forceinline__ float gelu_f(float x) {
     const float z = fabsf(x) * 0.70710678118654752f;
     const float t = __frcp_rn(fmaf(0.3275911f, z, 1.0f));
@@ -66,7 +63,6 @@ __device__ __forceinline__ float gelu_f(float x) {
     const float erfz = 1.0f - p * t * __expf(-z * z);
     return 0.5f * x * (1.0f + copysignf(erfz, x));
 }
-#endif
 
 // Two exact-erf GELUs at once WITHOUT transcendentals (round 6): gelu(x) = x/2 + |x|/2 * E(|x| / sqrt 2), E(z) = erf(z) on [0, 3.5] as z * Q(w), w = 2 z^2 / 3.5^2 - 1,
 // Q = the degree-12 Chebyshev fit of erf(z) / z in z^2 (monomial coefficients in w, all <= 0.41 in magnitude: well conditioned in fp32), z clamped to 3.5

@@ -5,16 +5,15 @@
 // B (weight, [N][K] K-contiguous) tiles; MFMA operands are read with ds_read_b128.
 //   FAST path (h16 activations, channel counts multiples of 64): both tiles are filled by LDS-DMA
 //     (global_load_lds_dwordx4, per-lane source address = the im2col gather, swizzle applied on the SOURCE address,
-//     out-of-image taps read a zero page), no staging VGPRs, no ds_write.  Three buffering variants were measured A/B in
-//     one process (VV_GEMM_SPLIT, profiles/r1_gemm_ab.txt): 2 = SINGLE buffer (fill -> barrier -> MFMAs -> barrier; 36 KB
-//     of LDS, so 3-4 co-resident blocks per CU hide each other's fills) is the fastest and the default; 0 = one array
-//     double buffered (hipcc drains vmcnt(0) before the ds_reads); 1 = double buffered in DISTINCT __shared__ arrays with
-//     the k loop unrolled by two (the DMA of tile k+1 really flies during the MFMAs of tile k) -- the slowest of the three.
+//     out-of-image taps read a zero page), no staging VGPRs, no ds_write.  Three buffering variants were measured A/B
+//     (profiles/r1_gemm_ab.txt): a SINGLE buffer (fill -> barrier -> MFMAs -> barrier; 36 KB of LDS, so 3-4 co-resident
+//     blocks per CU hide each other's fills) is the fastest and the one built; one array double buffered (hipcc drains
+//     vmcnt(0) before the ds_reads) and a double buffer in DISTINCT __shared__ arrays with the k loop unrolled by two (the
+//     DMA of tile k+1 really flies during the MFMAs of tile k) -- the slowest of the three -- are gone.
 //   generic / fp32-activation paths: register staged (issue-early, convert, write-late).
 // The MFMA is issued with swapped operands (D = W_tile * A_tile^T) so every lane owns 4 CONSECUTIVE output channels
 // of one output row: the epilogue (bias, time-embedding vector, residuals, GEGLU, cast) is 16-byte vectorised.
 // The block index is remapped so that the column tiles of one row panel run on the same XCD (shared L2).
-#include <stdlib.h>
 #include <type_traits>
 #include "vv_common.h"
 #include "vv_gemm_epilogue.h"
@@ -22,21 +21,9 @@
 extern "C" int vv_gemm256_route(const vv_conv_params* pp, int force);
 extern "C" int vv_gemm256_launch(const vv_conv_params* pp, int dtype, int route, void* stream);
 
-// A/B switches of the lab build (-DVV_AB: environment variables read once per process).  The product build takes the measured
-// defaults (profiles/r1_gemm_ab.txt) with no getenv in any launch path.
-#ifdef VV_AB
-#define VV_AB_ENV(name) (getenv(name) != nullptr)
-#define VV_AB_INT(name, dflt) (getenv(name) ? atoi(getenv(name)) : (dflt))
-extern "C" int vv_conv3_halo_eligible(const vv_conv_params* pp);
-extern "C" int vv_conv3_halo_launch(const vv_conv_params* pp, int dtype, void* stream);
-#else
-#define VV_AB_ENV(name) false
-#define VV_AB_INT(name, dflt) (dflt)
-#endif
-
 namespace {
 
-[[maybe_unused]] constexpr int BK = 64;
+constexpr int BK = 64;
 enum { MODE_H16 = 0, MODE_F32 = 1, MODE_FAST = 2, MODE_FAST32 = 3, MODE_HALO = 4, MODE_LIN = 5, MODE_FAST9 = 6 };
 constexpr int HALO_PX = 184;   // (8+2) x (16+2) = 180 halo pixels of an 8x16 output patch, padded to whole 1 KB DMA blocks
 
@@ -48,16 +35,16 @@ __device__ __forceinline__ void glds16(const void* gptr, void* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((gp_t)gptr, (lp_t)lds_wave_base, 16, 0, 0);
 }
 
-template <typename T, int WR, int WC, int MT, int NT, int MODE, int SPLIT, int BKT, int OCCW = 2, bool GN = false>
+template <typename T, int WR, int WC, int MT, int NT, int MODE, int OCCW = 2, bool GN = false>
 __global__ __launch_bounds__(256, OCCW) void conv_gemm_kernel(const vv_conv_params p, const int M, const int tilesM, const int tilesN) {
     constexpr int BM = WR * MT * 16, BN = WC * NT * 16;
-    constexpr int CH = BKT / 8;                 // 16-byte chunks per tile row (8 for a 64-wide k tile, 4 for 32)
-    constexpr int SH = CH == 8 ? 3 : 2;         // log2(CH)
-    constexpr int RP = BKT * 2;                 // LDS row pitch in bytes
-    constexpr int RPB = 256 >> SH;              // tile rows filled by one 256-thread pass (32 or 64)
+    constexpr int CH = BK / 8;                  // 16-byte chunks per tile row
+    constexpr int SH = 3;                       // log2(CH)
+    constexpr int RP = BK * 2;                  // LDS row pitch in bytes
+    constexpr int RPB = 256 >> SH;              // tile rows filled by one 256-thread pass
     constexpr int AR = BM / RPB;                // A chunks staged per thread
     constexpr int BCH = (BN + RPB - 1) / RPB;   // B chunks staged per thread
-    constexpr int KS = BKT / 32;                // MFMA k steps per tile
+    constexpr int KS = BK / 32;                 // MFMA k steps per tile
     // HALO (3x3, stride 1, h16): the M tile is an 8 x 16 pixel patch of one frame; per 64-channel chunk its 10 x 18 halo is
     // DMA'd ONCE and the 9 taps read their A operands out of it (L2->LDS bytes per 9 k tiles: 23 + 9*20 KB instead of 9*36)
     // LIN (plain linear layer / 1x1 stride-1 conv, one h16 source): rows of A are consecutive, no gather state at all -> the kernel
@@ -67,21 +54,17 @@ __global__ __launch_bounds__(256, OCCW) void conv_gemm_kernel(const vv_conv_para
     // kept (two rows per VGPR) instead of coordinates + frame + flags -> the 128x160 kernel fits 128 VGPRs = 4 blocks per CU
     constexpr bool F9 = MODE == MODE_FAST9;
     constexpr bool FAST = MODE == MODE_FAST || A32 || HALO || LIN || F9;
-    static_assert(!HALO || (WR * MT == 8 && SPLIT == 2 && BKT == 64), "HALO: 128-row tile, single buffer");
+    static_assert(!HALO || WR * MT == 8, "HALO: 128-row tile");
     constexpr int HP = HALO ? (HALO_PX * 8 + 255) / 256 : 1;    // halo DMA passes
     // FAST32: the fp32 A tile is DMA'd as fp32 (256-byte rows, 16 chunks) and rounded to h16 when the operand is read
-    constexpr int RPA = A32 ? BKT * 4 : RP;     // A row pitch
+    constexpr int RPA = A32 ? BK * 4 : RP;      // A row pitch
     constexpr int SHA = A32 ? 4 : SH;           // log2(A chunks per row)
     constexpr int RPBA = 256 >> SHA;            // A rows filled per pass
     constexpr int ARA = BM / RPBA;              // A chunks staged per thread
     // XOR swizzle of the chunk index that makes the ds_read_b128 operand reads conflict free (tools/lds_bank_model.py)
-    auto SWZ = [](int row) { return CH == 8 ? (row & 7) : ((row >> 1) & 3); };
-    __shared__ __attribute__((aligned(16))) unsigned char sA0[SPLIT == 0 ? 16 : (HALO ? HALO_PX * 128 : BM * RPA)];
-    __shared__ __attribute__((aligned(16))) unsigned char sA1[SPLIT == 1 ? BM * RP : 16];
-    __shared__ __attribute__((aligned(16))) unsigned char sB0[SPLIT == 0 ? 16 : BN * RP];
-    __shared__ __attribute__((aligned(16))) unsigned char sB1[SPLIT == 1 ? BN * RP : 16];
-    __shared__ __attribute__((aligned(16))) unsigned char sAB[SPLIT == 0 ? 2 * (BM + BN) * RP : 16];
-
+    auto SWZ = [](int row) { return row & 7; };
+    __shared__ __attribute__((aligned(16))) unsigned char sA0[HALO ? HALO_PX * 128 : BM * RPA];
+    __shared__ __attribute__((aligned(16))) unsigned char sB0[BN * RP];
     __shared__ __attribute__((aligned(16))) float sBias[(MODE == MODE_HALO || MODE == MODE_FAST32) ? 4 : BN];      // the block's bias columns: the non-LEAN epilogue reads them from here (vv_gemm_epilogue.h)
 
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -204,16 +187,16 @@ __global__ __launch_bounds__(256, OCCW) void conv_gemm_kernel(const vv_conv_para
         if constexpr (LIN) {
             unsigned char* a = bufA + wave * 1024;
 #pragma unroll
-            for (int i = 0; i < ARA; ++i) glds16(linA[i] + kt * (BKT * 2), a + i * RPBA * RPA);
+            for (int i = 0; i < ARA; ++i) glds16(linA[i] + kt * (BK * 2), a + i * RPBA * RPA);
             unsigned char* b = bufB + wave * 1024;
-            const unsigned short* wrow = wbase + (int64_t)(n0 + (t >> SH)) * p.Kpad + kt * BKT + ((c8 ^ rsw) << 3);
+            const unsigned short* wrow = wbase + (int64_t)(n0 + (t >> SH)) * p.Kpad + kt * BK + ((c8 ^ rsw) << 3);
 #pragma unroll
             for (int i = 0; i < BCH; ++i) {
                 if (BN % RPB == 0 || (t >> SH) + RPB * i < BN) glds16(wrow + (int64_t)(RPB * i) * p.Kpad, b + i * RPB * RP);
             }
             return;
         }
-        const int k0 = kt * BKT;
+        const int k0 = kt * BK;
         const int tap = k0 / Cin;
         int cc = k0 - tap * Cin;
         const int ky = tap / KW, kx = tap - ky * KW;
@@ -276,7 +259,7 @@ __global__ __launch_bounds__(256, OCCW) void conv_gemm_kernel(const vv_conv_para
     };
     // ---- generic: register staged
     auto load_tile = [&](int kt) {
-        const int k = kt * BKT + c8 * 8;
+        const int k = kt * BK + c8 * 8;
         const bool kvalid = k < p.K;
         const int tap = kvalid ? k / Cin : 0;
         int cc = k - tap * Cin;
@@ -303,7 +286,7 @@ __global__ __launch_bounds__(256, OCCW) void conv_gemm_kernel(const vv_conv_para
 #pragma unroll
         for (int i = 0; i < BCH; ++i) {
             const int row = (t >> SH) + RPB * i;
-            if (BN % RPB == 0 || row < BN) rb[i] = *(const uint4*)(wbase + (int64_t)(n0 + row) * p.Kpad + kt * BKT + c8 * 8);
+            if (BN % RPB == 0 || row < BN) rb[i] = *(const uint4*)(wbase + (int64_t)(n0 + row) * p.Kpad + kt * BK + c8 * 8);
         }
     };
     auto store_tile = [&](unsigned char* a, unsigned char* b) {
@@ -331,9 +314,11 @@ __global__ __launch_bounds__(256, OCCW) void conv_gemm_kernel(const vv_conv_para
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const int nk = p.Kpad / BKT;
+    const int nk = p.Kpad / BK;
     const int lr = lane & 15, lq = lane >> 4;
-    // one k tile: prefetch the next tile into (nA,nB), run the MFMAs on (cA,cB), then barrier
+    // one k tile: prefetch the next tile into (nA,nB), run the MFMAs on (cA,cB), then barrier.  The single-buffer loops below pass kt = nk: no prefetch, the
+    // barrier frees the buffers for the next fill.  (The prefetch arm is dead there, but taking it out moves instructions in three kernels -- generic-f32
+    // 128x160 / 128x128, halo 128x16: profiles/lab_retired_isa.txt -- so it waits for a change that re-measures them.)
     auto k_step = [&](int kt, const unsigned char* cA, const unsigned char* cB, unsigned char* nA, unsigned char* nB, int tapofs = 0) {
         const bool more = kt + 1 < nk;
         if (more) { if (FAST) dma_tile(kt + 1, nA, nB); else load_tile(kt + 1); }
@@ -369,7 +354,7 @@ __global__ __launch_bounds__(256, OCCW) void conv_gemm_kernel(const vv_conv_para
                 for (int j = 0; j < NT; ++j) acc[i][j] = T::mfma(bf[j], af[i], acc[i][j]);
         }
         if (!FAST && more) store_tile(nA, nB);
-        __syncthreads();     // with LDS-DMA in flight hipcc drains vmcnt(0) here: the prefetch overlapped the MFMAs
+        __syncthreads();
     };
 
     if constexpr (HALO) {
@@ -383,30 +368,13 @@ __global__ __launch_bounds__(256, OCCW) void conv_gemm_kernel(const vv_conv_para
                 k_step(nk, sA0, sB0, sA0, sB0, (tap / KW) * 18 + tap % KW);
             }
         }
-    } else if (SPLIT == 2) {
-        // single buffer: fill -> barrier -> MFMAs -> barrier; half the LDS, so twice the co-resident blocks hide the fill
+    } else {
+        // single buffer: fill -> barrier -> MFMAs -> barrier; half the LDS of a double buffer, so twice the co-resident blocks hide the fill
         for (int kt = 0; kt < nk; ++kt) {
             if (FAST) dma_tile(kt, sA0, sB0);
             else { load_tile(kt); store_tile(sA0, sB0); }
             __syncthreads();
             k_step(nk, sA0, sB0, sA0, sB0);      // kt argument = nk: no prefetch inside, ends with a barrier
-        }
-    } else if (SPLIT == 1) {
-        if (FAST) dma_tile(0, sA0, sB0);
-        else { load_tile(0); store_tile(sA0, sB0); }
-        __syncthreads();
-        for (int kt = 0; kt < nk; kt += 2) {
-            k_step(kt, sA0, sB0, sA1, sB1);
-            if (kt + 1 < nk) k_step(kt + 1, sA1, sB1, sA0, sB0);
-        }
-    } else {
-        unsigned char* a2 = sAB; unsigned char* b2 = sAB + 2 * BM * RP;
-        if (FAST) dma_tile(0, a2, b2);
-        else { load_tile(0); store_tile(a2, b2); }
-        __syncthreads();
-        for (int kt = 0; kt < nk; ++kt) {
-            const int cur = kt & 1;
-            k_step(kt, a2 + cur * BM * RP, b2 + cur * BN * RP, a2 + (cur ^ 1) * BM * RP, b2 + (cur ^ 1) * BN * RP);
         }
     }
 
@@ -427,18 +395,12 @@ int launch_cfg(const vv_conv_params& p, int M, hipStream_t st) {
     int tilesM = (M + BM - 1) / BM;
     const int tilesN = p.Npad / BN;
     if constexpr (MODE == MODE_HALO) tilesM = p.F * ((p.Hin + 7) / 8) * ((p.Win + 15) / 16);
-    static const int split = VV_AB_INT("VV_GEMM_SPLIT", 2);
     // 128x128 tiles: 130 VGPRs uncapped; capping at 128 (4 spilled) lets a 4th block share the CU (LDS 4 x 32-40 KB)
-    static const bool occ4 = !VV_AB_ENV("VV_GEMM_NO_OCC4");
     constexpr bool CAN4 = WR * WC == 4 && (MODE == MODE_LIN || MODE == MODE_FAST9 || (NT == 4 && (MODE == MODE_FAST || MODE == MODE_HALO)));
-    if (CAN4 && occ4 && (MODE == MODE_HALO || split == 2)) { if constexpr (CAN4) hipLaunchKernelGGL((conv_gemm_kernel<T, WR, WC, MT, NT, MODE, 2, 64, 4>), dim3(tilesM * tilesN), dim3(256), 0, st, p, M, tilesM, tilesN); }
-    else if constexpr (MODE == MODE_FAST32 || MODE == MODE_HALO) hipLaunchKernelGGL((conv_gemm_kernel<T, WR, WC, MT, NT, MODE, 2, 64>), dim3(tilesM * tilesN), dim3(256), 0, st, p, M, tilesM, tilesN);
-#ifdef VV_AB
-    else if (split == 1) hipLaunchKernelGGL((conv_gemm_kernel<T, WR, WC, MT, NT, MODE, 1, 64>), dim3(tilesM * tilesN), dim3(256), 0, st, p, M, tilesM, tilesN);
-    else if (split == 3 && MODE == MODE_FAST) hipLaunchKernelGGL((conv_gemm_kernel<T, WR, WC, MT, NT, MODE, 1, 32>), dim3(tilesM * tilesN), dim3(256), 0, st, p, M, tilesM, tilesN);
-    else if (split == 0) hipLaunchKernelGGL((conv_gemm_kernel<T, WR, WC, MT, NT, MODE, 0, 64>), dim3(tilesM * tilesN), dim3(256), 0, st, p, M, tilesM, tilesN);
-#endif
-    else hipLaunchKernelGGL((conv_gemm_kernel<T, WR, WC, MT, NT, MODE, 2, 64>), dim3(tilesM * tilesN), dim3(256), 0, st, p, M, tilesM, tilesN);
+    // (the plain `if` also instantiates the 2-blocks form of those tiles, which is never launched: kept so that retiring the A/B switches left the device code
+    //  byte-identical, profiles/lab_retired_isa.txt -- `if constexpr` alone would drop them)
+    if (CAN4) { if constexpr (CAN4) hipLaunchKernelGGL((conv_gemm_kernel<T, WR, WC, MT, NT, MODE, 4>), dim3(tilesM * tilesN), dim3(256), 0, st, p, M, tilesM, tilesN); }
+    else hipLaunchKernelGGL((conv_gemm_kernel<T, WR, WC, MT, NT, MODE>), dim3(tilesM * tilesN), dim3(256), 0, st, p, M, tilesM, tilesN);
     VV_CHECK_LAUNCH("vv_conv_gemm");
     return VV_OK;
 }
@@ -447,21 +409,16 @@ int launch_cfg(const vv_conv_params& p, int M, hipStream_t st) {
 // vv_gemm256_route): vv_conv_gemm launches the route it returns and vv_conv_gemm_route reports it -- one copy of the rules.
 
 // tile of the 128-row kernels for a loader: VV_ROUTE_TILE_*, or a VV_E_* code
-int tile_of(const vv_conv_params& p, int mode, int M) {
+int tile_of(const vv_conv_params& p) {
     // tile choice: GEGLU needs an even number of N tiles per wave; N % 160 == 0 -> 128x160; tiny N -> 128x16
-#ifdef VV_AB      // lab: 128 x 320 tile (wave tile 64 x 160: 14 operand fragments per 40 MFMAs instead of 9 per 20; 2 blocks per CU), profiles/r3_gemm_n320_ab.txt
-    static const bool n320 = VV_AB_ENV("VV_GEMM_N320");
-    if (mode != MODE_H16 && mode != MODE_F32 && n320 && p.Npad % 320 == 0 && M >= 4096) return VV_ROUTE_TILE_128x320;
-#endif
+    // (a 128 x 320 tile -- wave tile 64 x 160: 14 operand fragments per 40 MFMAs instead of 9 per 20, 2 blocks per CU -- did not pay: profiles/r3_gemm_n320_ab.txt)
     if (p.epilogue == VV_EPI_GEGLU) {
         if (p.Npad % 128 != 0) VV_FAIL(VV_E_ARG, "vv_conv_gemm: Npad %d not a multiple of tile N %d", p.Npad, 128);
         return VV_ROUTE_TILE_128x128;
     }
-    // N a multiple of both: the 128x128 tile runs 4 blocks per CU (128 VGPRs) against 3 for 128x160 -> +2..8 % on the LDS-DMA
-    // loaders when there are enough row tiles (profiles/r1_gemm_ab.txt, eighth A/B)
-    // (opt-in: in the pipeline the 3x3 convs lose 2-3 % with it, and the linear layers now run 128x160 at 4 blocks through LIN)
-    static const bool pref128 = VV_AB_ENV("VV_GEMM_PREF128") && !VV_AB_ENV("VV_GEMM_NO_OCC4");
-    if (pref128 && p.Npad % 128 == 0 && (mode == MODE_FAST || mode == MODE_HALO) && M >= 16384) return VV_ROUTE_TILE_128x128;
+    // N a multiple of both 160 and 128: the 128x128 tile runs 4 blocks per CU (128 VGPRs) against 3 for 128x160 -> +2..8 % on the LDS-DMA
+    // loaders in isolation (profiles/r1_gemm_ab.txt, eighth A/B), but in the pipeline the 3x3 convs lose 2-3 % with it, and the linear
+    // layers run 128x160 at 4 blocks through LIN: 128x160 goes first
     if (p.Npad % 160 == 0) return VV_ROUTE_TILE_128x160;   // (a 256x160 4-wave tile measured the same: profiles/r1_gemm_ab.txt)
     if (p.Npad % 128 == 0) return VV_ROUTE_TILE_128x128;
     if (p.Npad % 16 == 0 && p.Npad <= 64) return VV_ROUTE_TILE_128x16;
@@ -472,7 +429,6 @@ constexpr int kLoaderRoute[] = {VV_ROUTE_GENERIC, VV_ROUTE_GENERIC_F32, VV_ROUTE
 
 // route of a launch whose arguments conv_validate accepted: a VV_ROUTE_* code, or the VV_E_* code the launch is refused with
 int conv_route(const vv_conv_params& p) {
-    const int M = (int)((int64_t)p.F * p.Hout * p.Wout);
     const bool fast = (p.C0 % 64 == 0) && (p.C1 % 64 == 0) && p.Kpad == p.K;
     if (p.gn_partials) {      // GroupNorm partials out of the epilogue: only the 128 x 160 halo-tile kernel with the staged fp32 epilogue writes them (vvhip.h)
         const bool ok = fast && p.in_dtype != VV_F32 && p.ksize == 3 && (p.ksize_w == 0 || p.ksize_w == 3) && p.pad_t == 1 && p.pad_l == 1 && p.stride == 1 && p.sc_oh == 0 &&
@@ -485,13 +441,6 @@ int conv_route(const vv_conv_params& p) {
         const int r = vv_gemm256_route(&p, p.tile_hint >= 2 ? p.tile_hint - 1 : 0);
         if (r) return r;
     }
-#ifdef VV_AB
-    if (p.sc_oh == 0 && vv_conv3_halo_eligible(&p)) return VV_ROUTE_HALO256;   // opt-in 256-pixel halo kernel (vv_conv3.hip; measured slower than the 128-row halo tile); it has no output scatter
-#endif
-    static const bool no32 = VV_AB_ENV("VV_GEMM_NO_FAST32");
-    static const bool nohalo = VV_AB_ENV("VV_GEMM_NO_HALO");
-    static const bool nolin = VV_AB_ENV("VV_GEMM_NO_LIN");
-    static const bool no9 = VV_AB_ENV("VV_GEMM_NO_FAST9");
     int mode;
     // 3x3 / pad 1, and (round 5) the 2x2 / pad 0 or 1 parity convolutions of nn.UpConv2x with their scattered store: the 10 x 18 halo of an 8 x 16 patch starts
     // at (y0 - pad_t, x0 - pad_l) and holds every tap of both kernel sizes
@@ -499,15 +448,15 @@ int conv_route(const vv_conv_params& p) {
     const bool halo2 = p.ksize == 2 && (p.ksize_w == 0 || p.ksize_w == 2) && p.pad_t >= 0 && p.pad_t <= 1 && p.pad_l >= 0 && p.pad_l <= 1;
     // patch grid waste <= 15 % (the halo tile is worth 17-25 %)
     const int64_t cover = (int64_t)((p.Hin + 7) / 8) * 8 * ((p.Win + 15) / 16) * 16;
-    if (fast && !nohalo && p.in_dtype != VV_F32 && (halo3 || halo2) && p.stride == 1 &&
+    if (fast && p.in_dtype != VV_F32 && (halo3 || halo2) && p.stride == 1 &&
         p.Hv == p.Hin && p.Wv == p.Win && p.Hout == p.Hin && p.Wout == p.Win && p.epilogue != VV_EPI_GEGLU && (p.Npad % 160 == 0 || p.Npad % 128 == 0 || (p.Npad % 16 == 0 && p.Npad <= 64)) &&      // (the narrow tile: conv_out layers, 4 MFMAs per k tile -- all data movement, the halo saves 3/4 of it)
         cover * 100 <= (int64_t)p.Hin * p.Win * 115) mode = MODE_HALO;
-    else if (fast && !nolin && p.in_dtype != VV_F32 && p.ksize == 1 && p.ksize_w <= 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.C1 == 0 &&
+    else if (fast && p.in_dtype != VV_F32 && p.ksize == 1 && p.ksize_w <= 1 && p.stride == 1 && p.pad_t == 0 && p.pad_l == 0 && p.C1 == 0 &&
              p.Hv == p.Hin && p.Wv == p.Win && p.Hout == p.Hin && p.Wout == p.Win) mode = MODE_LIN;
-    else if (p.in_dtype == VV_F32) mode = (fast && !no32) ? MODE_FAST32 : MODE_F32;
-    else if (fast && !no9 && p.Hv == p.Hin && p.Wv == p.Win && p.ksize * (p.ksize_w > 0 ? p.ksize_w : p.ksize) <= 9) mode = MODE_FAST9;
+    else if (p.in_dtype == VV_F32) mode = fast ? MODE_FAST32 : MODE_F32;
+    else if (fast && p.Hv == p.Hin && p.Wv == p.Win && p.ksize * (p.ksize_w > 0 ? p.ksize_w : p.ksize) <= 9) mode = MODE_FAST9;
     else mode = fast ? MODE_FAST : MODE_H16;
-    const int tile = tile_of(p, mode, M);
+    const int tile = tile_of(p);
     if (tile < 0) return tile;
     return kLoaderRoute[mode] + tile;
 }
@@ -515,9 +464,6 @@ int conv_route(const vv_conv_params& p) {
 template <typename T, int MODE>
 int launch_t(const vv_conv_params& p, int M, int tile, hipStream_t st) {
     switch (tile) {
-#ifdef VV_AB
-    case VV_ROUTE_TILE_128x320: if constexpr (MODE != MODE_H16 && MODE != MODE_F32) return launch_cfg<T, 2, 2, 4, 10, MODE>(p, M, st); break;
-#endif
     case VV_ROUTE_TILE_128x160: return launch_cfg<T, 2, 2, 4, 5, MODE>(p, M, st);
     case VV_ROUTE_TILE_128x128: return launch_cfg<T, 2, 2, 4, 4, MODE>(p, M, st);
     case VV_ROUTE_TILE_128x16: return launch_cfg<T, 4, 1, 2, 1, MODE>(p, M, st);
@@ -530,14 +476,11 @@ int launch_mode(const vv_conv_params& p, int M, int route, hipStream_t st) {
     constexpr int dt = std::is_same<T, BF16>::value ? VV_BF16 : VV_F16;
     if (route == VV_ROUTE_HALO_GN) {
         const int tilesM = p.F * ((p.Hin + 7) / 8) * ((p.Win + 15) / 16), tilesN = p.Npad / 160;
-        hipLaunchKernelGGL((conv_gemm_kernel<T, 2, 2, 4, 5, MODE_HALO, 2, 64, 2, true>), dim3(tilesM * tilesN), dim3(256), 0, st, p, M, tilesM, tilesN);      // its own instantiation: the
+        hipLaunchKernelGGL((conv_gemm_kernel<T, 2, 2, 4, 5, MODE_HALO, 2, true>), dim3(tilesM * tilesN), dim3(256), 0, st, p, M, tilesM, tilesN);      // its own instantiation: the
         VV_CHECK_LAUNCH("vv_conv_gemm");                                                                                                                          // plain kernel keeps its registers
         return VV_OK;
     }
     if (route >= VV_ROUTE_256x320_LIN && route <= VV_ROUTE_256P8A_CONV) return vv_gemm256_launch(&p, dt, route, (void*)st);
-#ifdef VV_AB
-    if (route == VV_ROUTE_HALO256) return vv_conv3_halo_launch(&p, dt, (void*)st);
-#endif
     const int tile = route & 15;
     switch (route & ~15) {
     case VV_ROUTE_GENERIC: return launch_t<T, MODE_H16>(p, M, tile, st);

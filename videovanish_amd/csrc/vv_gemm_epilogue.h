@@ -1,4 +1,4 @@
-// Epilogue shared by the MFMA GEMM / convolution kernels (vv_gemm.hip, vv_gemm256.hip, vv_conv3.hip): accumulators in the swapped-operand layout
+// Epilogue shared by the MFMA GEMM / convolution kernels (vv_gemm.hip, vv_gemm256.hip): accumulators in the swapped-operand layout
 // (lane (lr, lq) owns output row row0 + i*16 + lr, channels ncol0 + j*16 + 4*lq .. +3) -> bias, out_scale, time-embedding row
 // vector, up to two residuals, ReLU, GEGLU, cast, 16-byte stores.  row_m(tile_row, ok&) maps a tile row to the output row.
 //
@@ -59,16 +59,11 @@ __device__ __forceinline__ void gemm_epilogue(const vv_conv_params& p, f32x4 (&a
                     const float bvv[4] = {bv[j / 2].x, bv[j / 2].y, bv[j / 2].z, bv[j / 2].w};
                     const float bgg[4] = {bg[j / 2].x, bg[j / 2].y, bg[j / 2].z, bg[j / 2].w};
                     float o[4];
-#ifdef VV_GELU_SCALAR      // lab: the scalar A&S form (v_rcp + v_exp per element) the epilogue used until round 6
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) o[r] = (acc[i][j][r] + bvv[r]) * gelu_f(acc[i][j + 1][r] + bgg[r]);
-#else
-#pragma unroll
-                    for (int r = 0; r < 4; r += 2) {
+                    for (int r = 0; r < 4; r += 2) {      // (gelu_poly2: two GELUs per packed-fp32 issue; the scalar form with v_rcp + v_exp per element lost 4.5-6.6 % here in round 6)
                         const vv_f32x2 ge = gelu_poly2((vv_f32x2){acc[i][j + 1][r] + bgg[r], acc[i][j + 1][r + 1] + bgg[r + 1]});
                         o[r] = (acc[i][j][r] + bvv[r]) * ge.x; o[r + 1] = (acc[i][j][r + 1] + bvv[r + 1]) * ge.y;
                     }
-#endif
                     const int64_t oc = (int64_t)m * p.ldo + (nt0 >> 1) + 4 * lq;
                     if (p.out_dtype == VV_F32) *(float4*)((float*)p.out + oc) = make_float4(o[0], o[1], o[2], o[3]);
                     else *(uint2*)((unsigned short*)p.out + oc) = make_uint2(pack2<T>(o[0], o[1]), pack2<T>(o[2], o[3]));
@@ -77,12 +72,8 @@ __device__ __forceinline__ void gemm_epilogue(const vv_conv_params& p, f32x4 (&a
         }
         return;
     }
-#ifdef VV_NO_STAGE_F32      // lab: the fp32 strips stay in the accumulator layout (the form before round 5's second session) -- the in-pipeline A/B of the staged form, profiles/r6_stage_f32_pipeline_ab.txt
-    constexpr bool STAGE_F32 = false;
-#else
-    constexpr bool STAGE_F32 = true;
-#endif
-    if (STAGE_F32 && LEAN && STAGED && vec && stage && p.out_dtype == VV_F32 && p.split_heads <= 0 && !p.rowvec && !p.res1 && p.act == VV_ACT_NONE && (!p.res0 || r0f32)) {
+    // (the in-pipeline A/B of this staged form against fp32 strips left in the accumulator layout: profiles/r6_stage_f32_pipeline_ab.txt)
+    if (LEAN && STAGED && vec && stage && p.out_dtype == VV_F32 && p.split_heads <= 0 && !p.rowvec && !p.res1 && p.act == VV_ACT_NONE && (!p.res0 || r0f32)) {
         // STAGED form of the lean path (fp32 trunk out, at most the fp32 residual: the out-projections and FF outputs of levels 1 / 2 -- streaming kernels, 60 % of
         // their time in this epilogue).  In the accumulator layout a wave instruction touches 16 rows x 64 bytes: half a cache line per row and request.  A strip
         // (16 rows x W columns) goes through a wave-private LDS tile instead and comes back row-major: each instruction then covers 256 / W rows x W * 4 contiguous bytes

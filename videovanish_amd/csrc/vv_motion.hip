@@ -41,16 +41,7 @@ __device__ __forceinline__ void glds16_asm(const void* gptr, void* lds_wave_base
 
 // exact (erf) GELU through Abramowitz-Stegun 7.1.26 (|erf error| <= 1.5e-7, far below the h16 rounding that follows): 2 transcendentals
 // + ~12 VALU instead of the ~30 of erff -- with ONE wave per SIMD the activation is not hidden behind another wave's MFMAs
-__device__ __forceinline__ float gelu_fast(float x) {
-    const float z = fabsf(x) * 0.70710678118654752f;
-    const float t = __builtin_amdgcn_rcpf(1.0f + 0.3275911f * z);
-    const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-    const float e = poly * __builtin_amdgcn_exp2f(-z * z * 1.4426950408889634f);      // = 1 - erf(z)
-    const float erf_abs = 1.0f - e;
-    return 0.5f * x * (1.0f + copysignf(erf_abs, x));
-}
-
-// two GELUs at once on packed fp32 math (v_pk_fma_f32)
+// (two GELUs at once on packed fp32 math: v_pk_fma_f32)
 __device__ __forceinline__ vv_f32x2 gelu2(vv_f32x2 x) {
     const vv_f32x2 ax = {fabsf(x.x), fabsf(x.y)};
     const vv_f32x2 z = ax * 0.70710678118654752f;
@@ -66,14 +57,9 @@ __device__ __forceinline__ vv_f32x2 gelu2(vv_f32x2 x) {
     const vv_f32x2 erfc = q * e;                                       // 1 - erf(|x| / sqrt 2)
     return __builtin_elementwise_fma(ax * 0.5f, (vv_f32x2){1.0f, 1.0f} - erfc, x * 0.5f);      // 0.5 x (1 + sign(x) (1 - erfc))
 }
-// which GELU the fused kernel evaluates: the A&S form above.  gelu_poly2 (vv_common.h: packed fp32 polynomial, no v_rcp / v_exp -- the GEMM kernels' GEGLU epilogue since
-// round 6, +4.5..6.6 % there) was measured here too (-DVV_GELU2_POLY, lab): the motion module LOSES 3 % (3.04 -> 3.13 ms), the chain tail is unchanged -- these kernels
+// The fused kernel evaluates this A&S form.  gelu_poly2 (vv_common.h: packed fp32 polynomial, no v_rcp / v_exp -- the GEMM kernels' GEGLU epilogue since
+// round 6, +4.5..6.6 % there) was measured here too: the motion module LOSES 3 % (3.04 -> 3.13 ms), the chain tail is unchanged -- these kernels
 // run one or two waves per SIMD beside the matrix pipe, the transcendental unit is otherwise idle and the polynomial's 14 extra packed FMAs are not (profiles/r6_gelu_ab.txt)
-#ifdef VV_GELU2_POLY
-#define VV_GELU2 gelu_poly2
-#else
-#define VV_GELU2 gelu2
-#endif
 
 template <typename T>
 __global__ __launch_bounds__(256, 1) void motion_c320_kernel(const vv_motion_params p) {
@@ -350,8 +336,8 @@ __global__ __launch_bounds__(256, 1) void motion_c320_kernel(const vv_motion_par
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const float4 bv = *(const float4*)(prm + P_B1 + c * 128 + (2 * i) * 16 + 4 * lg), bg = *(const float4*)(prm + P_B1 + c * 128 + (2 * i + 1) * 16 + 4 * lg);
-                const vv_f32x2 g01 = VV_GELU2((vv_f32x2){g[2 * i + 1][tt][0] + bg.x, g[2 * i + 1][tt][1] + bg.y});
-                const vv_f32x2 g23 = VV_GELU2((vv_f32x2){g[2 * i + 1][tt][2] + bg.z, g[2 * i + 1][tt][3] + bg.w});
+                const vv_f32x2 g01 = gelu2((vv_f32x2){g[2 * i + 1][tt][0] + bg.x, g[2 * i + 1][tt][1] + bg.y});
+                const vv_f32x2 g23 = gelu2((vv_f32x2){g[2 * i + 1][tt][2] + bg.z, g[2 * i + 1][tt][3] + bg.w});
                 hv[i][0] = (g[2 * i][tt][0] + bv.x) * g01.x; hv[i][1] = (g[2 * i][tt][1] + bv.y) * g01.y;
                 hv[i][2] = (g[2 * i][tt][2] + bv.z) * g23.x; hv[i][3] = (g[2 * i][tt][3] + bv.w) * g23.y;
             }
@@ -411,13 +397,6 @@ __global__ __launch_bounds__(256, 1) void motion_c320_kernel(const vv_motion_par
     }
 }
 
-#ifndef VV_MOTION_FORM
-#define VV_MOTION_FORM 0      // 0 = 4 waves x 32 tokens (the product form; stream layout "tokens"); 1 = row-split pairs (lab: vv_motion_lab.h, layout "rowsplit")
-#endif
-#if VV_MOTION_FORM == 1
-#include "vv_motion_lab.h"
-#endif
-
 // per-channel GroupNorm affine of a clip-pooled GroupNorm: a[c] = rstd_g * gamma_c, b[c] = beta_c - mean_g * a[c]   ([2][C] floats)
 __global__ void gn_affine_kernel(const float* fin /* [groups][2] */, const float* gamma, const float* beta, int C, int groups, float* out) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -446,13 +425,8 @@ extern "C" int vv_motion_module_c320(const vv_motion_params* pp, int dtype, void
     if (p.out_dtype != VV_F32 && p.out_dtype != dtype) VV_FAIL(VV_E_ARG, "vv_motion_module_c320: out_dtype mismatch");
     if (p.n_slabs != N_SLABS || p.n_params != P_TOTAL - 640) VV_FAIL(VV_E_ARG, "vv_motion_module_c320: stream / parameter block size mismatch (%d slabs, %d floats)", p.n_slabs, p.n_params);
     hipStream_t st = (hipStream_t)stream;
-#if VV_MOTION_FORM == 1
-    if (dtype == VV_BF16) hipLaunchKernelGGL(motion_rs_c320_kernel<BF16>, dim3(p.HW / 4), dim3(512), 0, st, p);
-    else if (dtype == VV_F16) hipLaunchKernelGGL(motion_rs_c320_kernel<F16>, dim3(p.HW / 4), dim3(512), 0, st, p);
-#else
     if (dtype == VV_BF16) hipLaunchKernelGGL(motion_c320_kernel<BF16>, dim3(p.HW / 4), dim3(256), 0, st, p);
     else if (dtype == VV_F16) hipLaunchKernelGGL(motion_c320_kernel<F16>, dim3(p.HW / 4), dim3(256), 0, st, p);
-#endif
     else VV_FAIL(VV_E_ARG, "vv_motion_module_c320: bad dtype");
     VV_CHECK_LAUNCH("vv_motion_module_c320");
     return VV_OK;

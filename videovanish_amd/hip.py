@@ -40,7 +40,7 @@ class _Prof:
         return False
 
 
-# the in-tree product build; lab tools that A/B another build of the library set hip._LIB_PATH before the first launch (tools/bench_*.py).  No
+# the in-tree build; tools that A/B another build of the library set hip._LIB_PATH before the first launch (tools/bench_*.py).  No
 # environment variable is read anywhere in this module: behaviour is selected by API only.
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libvvhip.so")
 PROFILE_SHAPES = False   # bench.py --profile-shapes: profile keys of the GEMM / attention launches carry their M, N, K (tools/shape_table.py)
@@ -87,7 +87,7 @@ class ChainParams(C.Structure):
                 ("n_slabs", C.c_int32), ("n_params", C.c_int32), ("layout", C.c_int32), ("o_hw", C.c_int32)]
 
 
-CHAIN_LAYOUT_IDS = {"tokens": 0, "rowsplit": 1, "columns": 2}      # VV_CHAIN_LAYOUT_* (vvhip.h)
+CHAIN_LAYOUT_IDS = {"rowsplit": 1}      # VV_CHAIN_LAYOUT_ROWSPLIT (vvhip.h): the one stream order the library accepts (0 and 2 are retired orders it refuses)
 
 
 class ChainFrontParams(C.Structure):
@@ -180,14 +180,13 @@ def _need_cuda(*ts):
 
 
 # vv_conv_gemm_route codes (vvhip.h VV_ROUTE_*): 128-row kernels = loader + tile
-ROUTE_TILE_128x160, ROUTE_TILE_128x128, ROUTE_TILE_128x16, ROUTE_TILE_128x320 = 0, 1, 2, 3
+ROUTE_TILE_128x160, ROUTE_TILE_128x128, ROUTE_TILE_128x16 = 0, 1, 2
 ROUTE_GENERIC, ROUTE_GENERIC_F32, ROUTE_FAST, ROUTE_FAST32, ROUTE_HALO, ROUTE_LIN, ROUTE_FAST9, ROUTE_HALO_GN = 0x10, 0x20, 0x30, 0x40, 0x50, 0x60, 0x70, 0x80
 ROUTE_256x320_LIN, ROUTE_256x320_CONV, ROUTE_256x256_LIN, ROUTE_256x256_CONV = 0x100, 0x101, 0x102, 0x103
 ROUTE_256P8_LIN, ROUTE_256P8_CONV, ROUTE_256P8A_LIN, ROUTE_256P8A_CONV = 0x104, 0x105, 0x106, 0x107
-ROUTE_HALO256 = 0x200
 _ROUTE_LOADERS = {ROUTE_GENERIC: "generic", ROUTE_GENERIC_F32: "generic-f32", ROUTE_FAST: "fast", ROUTE_FAST32: "fast32", ROUTE_HALO: "halo",
                   ROUTE_LIN: "lin", ROUTE_FAST9: "fast9", ROUTE_HALO_GN: "halo+gn"}
-_ROUTE_TILES = {ROUTE_TILE_128x160: "128x160", ROUTE_TILE_128x128: "128x128", ROUTE_TILE_128x16: "128x16", ROUTE_TILE_128x320: "128x320"}
+_ROUTE_TILES = {ROUTE_TILE_128x160: "128x160", ROUTE_TILE_128x128: "128x128", ROUTE_TILE_128x16: "128x16"}
 _ROUTE_256 = {ROUTE_256x320_LIN: ("256x320", "lin"), ROUTE_256x320_CONV: ("256x320", "conv"), ROUTE_256x256_LIN: ("256x256", "lin"),
               ROUTE_256x256_CONV: ("256x256", "conv"), ROUTE_256P8_LIN: ("256x256p8", "lin"), ROUTE_256P8_CONV: ("256x256p8", "conv"),
               ROUTE_256P8A_LIN: ("256x256p8", "lin"), ROUTE_256P8A_CONV: ("256x256p8", "conv")}
@@ -197,8 +196,6 @@ def route_tile(code):
     """Output tile of a route (the profile label): "128x160", "256x320", "256x256p8" (both 8-phase forms), ..."""
     if code in _ROUTE_256:
         return _ROUTE_256[code][0]
-    if code == ROUTE_HALO256:
-        return "halo256"
     if code >= 0x10 and (code & ~15) in _ROUTE_LOADERS and (code & 15) in _ROUTE_TILES:
         return _ROUTE_TILES[code & 15]
     raise ValueError(f"not a vv_conv_gemm route: {code}")
@@ -209,8 +206,6 @@ def route_name(code):
     if code in _ROUTE_256:
         t, m = _ROUTE_256[code]
         return f"{t}{'a' if code in (ROUTE_256P8A_LIN, ROUTE_256P8A_CONV) else ''} {m}"
-    if code == ROUTE_HALO256:
-        return "halo256"
     return f"{_ROUTE_LOADERS[code & ~15]} {route_tile(code)}"
 
 
@@ -667,7 +662,7 @@ def _packing():
     return packing
 
 
-def spatial_chain_c320(dtype, o, t_in, x, stream_w, params, *, res1=None, out_dtype=torch.float32, layout=None, o_hw=0):
+def spatial_chain_c320(dtype, o, t_in, x, stream_w, params, *, res1=None, out_dtype=torch.float32, o_hw=0):
     """The fused tail of a level-0 spatial transformer block (vv_chain.hip): attn1 out-proj + residual, cross-attention to the text tokens,
     GEGLU feed-forward, proj_out + block residual in ONE kernel.  o: h16 [M,320] (o_hw = 0), or head-major [M / o_hw, 8, o_hw, 40] as vv_attention writes it
     with o_hs = o_hw * 40; t_in, x (, res1): fp32 [M,320]."""
@@ -678,7 +673,7 @@ def spatial_chain_c320(dtype, o, t_in, x, stream_w, params, *, res1=None, out_dt
     out = torch.empty((M, Cc), dtype=out_dtype, device=x.device)
     cp = ChainParams(o=o.data_ptr(), t_in=t_in.data_ptr(), x=x.data_ptr(), res1=res1.data_ptr() if res1 is not None else 0, out=out.data_ptr(),
                      out_dtype=dt_of(out), stream=stream_w.data_ptr(), params=params.data_ptr(), M=M, C=Cc, heads=8, text_len=77,
-                     n_slabs=stream_w.shape[0], n_params=params.numel(), layout=CHAIN_LAYOUT_IDS[layout or _packing().CHAIN_LAYOUT], o_hw=int(o_hw))
+                     n_slabs=stream_w.shape[0], n_params=params.numel(), layout=CHAIN_LAYOUT_IDS[_packing().CHAIN_LAYOUT], o_hw=int(o_hw))
     flops = 2.0 * M * Cc * Cc * (1 + 1 + 1 + 12 + 1) + 4.0 * M * 77 * Cc
     with _Prof("spatial_chain_fused[c320]", flops, M * Cc * (2 + 4 + 4 + out.element_size())):
         _check(lib().vv_spatial_chain_c320(C.byref(cp), dtype, _stream()), "vv_spatial_chain_c320")
