@@ -30,10 +30,54 @@ def test_every_declared_symbol_is_exported(lib):
         assert hasattr(lib, n), f"{n} declared in include/vvhip.h but not exported"
 
 
+def _header():
+    """include/vvhip.h without its comments"""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vvhip.h")).read(), flags=re.S)
+
+
+CTYPE_OF = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
+
+
+def _prototypes():
+    """every prototype of include/vvhip.h -> {name: (restype, [argtypes])}: any pointer -> c_void_p, scalars by CTYPE_OF, `const char*` returned -> c_char_p"""
+    protos = {}
+    for ret, name, args in re.findall(r"^\s*(int|const char\*)\s+(vv_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _header(), flags=re.M):
+        args = [" ".join(a.split()) for a in args.split(",")]
+        args = [] if args in (["void"], [""]) else args
+        # a parameter is `type name`; a pointer of any pointee is an address
+        protos[name] = (ctypes.c_int if ret == "int" else ctypes.c_char_p, [ctypes.c_void_p if "*" in a else CTYPE_OF[a.rsplit(" ", 1)[0]] for a in args])
+    return protos
+
+
 def test_binding_lists_match_header(lib):
+    """hip.SIGNATURES declares every function of include/vvhip.h with the header's return and parameter types, and hip.lib() has applied it: an int64_t
+    or float parameter passed without its declaration would be truncated / passed as garbage silently."""
     from videovanish_amd import hip
+    protos = _prototypes()
+    assert sorted(protos) == _declared() and len(protos) == 87
     assert sorted(hip.EXPORTS) == _declared()
+    assert sorted(hip.SIGNATURES) == sorted(protos)
+    loaded = hip.lib()
+    for name, (restype, argtypes) in protos.items():
+        fn = getattr(loaded, name)
+        assert fn.restype is restype, (name, fn.restype, restype)
+        assert fn.argtypes is not None and list(fn.argtypes) == argtypes, (name, fn.argtypes, argtypes)
+    assert sum(ctypes.c_int64 in a for _, a in protos.values()) == 34 and sum(ctypes.c_float in a for _, a in protos.values()) == 16
     assert lib.vv_abi_version() == hip.ABI_VERSION == 10
+
+
+def test_wrong_kind_of_argument_is_refused_at_the_call():
+    """with the declared signatures a float where the header says int, or a Python object where it says pointer, raises ctypes.ArgumentError instead of
+    passing garbage.  vv_layernorm validates before it touches a device and every pointer is null: nothing could be launched even if a call went through."""
+    from videovanish_amd import hip
+    fn = hip.lib().vv_layernorm
+    assert fn(None, 1, 4, None, None, None, 1, None, 0, None) == -1      # the same call with well-typed arguments reaches the library (and is refused there)
+    with pytest.raises(ctypes.ArgumentError):
+        fn(None, 1.0, 4, None, None, None, 1, None, 0, None)             # float for `int M`
+    with pytest.raises(ctypes.ArgumentError):
+        fn(object(), 1, 4, None, None, None, 1, None, 0, None)           # an object (e.g. a tensor instead of its address) for `const float* x`
+    with pytest.raises(ctypes.ArgumentError):
+        hip.lib().vv_conv_gemm(ctypes.byref(hip.ConvParams()), 0.0, None)      # float for `int dtype` (all-null parameters: refused by the library otherwise)
 
 
 def test_integration_md_binding_snippet_version_check(lib):
@@ -154,15 +198,29 @@ def test_one_build_recipe():
             assert not re.search(r"hipcc[^\n]*csrc", open(os.path.join(ROOT, "tools", f)).read()), f
 
 
+def _struct_members(name):
+    """member names of `typedef struct { ... } name;` in include/vvhip.h, in order"""
+    body = re.search(r"typedef struct \{([^}]*)\}\s*" + name + r"\s*;", _header()).group(1)
+    names = []
+    for decl in body.split(";"):
+        if decl.strip():      # `type a, b, c` / `const type* a`: the declarators are the last word of each comma-separated piece
+            names += [re.search(r"(\w+)\s*$", d).group(1) for d in decl.split(",")]
+    return names
+
+
 def test_struct_layouts_match_header(tmp_path):
-    """sizeof / offsetof of the three parameter structs as gcc compiles include/vvhip.h == the ctypes mirrors in hip.py."""
+    """the seven parameter structs of include/vvhip.h == their ctypes mirrors in hip.py: the same member names in the same order, and sizeof / offsetof of
+    EVERY member as gcc compiles the header."""
     import subprocess
     from videovanish_amd import hip
-    probes = {"vv_conv_params": (hip.ConvParams, ["weight", "bias", "out", "ldo", "act", "split_heads", "split_tokens", "tile_hint", "act_slope", "sc_ox", "gn_partials"]),
-              "vv_deform_params": (hip.DeformParams, ["x_dtype", "offset", "flow", "max_residue", "col", "B", "deform_groups", "Wo"]),
-              "vv_attn_params": (hip.AttnParams, ["o", "q_rs", "D", "scale", "q_hs", "v_hs", "q_prescaled", "lse", "o_hs"]),
-              "vv_groupnorm_params": (hip.GroupNormParams, ["groups", "eps", "gamma", "stats_ws", "out_dtype"]),
-              "vv_chain_params": (hip.ChainParams, ["out_dtype", "stream", "M", "text_len", "n_params", "layout", "o_hw"])}
+    mirrors = {"vv_conv_params": hip.ConvParams, "vv_deform_params": hip.DeformParams, "vv_attn_params": hip.AttnParams,
+               "vv_groupnorm_params": hip.GroupNormParams, "vv_chain_params": hip.ChainParams, "vv_motion_params": hip.MotionParams,
+               "vv_chain_front_params": hip.ChainFrontParams}
+    assert sorted(mirrors) == sorted(re.findall(r"\}\s*(vv_\w+_params)\s*;", _header()))      # every struct of the header is probed
+    probes = {name: (cls, [f[0] for f in cls._fields_]) for name, cls in mirrors.items()}
+    for name, (cls, fields) in probes.items():
+        assert fields == _struct_members(name), (name, fields, _struct_members(name))
+    assert len(probes["vv_conv_params"][1]) == 45
     src = ['#include <stdio.h>', '#include <stddef.h>', '#include "vvhip.h"', "int main(void) {"]
     for name, (_, fields) in probes.items():
         src.append(f'  printf("{name} %zu", sizeof({name}));')
@@ -175,6 +233,7 @@ def test_struct_layouts_match_header(tmp_path):
     exe = tmp_path / "probe"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)], check=True)
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.strip().splitlines()
+    assert len(out) == len(probes)
     for line in out:
         parts = line.split()
         cls, fields = probes[parts[0]]

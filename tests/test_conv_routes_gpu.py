@@ -379,6 +379,6 @@ def test_profile_label_is_the_route(gpu, monkeypatch):
         kw, wp, x0, K = _launch(gpu, "fp16", torch.float16, c, epi, 50 + i, 0)
         route = hip.conv_gemm_route(hip.F16, x0, wp, c["N"], K, gn_partials=gn, **kw)
         assert route == want_route, hip.route_name(route)
-        hip.conv_gemm(hip.F16, x0, wp, c["N"], K, gn_partials=gn, **kw)
+        hip.conv_gemm(hip.F16, x0, wp, c["N"], K, gn_partials=hip.GNPartials(c["F"], kw["Hout"], kw["Wout"], c["N"], gpu) if gn else None, **kw)
         assert hip.PROFILE[-1][0] == want_key
     torch.cuda.synchronize()

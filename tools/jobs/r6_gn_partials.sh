@@ -14,8 +14,9 @@ for (Fr, H, W, C) in ((32, 90, 160, 320), (32, 45, 80, 640)):
     x = torch.randn(Fr * H * W, C, device="cuda").to(ctx.h16); res = torch.randn(Fr * H * W, C, device="cuda")
     g, b = torch.ones(C, device="cuda"), torch.zeros(C, device="cuda")
     def run(flag):
-        out, _, _ = conv(x, Fr, H, W, res0=res, gn_partials=flag)
-        return hip.groupnorm(ctx.dt, out, g, b, 32, 1e-6, F=Fr, HW=H * W, partials=getattr(out, "vv_gn", None))
+        gn = hip.GNPartials(Fr, H, W, C, "cuda") if flag else None
+        out, _, _ = conv(x, Fr, H, W, res0=res, gn_partials=gn)
+        return hip.groupnorm(ctx.dt, out, g, b, 32, 1e-6, F=Fr, HW=H * W, partials=gn)
     for r in range(3):
         for flag in (False, True):
             for _ in range(3): run(flag)

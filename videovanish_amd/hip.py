@@ -1,5 +1,8 @@
 """ctypes binding of libvvhip.so (include/vvhip.h).  PyTorch is used only for device memory and streams.
 
+The C ABI is declared once, in SIGNATURES, and lib() applies it: the wrappers pass plain Python values (an int64_t or float parameter is converted by its declaration, a pointer is
+an address (data_ptr(), _p(t)), a struct goes through C.byref) and a value of the wrong kind raises ctypes.ArgumentError.  tests/test_abi_cpu.py holds table and struct mirrors against the header.
+
 There is NO fallback: if the shared library is missing or a launcher reports an error, a RuntimeError is raised
 (the GUI turns exceptions into a dialog -- reference videovanish.py:121-128,1341-1343).
 """
@@ -103,19 +106,99 @@ class AttnParams(C.Structure):
                 ("scale", C.c_float), ("q_hs", C.c_int64), ("k_hs", C.c_int64), ("v_hs", C.c_int64), ("q_prescaled", C.c_int32), ("lse", C.c_void_p), ("o_hs", C.c_int64)]
 
 
-EXPORTS = ["vv_abi_version", "vv_last_error", "vv_device_count", "vv_device_name", "vv_conv_gemm", "vv_conv_gemm_route", "vv_groupnorm_nsplit",
-           "vv_groupnorm", "vv_layernorm", "vv_attention", "vv_axpby_f32", "vv_silu_f32", "vv_sched_step", "vv_add_inplace",
-           "vv_mask_collapse_dilate", "vv_resize_bilinear_u8", "vv_resize_nearest_u8", "vv_feather_composite", "vv_chamfer_dt", "vv_mask_bbox", "vv_roi_paste_composite",
-           "vv_mask_tile_union", "vv_mask_bbox_tiles",
-           "vv_preprocess", "vv_brushnet_input", "vv_pad_channels", "vv_decode_blend", "vv_blur_compose",
-           "vv_avgpool2_f32", "vv_corr_lookup", "vv_raft_ctx_split", "vv_raft_flow_prep", "vv_gru_rh", "vv_gru_update", "vv_add_flow",
-           "vv_add_relu_f32", "vv_convex_upsample", "vv_fb_valid", "vv_deform_im2col", "vv_fc_input", "vv_upsample2x_bilinear", "vv_flow_combine", "vv_gather_rows", "vv_fold_patches", "vv_flow_down4", "vv_gen_compose", "vv_gen_input", "vv_prop_fill", "vv_prop_combine", "vv_masked_sum_u8", "vv_u8_to_f32", "vv_u8_is_zero",
-           "vv_raft_prep", "vv_split_f32", "vv_pad_channels_f32", "vv_window_average",
-           "vv_groupnorm_stats", "vv_gn_affine", "vv_conv_gn_partial_blocks", "vv_gn_finalize_partials", "vv_groupnorm_apply_fin", "vv_motion_module_c320", "vv_split3", "vv_spatial_chain_c320", "vv_spatial_chain_front_c320", "vv_gn_affine_frames",
-           # SAM 2 (row n4)
-           "vv_u8_normalize", "vv_layernorm_ex", "vv_maxpool2x2", "vv_rope_apply", "vv_dwconv", "vv_pixel_shuffle2", "vv_resize_bilinear_f32",
-           "vv_mask_mem_input", "vv_act", "vv_prompt_points", "vv_sine_pe_1d", "vv_sam_select", "vv_sam_pick", "vv_select_f32",
-           "vv_add_rowvec_unless", "vv_clamp_f32", "vv_fill_holes", "vv_hyper_masks", "vv_attention_merge", "vv_ycbcr_to_rgb", "vv_sam2_maskdown"]
+# Every function of include/vvhip.h: name -> (restype, argtypes), in the header's order.  Every pointer is P whatever its pointee: device addresses are
+# ints, the host arrays (vv_blur_compose host_taps21, vv_u8_normalize mean3 / istd3) are ctypes arrays, structs are passed with C.byref.
+P, I, L, Fl = C.c_void_p, C.c_int, C.c_int64, C.c_float
+SIGNATURES = {
+    "vv_abi_version": (I, ()),
+    "vv_last_error": (C.c_char_p, ()),
+    "vv_device_count": (I, ()),
+    "vv_device_name": (I, (I, P, I)),
+    "vv_conv_gemm": (I, (P, I, P)),
+    "vv_conv_gemm_route": (I, (P, I)),
+    "vv_conv_gn_partial_blocks": (I, (I, I)),
+    "vv_gn_finalize_partials": (I, (P, I, I, I, I, I, Fl, I, P, P)),
+    "vv_groupnorm_nsplit": (I, (I, I)),
+    "vv_groupnorm_apply_fin": (I, (P, P, I, P)),
+    "vv_groupnorm": (I, (P, I, P)),
+    "vv_groupnorm_stats": (I, (P, I, P)),
+    "vv_gn_affine": (I, (P, P, P, I, I, P, P)),
+    "vv_motion_module_c320": (I, (P, I, P)),
+    "vv_spatial_chain_c320": (I, (P, I, P)),
+    "vv_spatial_chain_front_c320": (I, (P, I, P)),
+    "vv_gn_affine_frames": (I, (P, P, P, I, I, I, P, P)),
+    "vv_layernorm": (I, (P, I, I, P, P, P, I, P, I, P)),
+    "vv_attention": (I, (P, I, P)),
+    "vv_attention_merge": (I, (P, P, I, I, I, I, I, P, I, P)),
+    "vv_axpby_f32": (I, (P, P, Fl, Fl, P, L, P)),
+    "vv_sched_step": (I, (P, P, P, Fl, Fl, Fl, Fl, Fl, P, L, P)),
+    "vv_silu_f32": (I, (P, P, L, P)),
+    "vv_add_inplace": (I, (P, P, I, L, I, P)),
+    "vv_mask_collapse_dilate": (I, (P, I, I, I, I, I, P, P, P, P)),
+    "vv_resize_bilinear_u8": (I, (P, I, I, I, I, P, I, I, P)),
+    "vv_resize_nearest_u8": (I, (P, I, I, I, I, P, I, I, P)),
+    "vv_ycbcr_to_rgb": (I, (P, P, P, I, I, I, I, I, I, P, P)),
+    "vv_feather_composite": (I, (P, P, P, I, I, I, Fl, P, P)),
+    "vv_chamfer_dt": (I, (P, I, I, I, I, P, P)),
+    "vv_mask_bbox": (I, (P, I, I, I, P, P)),
+    "vv_roi_paste_composite": (I, (P, I, I, P, P, P, I, I, I, I, I, Fl, P, P)),
+    "vv_mask_tile_union": (I, (P, I, I, I, I, P, P)),
+    "vv_mask_bbox_tiles": (I, (P, I, I, I, I, P, I, I, P, P)),
+    "vv_avgpool2_f32": (I, (P, L, I, I, P, P)),
+    "vv_corr_lookup": (I, (P, P, P, P, I, I, P, L, I, P, I, P)),
+    "vv_raft_ctx_split": (I, (P, L, P, P, P, I, P)),
+    "vv_raft_flow_prep": (I, (P, L, I, I, P, P, I, P)),
+    "vv_gru_rh": (I, (P, P, L, P, I, P)),
+    "vv_gru_update": (I, (P, P, L, P, P, I, P)),
+    "vv_add_flow": (I, (P, P, I, L, P)),
+    "vv_add_relu_f32": (I, (P, P, P, L, P)),
+    "vv_convex_upsample": (I, (P, P, I, I, I, P, P)),
+    "vv_fb_valid": (I, (P, P, I, I, P, P)),
+    "vv_deform_im2col": (I, (P, I, P)),
+    "vv_fc_input": (I, (P, P, I, I, I, I, P, P)),
+    "vv_upsample2x_bilinear": (I, (P, I, I, I, I, I, P, I, P)),
+    "vv_flow_combine": (I, (P, I, P, P, L, P, P)),
+    "vv_gather_rows": (I, (P, P, L, I, P, P)),
+    "vv_fold_patches": (I, (P, I, I, I, I, I, I, I, I, I, I, I, I, P, I, I, P)),
+    "vv_flow_down4": (I, (P, I, I, I, P, P)),
+    "vv_gen_input": (I, (P, P, P, L, P, P)),
+    "vv_gen_compose": (I, (P, I, P, P, L, P, I, P)),
+    "vv_prop_fill": (I, (P, P, P, P, P, P, I, I, P, P)),
+    "vv_prop_combine": (I, (P, P, P, P, P, P, I, I, P, P, P, P)),
+    "vv_masked_sum_u8": (I, (P, P, L, P, P)),
+    "vv_u8_to_f32": (I, (P, P, L, P)),
+    "vv_u8_is_zero": (I, (P, P, L, P)),
+    "vv_raft_prep": (I, (P, L, P, I, P)),
+    "vv_preprocess": (I, (P, P, I, I, I, P, P, I, P)),
+    "vv_brushnet_input": (I, (P, P, P, I, I, I, I, I, P, I, P)),
+    "vv_pad_channels": (I, (P, L, I, I, Fl, P, I, P)),
+    "vv_window_average": (I, (P, P, I, L, P, P)),
+    "vv_pad_channels_f32": (I, (P, L, I, I, Fl, P, P)),
+    "vv_split_f32": (I, (P, L, Fl, P, P, I, P)),
+    "vv_split3": (I, (P, I, L, I, P, I, P)),
+    "vv_decode_blend": (I, (P, I, P, I, L, P, P)),
+    "vv_blur_compose": (I, (P, P, P, I, I, I, P, P, P, P)),
+    "vv_u8_normalize": (I, (P, I, I, P, P, P, I, I, I, P)),
+    "vv_layernorm_ex": (I, (P, L, I, P, P, Fl, I, P, I, I, I, P)),
+    "vv_maxpool2x2": (I, (P, I, I, I, I, I, L, P, P)),
+    "vv_rope_apply": (I, (P, L, I, I, I, P, I, I, P)),
+    "vv_dwconv": (I, (P, I, I, I, P, P, I, P, P)),
+    "vv_pixel_shuffle2": (I, (P, P, P, I, I, I, I, P, I, I, P)),
+    "vv_resize_bilinear_f32": (I, (P, I, I, I, P, I, I, P)),
+    "vv_mask_mem_input": (I, (P, L, I, Fl, Fl, P, I, P)),
+    "vv_act": (I, (P, I, L, I, P)),
+    "vv_prompt_points": (I, (P, P, I, Fl, P, P, I, P, P)),
+    "vv_sine_pe_1d": (I, (P, I, I, Fl, P, P)),
+    "vv_sam_select": (I, (P, I, I, P, P, I, Fl, Fl, P, P)),
+    "vv_sam_pick": (I, (P, I, P, Fl, P, P)),
+    "vv_select_f32": (I, (P, P, P, L, P, P)),
+    "vv_add_rowvec_unless": (I, (P, P, P, L, I, P)),
+    "vv_clamp_f32": (I, (P, L, Fl, Fl, P, P)),
+    "vv_sam2_maskdown": (I, (P, I, I, I, Fl, Fl, P, P, P, P, P, P, P, P, Fl, P, P, I, P)),
+    "vv_hyper_masks": (I, (P, P, I, I, I, P, P)),
+    "vv_fill_holes": (I, (P, I, I, I, P, P)),
+}
+EXPORTS = list(SIGNATURES)
 
 
 def lib():
@@ -125,15 +208,16 @@ def lib():
         if not os.path.isfile(_LIB_PATH):
             raise RuntimeError(f"videovanish_amd: HIP extension missing ({_LIB_PATH}); run videovanish_amd/csrc/build.sh "
                                "or __graft_entry__.build() -- there is no CPU fallback")
-        L = C.CDLL(_LIB_PATH)
-        L.vv_last_error.restype = C.c_char_p
-        for name in EXPORTS:
-            if not hasattr(L, name):
+        dll = C.CDLL(_LIB_PATH)
+        for name, (restype, argtypes) in SIGNATURES.items():
+            if not hasattr(dll, name):
                 raise RuntimeError(f"libvvhip.so does not export {name}")
-        v = L.vv_abi_version()
+            fn = getattr(dll, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        v = dll.vv_abi_version()
         if v != ABI_VERSION:
             raise RuntimeError(f"libvvhip.so ABI version {v} != {ABI_VERSION}")
-        _lib = L
+        _lib = dll
     return _lib
 
 
@@ -143,11 +227,11 @@ def _check(rc, what):
 
 
 def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
 
 
 def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    return t.data_ptr() if t is not None else 0
 
 
 def dt_of(t):
@@ -220,9 +304,9 @@ def _meta(v, dt):
 def conv_gemm(dtype, x0, weight, N, K, *, x1=None, F=1, Hin=1, Win=1, Hv=None, Wv=None, Hout=None, Wout=None, ksize=1,
               stride=1, pad_t=0, pad_l=0, bias=None, rowvec=None, res0=None, res1=None, out=None, out_dtype=None,
               epilogue=EPI_NONE, out_scale=1.0, C0=None, C1=0, ksize_w=0, act=ACT_NONE, out_col=0, split_heads=0, split_dim=0, split_tokens=0, tile_hint=0,
-              act_slope=0.0, scatter=None, gn_partials=False, _route=False):
-    """Launch vv_conv_gemm.  gn_partials: the layer also leaves per-channel (sum, sum of squares) partials of its output for the GroupNorm that reads it next
-    (vv_conv_params.gn_partials; only the 128 x 160 halo-tile 3x3 kernel can): the returned tensor carries them as `out.vv_gn`.  x0/x1: NHWC activations ([F,Hin,Win,C] or any shape with C last); weight: [Npad,Kpad] h16.
+              act_slope=0.0, scatter=None, gn_partials=None, _route=False):
+    """Launch vv_conv_gemm.  gn_partials (a GNPartials the caller made for this layer's output): the layer also leaves per-channel (sum, sum of squares) partials of its output there
+    for the GroupNorm that reads it next (vv_conv_params.gn_partials; only the 128 x 160 halo-tile 3x3 kernel can, any other launch is refused).  x0/x1: NHWC activations ([F,Hin,Win,C] or any shape with C last); weight: [Npad,Kpad] h16.
     scatter = (OH, OW, sy, sx, oy, ox): row (f, y, x) of this launch goes to row (f*OH + y*sy + oy)*OW + x*sx + ox of `out` (required; residuals
     are read at the same rows) -- the four parity launches of a convolution over a nearest-2x upsampled image (nn.UpConv2x)."""
     if _route:      # conv_gemm_route: nothing is launched, pointers are passed as null / non-null flags
@@ -258,19 +342,17 @@ def conv_gemm(dtype, x0, weight, N, K, *, x1=None, F=1, Hin=1, Win=1, Hv=None, W
                    Win=Win, Hv=Hv, Wv=Wv, Hout=Hout, Wout=Wout, ksize=ksize, stride=stride, pad_t=pad_t, pad_l=pad_l,
                    weight=ptr(weight), N=N, K=K, Kpad=weight.shape[1], Npad=weight.shape[0],
                    bias=ptr(bias), rowvec=ptr(rowvec), res0=ptr(res0), res1=ptr(res1),
-                   res_dtype=res_dt, out=ptr(out, out_col * out.element_size()), out_dtype=dt_of(out),
-                   ldo=out.shape[-1],
+                   res_dtype=res_dt, out=ptr(out, out_col * out.element_size()), out_dtype=dt_of(out), ldo=out.shape[-1],
                    epilogue=epilogue, out_scale=out_scale, ksize_w=ksize_w, act=act, split_heads=split_heads, split_dim=split_dim,
                    split_tokens=split_tokens, tile_hint=tile_hint, act_slope=act_slope,
                    sc_oh=sc[0], sc_ow=sc[1], sc_sy=sc[2], sc_sx=sc[3], sc_oy=sc[4], sc_ox=sc[5])
     if _route:
         p.gn_partials = 1 if gn_partials else 0
         return lib().vv_conv_gemm_route(C.byref(p), dtype)
-    if gn_partials:
-        nblk = lib().vv_conv_gn_partial_blocks(Hout, Wout)
-        part = torch.empty((F, nblk, N, 2), dtype=torch.float32, device=x0.device)
-        p.gn_partials = part.data_ptr()
-        out.vv_gn = GNPartials(part, nblk, F, Hout * Wout, N)
+    if gn_partials is not None:
+        assert (gn_partials.F, gn_partials.nblk, gn_partials.HW, gn_partials.C) == (F, lib().vv_conv_gn_partial_blocks(Hout, Wout), Hout * Wout, N), "GroupNorm partials of another shape"
+        p.gn_partials = _p(gn_partials.part)
+    key = None
     if PROFILE is not None:
         # the tile of the kernel that runs, from the dispatcher itself (vv_conv_gemm_route)
         route = lib().vv_conv_gemm_route(C.byref(p), dtype)
@@ -278,13 +360,10 @@ def conv_gemm(dtype, x0, weight, N, K, *, x1=None, F=1, Hin=1, Win=1, Hv=None, W
         if PROFILE_SHAPES:
             tile = f"M{M},N{N},K{K}|" + tile
         key = f"conv_gemm[{tile},{'f32in' if x0.dtype == torch.float32 else 'h16in'},k{ksize}{'x%d' % ksize_w if ksize_w and ksize_w != ksize else ''}]"
-        es = x0.element_size()
-        nbytes = F * Hin * Win * (C0 + C1) * es + N * K * 2 + M * nout * out.element_size() + sum(
-            M * N * r.element_size() for r in (res0, res1) if r is not None)
-        with _Prof(key, 2.0 * M * N * K, nbytes):
-            _check(lib().vv_conv_gemm(C.byref(p), dtype, _stream()), "vv_conv_gemm")
-        return out
-    _check(lib().vv_conv_gemm(C.byref(p), dtype, _stream()), "vv_conv_gemm")
+    nbytes = F * Hin * Win * (C0 + C1) * x0.element_size() + N * K * 2 + M * nout * out.element_size() + sum(
+        M * N * r.element_size() for r in (res0, res1) if r is not None)
+    with _Prof(key, 2.0 * M * N * K, nbytes):
+        _check(lib().vv_conv_gemm(C.byref(p), dtype, _stream()), "vv_conv_gemm")
     return out
 
 
@@ -297,17 +376,35 @@ def conv_gemm_route(dtype, x0, weight, N, K, **kw):
 
 
 class GNPartials:
-    """per-channel (sum, sum of squares) partials [F, nblk, C, 2] of a tensor, written by the epilogue of the layer that produced it (conv_gemm(gn_partials=True))"""
+    """per-channel (sum, sum of squares) partials [F, nblk, N, 2] of a layer's output [F * Hout * Wout, N]: the caller makes it, conv_gemm(gn_partials=) fills it, groupnorm(partials=) reads it"""
 
-    def __init__(self, part, nblk, F, HW, C):
-        self.part, self.nblk, self.F, self.HW, self.C = part, nblk, F, HW, C
+    def __init__(self, F, Hout, Wout, N, device):
+        self.nblk, self.F, self.HW, self.C = lib().vv_conv_gn_partial_blocks(Hout, Wout), F, Hout * Wout, N
+        self.part = torch.empty((F, self.nblk, N, 2), dtype=torch.float32, device=device)
 
     def finalize(self, groups, eps, pool_frames=False):
         """-> fin [F, groups, 2] (mean, rstd): vv_gn_finalize_partials (double accumulation, fixed order)"""
         fin = torch.empty((self.F, groups, 2), dtype=torch.float32, device=self.part.device)
-        _check(lib().vv_gn_finalize_partials(_p(self.part), self.F, self.nblk, self.C, self.HW, groups, _f(eps), int(bool(pool_frames)), _p(fin), _stream()),
+        _check(lib().vv_gn_finalize_partials(_p(self.part), self.F, self.nblk, self.C, self.HW, groups, eps, int(bool(pool_frames)), _p(fin), _stream()),
                "vv_gn_finalize_partials")
         return fin
+
+
+def _gn_workspace(F, HW, Ctot, groups, device):      # -> (stats_ws of a GroupNorm over [F * HW, Ctot], address of `fin` in it: (mean, rstd) [F, groups, 2] behind the F * nsplit partial records)
+    nsplit = lib().vv_groupnorm_nsplit(HW, Ctot)
+    ws = torch.empty(F * (nsplit + 1) * groups * 2, dtype=torch.float32, device=device)
+    return ws, ws.data_ptr() + F * nsplit * groups * 2 * ws.element_size()
+
+
+def _gn_stats(dtype, x, gamma, beta, groups, eps, F, HW, pool_frames):
+    """the statistics pass of a GroupNorm over x [F * HW, C] alone (vv_groupnorm_stats) -> (address of fin [F, groups, 2], the tensor that keeps it alive)"""
+    Cc = x.shape[-1]
+    ws, fin = _gn_workspace(F, HW, Cc, groups, x.device)
+    gp = GroupNormParams(in0=_p(x), in1=0, in_dtype=dt_of(x), C0=Cc, C1=0, F=F, HW=HW, groups=groups, pool_frames=pool_frames, eps=eps,
+                         gamma=_p(gamma), beta=_p(beta), silu=0, stats_ws=_p(ws), out=0, out_dtype=F32)
+    with _Prof("groupnorm", 0.0, F * HW * Cc * x.element_size()):
+        _check(lib().vv_groupnorm_stats(C.byref(gp), dtype, _stream()), "vv_groupnorm_stats")
+    return fin, ws
 
 
 def groupnorm(dtype, x0, gamma, beta, groups, eps, *, x1=None, F, HW, silu=False, pool_frames=False, out_dtype=None, act=None, partials=None):
@@ -316,17 +413,16 @@ def groupnorm(dtype, x0, gamma, beta, groups, eps, *, x1=None, F, HW, silu=False
     C0 = x0.shape[-1]
     C1 = x1.shape[-1] if x1 is not None else 0
     Ctot = C0 + C1
-    nsplit = lib().vv_groupnorm_nsplit(HW, Ctot)
-    ws = torch.empty(F * (nsplit + 1) * groups * 2, dtype=torch.float32, device=x0.device)
+    ws, _ = _gn_workspace(F, HW, Ctot, groups, x0.device)
     if out_dtype == "split3":          # [M, 3C] h16 = [hi | lo * 2^4 | hi * 2^-10]: feeds a split-precision GEMM directly (no fp32 round trip)
         out = torch.empty((F * HW, 3 * Ctot), dtype=h16(dtype), device=x0.device)
         odt = SPLIT3
     else:
         out = torch.empty((F * HW, Ctot), dtype=h16(dtype) if out_dtype is None else out_dtype, device=x0.device)
         odt = dt_of(out)
-    p = GroupNormParams(in0=x0.data_ptr(), in1=x1.data_ptr() if x1 is not None else 0, in_dtype=dt_of(x0), C0=C0, C1=C1, F=F, HW=HW,
-                        groups=groups, pool_frames=int(pool_frames), eps=eps, gamma=gamma.data_ptr(), beta=beta.data_ptr(),
-                        silu=int(act) if act is not None else int(silu), stats_ws=ws.data_ptr(), out=out.data_ptr(), out_dtype=odt)
+    p = GroupNormParams(in0=_p(x0), in1=_p(x1), in_dtype=dt_of(x0), C0=C0, C1=C1, F=F, HW=HW,
+                        groups=groups, pool_frames=int(pool_frames), eps=eps, gamma=_p(gamma), beta=_p(beta),
+                        silu=int(act) if act is not None else int(silu), stats_ws=_p(ws), out=_p(out), out_dtype=odt)
     if partials is not None:
         assert x1 is None and (partials.F, partials.HW, partials.C) == (F, HW, C0), "GroupNorm partials do not describe this tensor"
         fin = partials.finalize(groups, eps, pool_frames)
@@ -342,18 +438,11 @@ def motion_module_c320(dtype, x, stream_w, params, gamma, beta, groups, eps, *, 
     """The fused motion module (vv_motion.hip): clip-pooled GroupNorm statistics -> per-channel affine -> ONE kernel for the whole block."""
     _need_cuda(x, stream_w, params, gamma, beta, res1)
     Cc = x.shape[-1]
-    nsplit = lib().vv_groupnorm_nsplit(HW, Cc)
-    ws = torch.empty(F * (nsplit + 1) * groups * 2, dtype=torch.float32, device=x.device)
-    gp = GroupNormParams(in0=x.data_ptr(), in1=0, in_dtype=dt_of(x), C0=Cc, C1=0, F=F, HW=HW, groups=groups, pool_frames=1, eps=eps,
-                         gamma=gamma.data_ptr(), beta=beta.data_ptr(), silu=0, stats_ws=ws.data_ptr(), out=0, out_dtype=F32)
-    with _Prof("groupnorm", 0.0, F * HW * Cc * x.element_size()):
-        _check(lib().vv_groupnorm_stats(C.byref(gp), dtype, _stream()), "vv_groupnorm_stats")
+    fin, keep = _gn_stats(dtype, x, gamma, beta, groups, eps, F, HW, 1)      # keep: owns fin until the launches below are enqueued
     aff = torch.empty((2, Cc), dtype=torch.float32, device=x.device)
-    fin = ws.data_ptr() + F * nsplit * groups * 2 * 4
-    _check(lib().vv_gn_affine(C.c_void_p(fin), _p(gamma), _p(beta), Cc, groups, _p(aff), _stream()), "vv_gn_affine")
+    _check(lib().vv_gn_affine(fin, _p(gamma), _p(beta), Cc, groups, _p(aff), _stream()), "vv_gn_affine")
     out = torch.empty((F * HW, Cc), dtype=out_dtype, device=x.device)
-    mp = MotionParams(x=x.data_ptr(), res1=res1.data_ptr() if res1 is not None else 0, out=out.data_ptr(), out_dtype=dt_of(out),
-                      stream=stream_w.data_ptr(), params=params.data_ptr(), gn_affine=aff.data_ptr(), C=Cc, F=F, heads=8, HW=HW,
+    mp = MotionParams(x=_p(x), res1=_p(res1), out=_p(out), out_dtype=dt_of(out), stream=_p(stream_w), params=_p(params), gn_affine=_p(aff), C=Cc, F=F, heads=8, HW=HW,
                       n_slabs=stream_w.shape[0], n_params=params.numel())
     with _Prof("motion_module_fused[c320]", 2.0 * 22 * Cc * Cc * F * HW + 8.0 * F * Cc * F * HW, F * HW * Cc * (x.element_size() * 2 + out.element_size())):
         _check(lib().vv_motion_module_c320(C.byref(mp), dtype, _stream()), "vv_motion_module_c320")
@@ -380,9 +469,9 @@ def attention(dtype, q, k, v, out, *, B, heads, Nq, Nkv, D, q_bs, k_bs, v_bs, o_
     q_prescaled: q already carries D**-0.5 * log2(e) (attention_q_scale(D) folded into the query projection)."""
     _need_cuda(q, k, v, out)
     es = 2
-    p = AttnParams(q=q.data_ptr() + q_off * es, k=k.data_ptr() + k_off * es, v=v.data_ptr() + v_off * es, o=out.data_ptr(),
+    p = AttnParams(q=q.data_ptr() + q_off * es, k=k.data_ptr() + k_off * es, v=v.data_ptr() + v_off * es, o=_p(out),
                    q_bs=q_bs, k_bs=k_bs, v_bs=v_bs, o_bs=o_bs, q_rs=q_rs, k_rs=k_rs, v_rs=v_rs, o_rs=o_rs, B=B, heads=heads, Nq=Nq,
-                   Nkv=Nkv, D=D, scale=float(D) ** -0.5 if scale is None else float(scale), q_hs=q_hs, k_hs=k_hs, v_hs=v_hs, q_prescaled=1 if q_prescaled else 0, lse=lse.data_ptr() if lse is not None else 0, o_hs=o_hs)
+                   Nkv=Nkv, D=D, scale=float(D) ** -0.5 if scale is None else float(scale), q_hs=q_hs, k_hs=k_hs, v_hs=v_hs, q_prescaled=1 if q_prescaled else 0, lse=_p(lse), o_hs=o_hs)
     kind = "temporal" if (Nq <= 32 and Nkv <= 32) else ("cross" if Nkv < 128 and Nq != Nkv else "spatial")
     if PROFILE_SHAPES:
         kind = f"B{B},N{Nq}|" + kind
@@ -403,8 +492,8 @@ def deform_im2col(dtype, x, *, B, H, W, kh=3, kw=3, stride=1, pad=1, dil=1, defo
     for t in (offset, mask, raw, flow):
         if t is not None and t.dtype != torch.float32:
             raise RuntimeError("vv_deform_im2col: offset / mask / raw / flow must be fp32")
-    p = DeformParams(x=x.data_ptr(), x_dtype=dt_of(x), offset=_p(offset), mask=_p(mask), raw=_p(raw), flow=_p(flow), max_residue=max_residue,
-                     col=col.data_ptr(), B=B, H=H, W=W, C=Cc, kh=kh, kw=kw, stride=stride, pad=pad, dil=dil, deform_groups=deform_groups, Ho=Ho, Wo=Wo)
+    p = DeformParams(x=_p(x), x_dtype=dt_of(x), offset=_p(offset), mask=_p(mask), raw=_p(raw), flow=_p(flow), max_residue=max_residue,
+                     col=_p(col), B=B, H=H, W=W, C=Cc, kh=kh, kw=kw, stride=stride, pad=pad, dil=dil, deform_groups=deform_groups, Ho=Ho, Wo=Wo)
     with _Prof("deform_im2col", 0.0, col.numel() * 2 * 5):
         _check(lib().vv_deform_im2col(C.byref(p), dtype, _stream()), "vv_deform_im2col")
     return col, Ho, Wo
@@ -432,7 +521,7 @@ def flow_combine(pred, flow, mask_u8):
     """pred fp32 [N, ld>=2], flow fp32 [..., 2] with N pixels, mask u8 [N] -> fp32 like flow: pred in the hole, flow outside."""
     _need_cuda(pred, flow, mask_u8)
     out = torch.empty_like(flow)
-    _check(lib().vv_flow_combine(_p(pred), pred.shape[-1], _p(flow), _p(mask_u8), C.c_int64(mask_u8.numel()), _p(out), _stream()), "vv_flow_combine")
+    _check(lib().vv_flow_combine(_p(pred), pred.shape[-1], _p(flow), _p(mask_u8), mask_u8.numel(), _p(out), _stream()), "vv_flow_combine")
     return out
 
 
@@ -440,7 +529,7 @@ def gather_rows(src, idx):
     """out[i] = src[idx[i]] (idx int32 on the device, < 0 -> zero row); rows must be multiples of 16 bytes."""
     _need_cuda(src, idx)
     out = torch.empty((idx.numel(), src.shape[-1]), dtype=src.dtype, device=src.device)
-    _check(lib().vv_gather_rows(_p(src), _p(idx), C.c_int64(idx.numel()), src.shape[-1] * src.element_size(), _p(out), _stream()), "vv_gather_rows")
+    _check(lib().vv_gather_rows(_p(src), _p(idx), idx.numel(), src.shape[-1] * src.element_size(), _p(out), _stream()), "vv_gather_rows")
     return out
 
 
@@ -467,42 +556,42 @@ def gen_input(frames_u8, mask_in_u8, mask_up_u8):
     _need_cuda(frames_u8, mask_in_u8, mask_up_u8)
     n = mask_in_u8.numel()
     out = torch.empty((n, 8), dtype=torch.float32, device=frames_u8.device)
-    _check(lib().vv_gen_input(_p(frames_u8), _p(mask_in_u8), _p(mask_up_u8), C.c_int64(n), _p(out), _stream()), "vv_gen_input")
+    _check(lib().vv_gen_input(_p(frames_u8), _p(mask_in_u8), _p(mask_up_u8), n, _p(out), _stream()), "vv_gen_input")
     return out
 
 
 def gen_compose(pred, ori_u8, mask_u8, acc, first):
     _need_cuda(pred, ori_u8, mask_u8, acc)
-    _check(lib().vv_gen_compose(_p(pred), pred.shape[-1], _p(ori_u8), _p(mask_u8), C.c_int64(mask_u8.numel()), _p(acc), int(first), _stream()), "vv_gen_compose")
+    _check(lib().vv_gen_compose(_p(pred), pred.shape[-1], _p(ori_u8), _p(mask_u8), mask_u8.numel(), _p(acc), int(first), _stream()), "vv_gen_compose")
     return acc
 
 
 def axpby(x, y, ca, cb, out=None):
     _need_cuda(x, y, out)
     out = torch.empty_like(x) if out is None else out
-    _check(lib().vv_axpby_f32(_p(x), _p(y), C.c_float(ca), C.c_float(cb), _p(out), C.c_int64(x.numel()), _stream()), "vv_axpby_f32")
+    _check(lib().vv_axpby_f32(_p(x), _p(y), ca, cb, _p(out), x.numel(), _stream()), "vv_axpby_f32")
     return out
 
 
 def sched_step(x, eps, z, sa_t, sb_t, c_x0, c_eps, c_z=0.0, out=None):
     _need_cuda(x, eps, z, out)
     out = torch.empty_like(x) if out is None else out
-    _check(lib().vv_sched_step(_p(x), _p(eps), _p(z), C.c_float(sa_t), C.c_float(sb_t), C.c_float(c_x0), C.c_float(c_eps), C.c_float(c_z),
-                               _p(out), C.c_int64(x.numel()), _stream()), "vv_sched_step")
+    _check(lib().vv_sched_step(_p(x), _p(eps), _p(z), sa_t, sb_t, c_x0, c_eps, c_z,
+                               _p(out), x.numel(), _stream()), "vv_sched_step")
     return out
 
 
 def silu(x):
     _need_cuda(x)
     out = torch.empty_like(x)
-    _check(lib().vv_silu_f32(_p(x), _p(out), C.c_int64(x.numel()), _stream()), "vv_silu_f32")
+    _check(lib().vv_silu_f32(_p(x), _p(out), x.numel(), _stream()), "vv_silu_f32")
     return out
 
 
 def add_inplace(dtype, x, y):
     _need_cuda(x, y)
     assert x.dtype == torch.float32 and x.numel() == y.numel()
-    _check(lib().vv_add_inplace(_p(x), _p(y), dt_of(y), C.c_int64(x.numel()), dtype, _stream()), "vv_add_inplace")
+    _check(lib().vv_add_inplace(_p(x), _p(y), dt_of(y), x.numel(), dtype, _stream()), "vv_add_inplace")
     return x
 
 
@@ -536,7 +625,7 @@ def feather_composite(inpainted, orig, mask2d, feather_px):
     T, H, W, _ = inpainted.shape
     out = torch.empty_like(inpainted)
     with _Prof("feather_composite", 0.0, T * H * W * (3 + 3 + 1 + 3)):
-        _check(lib().vv_feather_composite(_p(inpainted), _p(orig), _p(mask2d), T, H, W, C.c_float(feather_px), _p(out), _stream()), "vv_feather_composite")
+        _check(lib().vv_feather_composite(_p(inpainted), _p(orig), _p(mask2d), T, H, W, feather_px, _p(out), _stream()), "vv_feather_composite")
     return out
 
 
@@ -590,7 +679,7 @@ def roi_paste_composite(patch, orig, mask2d, offsets, h, w, feather_px, out=None
     elif out.shape != orig.shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.data_ptr() == orig.data_ptr():
         raise RuntimeError("roi_paste_composite: out must be a contiguous u8 buffer of orig's shape, not orig itself")
     with _Prof("roi_paste_composite", 0.0, T * H0 * W0 * (3 + 1 + 3) + patch.numel()):
-        _check(lib().vv_roi_paste_composite(_p(patch), Hm, Wm, _p(orig), _p(mask2d), _p(offsets), T, H0, W0, int(h), int(w), C.c_float(feather_px), _p(out),
+        _check(lib().vv_roi_paste_composite(_p(patch), Hm, Wm, _p(orig), _p(mask2d), _p(offsets), T, H0, W0, int(h), int(w), feather_px, _p(out),
                                             _stream()), "vv_roi_paste_composite")
     return out
 
@@ -625,7 +714,7 @@ def pad_channels(dtype, x, cpad, scale=1.0):
     cin = x.shape[-1]
     rows = x.numel() // cin
     out = torch.empty(x.shape[:-1] + (cpad,), dtype=h16(dtype), device=x.device)
-    _check(lib().vv_pad_channels(_p(x), C.c_int64(rows), cin, cpad, C.c_float(scale), _p(out), dtype, _stream()), "vv_pad_channels")
+    _check(lib().vv_pad_channels(_p(x), rows, cin, cpad, scale, _p(out), dtype, _stream()), "vv_pad_channels")
     return out
 
 
@@ -634,7 +723,7 @@ def window_average(value, count):
     _need_cuda(value, count)
     T = value.shape[0]
     out = torch.empty_like(value)
-    _check(lib().vv_window_average(_p(value), _p(count), T, C.c_int64(value.numel() // T), _p(out), _stream()), "vv_window_average")
+    _check(lib().vv_window_average(_p(value), _p(count), T, value.numel() // T, _p(out), _stream()), "vv_window_average")
     return out
 
 
@@ -643,7 +732,7 @@ def pad_channels_f32(x, cpad, scale=1.0):
     cin = x.shape[-1]
     rows = x.numel() // cin
     out = torch.empty(x.shape[:-1] + (cpad,), dtype=torch.float32, device=x.device)
-    _check(lib().vv_pad_channels_f32(_p(x), C.c_int64(rows), cin, cpad, C.c_float(scale), _p(out), _stream()), "vv_pad_channels_f32")
+    _check(lib().vv_pad_channels_f32(_p(x), rows, cin, cpad, scale, _p(out), _stream()), "vv_pad_channels_f32")
     return out
 
 
@@ -653,7 +742,7 @@ def split_f32(dtype, x, lo_scale):
     assert x.dtype == torch.float32
     hi = torch.empty(x.shape, dtype=h16(dtype), device=x.device)
     lo = torch.empty(x.shape, dtype=h16(dtype), device=x.device)
-    _check(lib().vv_split_f32(_p(x), C.c_int64(x.numel()), C.c_float(lo_scale), _p(hi), _p(lo), dtype, _stream()), "vv_split_f32")
+    _check(lib().vv_split_f32(_p(x), x.numel(), lo_scale, _p(hi), _p(lo), dtype, _stream()), "vv_split_f32")
     return hi, lo
 
 
@@ -671,8 +760,8 @@ def spatial_chain_c320(dtype, o, t_in, x, stream_w, params, *, res1=None, out_dt
     assert o.numel() == M * Cc and x.shape == (M, Cc) and o.dtype == h16(dtype) and t_in.dtype == x.dtype == torch.float32
     assert (o.shape == (M, Cc)) if o_hw == 0 else (M % o_hw == 0 and o.is_contiguous())
     out = torch.empty((M, Cc), dtype=out_dtype, device=x.device)
-    cp = ChainParams(o=o.data_ptr(), t_in=t_in.data_ptr(), x=x.data_ptr(), res1=res1.data_ptr() if res1 is not None else 0, out=out.data_ptr(),
-                     out_dtype=dt_of(out), stream=stream_w.data_ptr(), params=params.data_ptr(), M=M, C=Cc, heads=8, text_len=77,
+    cp = ChainParams(o=_p(o), t_in=_p(t_in), x=_p(x), res1=_p(res1), out=_p(out),
+                     out_dtype=dt_of(out), stream=_p(stream_w), params=_p(params), M=M, C=Cc, heads=8, text_len=77,
                      n_slabs=stream_w.shape[0], n_params=params.numel(), layout=CHAIN_LAYOUT_IDS[_packing().CHAIN_LAYOUT], o_hw=int(o_hw))
     flops = 2.0 * M * Cc * Cc * (1 + 1 + 1 + 12 + 1) + 4.0 * M * 77 * Cc
     with _Prof("spatial_chain_fused[c320]", flops, M * Cc * (2 + 4 + 4 + out.element_size())):
@@ -688,23 +777,17 @@ def spatial_chain_front_c320(dtype, x, gamma, beta, groups, eps, stream_w, param
     M, Cc = x.shape
     assert M == F * HW and x.dtype == torch.float32
     aff = torch.empty((F, 2, Cc), dtype=torch.float32, device=x.device)
-    if partials is not None:      # the producing convolution left per-channel partial sums of x (conv_gemm(gn_partials=True)): no statistics pass over HBM
+    if partials is not None:      # the producing convolution left per-channel partial sums of x (conv_gemm(gn_partials=)): no statistics pass over HBM
         assert (partials.F, partials.HW, partials.C) == (F, HW, Cc), "GroupNorm partials do not describe this tensor"
-        fin_t = partials.finalize(groups, eps)
-        fin = fin_t.data_ptr()
+        keep = partials.finalize(groups, eps)
+        fin = _p(keep)
     else:
-        nsplit = lib().vv_groupnorm_nsplit(HW, Cc)
-        ws = torch.empty(F * (nsplit + 1) * groups * 2, dtype=torch.float32, device=x.device)
-        gp = GroupNormParams(in0=x.data_ptr(), in1=0, in_dtype=dt_of(x), C0=Cc, C1=0, F=F, HW=HW, groups=groups, pool_frames=0, eps=eps,
-                             gamma=gamma.data_ptr(), beta=beta.data_ptr(), silu=0, stats_ws=ws.data_ptr(), out=0, out_dtype=F32)
-        with _Prof("groupnorm", 0.0, F * HW * Cc * x.element_size()):
-            _check(lib().vv_groupnorm_stats(C.byref(gp), dtype, _stream()), "vv_groupnorm_stats")
-        fin = ws.data_ptr() + F * nsplit * groups * 2 * 4
-    _check(lib().vv_gn_affine_frames(C.c_void_p(fin), _p(gamma), _p(beta), Cc, groups, F, _p(aff), _stream()), "vv_gn_affine_frames")
+        fin, keep = _gn_stats(dtype, x, gamma, beta, groups, eps, F, HW, 0)
+    _check(lib().vv_gn_affine_frames(fin, _p(gamma), _p(beta), Cc, groups, F, _p(aff), _stream()), "vv_gn_affine_frames")
     t = torch.empty((M, Cc), dtype=torch.float32, device=x.device)
     qkv = torch.empty((F, 3, 8, HW, Cc // 8), dtype=h16(dtype), device=x.device)
-    fp = ChainFrontParams(x=x.data_ptr(), gn_affine=aff.data_ptr(), t_out=t.data_ptr(), qkv=qkv.data_ptr(), stream=stream_w.data_ptr(),
-                          params=params.data_ptr(), M=M, HW=HW, C=Cc, heads=8, n_slabs=stream_w.shape[0], n_params=params.numel())
+    fp = ChainFrontParams(x=_p(x), gn_affine=_p(aff), t_out=_p(t), qkv=_p(qkv), stream=_p(stream_w),
+                          params=_p(params), M=M, HW=HW, C=Cc, heads=8, n_slabs=stream_w.shape[0], n_params=params.numel())
     with _Prof("spatial_chain_front_fused[c320]", 2.0 * M * Cc * Cc * 4, M * Cc * (4 + 4 + 6)):
         _check(lib().vv_spatial_chain_front_c320(C.byref(fp), dtype, _stream()), "vv_spatial_chain_front_c320")
     return t, qkv
@@ -717,7 +800,7 @@ def split3(dtype, x):
     M, Cc = x.shape
     out = torch.empty((M, 3 * Cc), dtype=h16(dtype), device=x.device)
     with _Prof("split3", 0.0, x.numel() * (x.element_size() + 6)):
-        _check(lib().vv_split3(_p(x), dt_of(x), C.c_int64(M), Cc, _p(out), dtype, _stream()), "vv_split3")
+        _check(lib().vv_split3(_p(x), dt_of(x), M, Cc, _p(out), dtype, _stream()), "vv_split3")
     return out
 
 
@@ -725,7 +808,7 @@ def decode_blend(dec, w, acc):
     """dec [T,H,W,ld] fp32 ; w [T] fp32 ; acc [T,H,W,3] fp32 updated in place."""
     _need_cuda(dec, w, acc)
     T, H, W, ld = dec.shape
-    _check(lib().vv_decode_blend(_p(dec), ld, _p(w), T, C.c_int64(H * W), _p(acc), _stream()), "vv_decode_blend")
+    _check(lib().vv_decode_blend(_p(dec), ld, _p(w), T, H * W, _p(acc), _stream()), "vv_decode_blend")
     return acc
 
 
@@ -746,7 +829,7 @@ def avgpool2(x):
     N, h, w = x.shape
     out = torch.empty((N, h // 2, w // 2), dtype=torch.float32, device=x.device)
     with _Prof("avgpool2[corr pyramid]", 0.0, x.numel() * 5):
-        _check(lib().vv_avgpool2_f32(_p(x), C.c_int64(N), h, w, _p(out), _stream()), "vv_avgpool2_f32")
+        _check(lib().vv_avgpool2_f32(_p(x), N, h, w, _p(out), _stream()), "vv_avgpool2_f32")
     return out
 
 
@@ -756,7 +839,7 @@ def corr_lookup(dtype, pyr, coords, cpad=384):
     N, h, w = pyr[0].shape
     out = torch.empty((N, cpad), dtype=h16(dtype), device=coords.device)
     with _Prof("corr_lookup", 0.0, N * (4 * 100 * 4 + 324 * 2 + 8)):
-        _check(lib().vv_corr_lookup(_p(pyr[0]), _p(pyr[1]), _p(pyr[2]), _p(pyr[3]), h, w, _p(coords), C.c_int64(N), cpad, _p(out), dtype, _stream()),
+        _check(lib().vv_corr_lookup(_p(pyr[0]), _p(pyr[1]), _p(pyr[2]), _p(pyr[3]), h, w, _p(coords), N, cpad, _p(out), dtype, _stream()),
                "vv_corr_lookup")
     return out
 
@@ -764,38 +847,38 @@ def corr_lookup(dtype, pyr, coords, cpad=384):
 def raft_ctx_split(dtype, cn, net, net16, xbuf):
     _need_cuda(cn, net, net16, xbuf)
     with _Prof("raft_elementwise", 0.0, cn.numel() * 4 + net.numel() * 6 + xbuf.shape[0] * 256):
-        _check(lib().vv_raft_ctx_split(_p(cn), C.c_int64(cn.shape[0]), _p(net), _p(net16), _p(xbuf), dtype, _stream()), "vv_raft_ctx_split")
+        _check(lib().vv_raft_ctx_split(_p(cn), cn.shape[0], _p(net), _p(net16), _p(xbuf), dtype, _stream()), "vv_raft_ctx_split")
 
 
 def raft_flow_prep(dtype, coords1, w, h, flow8, xbuf):
     _need_cuda(coords1, flow8, xbuf)
     with _Prof("raft_elementwise", 0.0, coords1.numel() * 4 + flow8.numel() * 2 + coords1.shape[0] * 4):
-        _check(lib().vv_raft_flow_prep(_p(coords1), C.c_int64(coords1.shape[0]), w, h, _p(flow8), _p(xbuf), dtype, _stream()), "vv_raft_flow_prep")
+        _check(lib().vv_raft_flow_prep(_p(coords1), coords1.shape[0], w, h, _p(flow8), _p(xbuf), dtype, _stream()), "vv_raft_flow_prep")
 
 
 def gru_rh(dtype, zr, h, rh):
     _need_cuda(zr, h, rh)
     with _Prof("raft_elementwise", 0.0, h.numel() * (2 + 4 + 2)):
-        _check(lib().vv_gru_rh(_p(zr), _p(h), C.c_int64(h.shape[0]), _p(rh), dtype, _stream()), "vv_gru_rh")
+        _check(lib().vv_gru_rh(_p(zr), _p(h), h.shape[0], _p(rh), dtype, _stream()), "vv_gru_rh")
 
 
 def gru_update(dtype, zr, q, h, h16_out):
     _need_cuda(zr, q, h, h16_out)
     with _Prof("raft_elementwise", 0.0, h.numel() * (4 + 2 + 4 + 4 + 2)):
-        _check(lib().vv_gru_update(_p(zr), _p(q), C.c_int64(h.shape[0]), _p(h), _p(h16_out), dtype, _stream()), "vv_gru_update")
+        _check(lib().vv_gru_update(_p(zr), _p(q), h.shape[0], _p(h), _p(h16_out), dtype, _stream()), "vv_gru_update")
 
 
 def add_flow(coords1, dflow):
     _need_cuda(coords1, dflow)
     with _Prof("raft_elementwise", 0.0, coords1.numel() * 12):
-        _check(lib().vv_add_flow(_p(coords1), _p(dflow), dflow.shape[-1], C.c_int64(coords1.shape[0]), _stream()), "vv_add_flow")
+        _check(lib().vv_add_flow(_p(coords1), _p(dflow), dflow.shape[-1], coords1.shape[0], _stream()), "vv_add_flow")
 
 
 def add_relu(a, b):
     _need_cuda(a, b)
     out = torch.empty_like(a)
     with _Prof("add_relu", 0.0, a.numel() * 12):
-        _check(lib().vv_add_relu_f32(_p(a), _p(b), _p(out), C.c_int64(a.numel()), _stream()), "vv_add_relu_f32")
+        _check(lib().vv_add_relu_f32(_p(a), _p(b), _p(out), a.numel(), _stream()), "vv_add_relu_f32")
     return out
 
 
@@ -838,21 +921,21 @@ def masked_sum_u8(frame, hole):
     """-> int64 tensor [4] (sum r, g, b over non-hole pixels, count) on the device."""
     _need_cuda(frame, hole)
     sums = torch.empty(4, dtype=torch.int64, device=frame.device)
-    _check(lib().vv_masked_sum_u8(_p(frame), _p(hole), C.c_int64(hole.numel()), _p(sums), _stream()), "vv_masked_sum_u8")
+    _check(lib().vv_masked_sum_u8(_p(frame), _p(hole), hole.numel(), _p(sums), _stream()), "vv_masked_sum_u8")
     return sums
 
 
 def u8_to_f32(x):
     _need_cuda(x)
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    _check(lib().vv_u8_to_f32(_p(x), _p(out), C.c_int64(x.numel()), _stream()), "vv_u8_to_f32")
+    _check(lib().vv_u8_to_f32(_p(x), _p(out), x.numel(), _stream()), "vv_u8_to_f32")
     return out
 
 
 def u8_is_zero(x):
     _need_cuda(x)
     out = torch.empty_like(x)
-    _check(lib().vv_u8_is_zero(_p(x), _p(out), C.c_int64(x.numel()), _stream()), "vv_u8_is_zero")
+    _check(lib().vv_u8_is_zero(_p(x), _p(out), x.numel(), _stream()), "vv_u8_is_zero")
     return out
 
 
@@ -861,15 +944,11 @@ def raft_prep(dtype, img):
     _need_cuda(img)
     out = torch.empty(img.shape[:-1] + (8,), dtype=h16(dtype), device=img.device)
     with _Prof("raft_prep", 0.0, img.numel() + out.numel() * 2):
-        _check(lib().vv_raft_prep(_p(img), C.c_int64(img.numel() // 3), _p(out), dtype, _stream()), "vv_raft_prep")
+        _check(lib().vv_raft_prep(_p(img), img.numel() // 3, _p(out), dtype, _stream()), "vv_raft_prep")
     return out
 
 
 # ---- SAM 2 (include/vvhip.h "SAM 2" section) ---------------------------------------------------------------------
-def _f(x):
-    return C.c_float(float(x))
-
-
 def u8_normalize(dtype, img_u8, mean, std, cpad=8, s2d=1):
     """uint8 [H, W, 3] -> h16 [(H/s2d)*(W/s2d), cpad] = ((x / 255) - mean) / std; s2d > 1: space-to-depth blocks, channel (dy*s2d + dx)*3 + c."""
     _need_cuda(img_u8)
@@ -888,7 +967,7 @@ def layernorm_ex(dtype, x, gamma, beta, eps, act=ACT_NONE, out_dtype=None, cpad=
     M, Cc = x.shape
     cp = Cc if cpad is None else cpad
     out = torch.empty((M, cp), dtype=h16(dtype) if out_dtype is None else out_dtype, device=x.device)
-    _check(lib().vv_layernorm_ex(_p(x), C.c_int64(M), Cc, _p(gamma), _p(beta), _f(eps), act, _p(out), dt_of(out), cp, dtype, _stream()), "vv_layernorm_ex")
+    _check(lib().vv_layernorm_ex(_p(x), M, Cc, _p(gamma), _p(beta), eps, act, _p(out), dt_of(out), cp, dtype, _stream()), "vv_layernorm_ex")
     return out
 
 
@@ -897,7 +976,7 @@ def maxpool2x2(x, B, H, W, Cc=None, in_bs=0, x_off=0):
     _need_cuda(x)
     Cc = x.shape[-1] if Cc is None else Cc
     out = torch.empty((B * (H // 2) * (W // 2), Cc), dtype=x.dtype, device=x.device)
-    _check(lib().vv_maxpool2x2(C.c_void_p(x.data_ptr() + x_off * x.element_size()), dt_of(x), B, H, W, Cc, C.c_int64(in_bs), _p(out), _stream()),
+    _check(lib().vv_maxpool2x2(x.data_ptr() + x_off * x.element_size(), dt_of(x), B, H, W, Cc, in_bs, _p(out), _stream()),
            "vv_maxpool2x2")
     return out
 
@@ -905,7 +984,7 @@ def maxpool2x2(x, B, H, W, Cc=None, in_bs=0, x_off=0):
 def rope_apply(dtype, x, rows_rope, cos_sin, D, col0=0, ld=None):
     """in place: rows < rows_rope of the h16 matrix x, columns col0 .. col0 + D, rotated pairwise by cos_sin [n, D/2, 2] (row r uses r % n)."""
     _need_cuda(x, cos_sin)
-    _check(lib().vv_rope_apply(_p(x), C.c_int64(rows_rope), x.shape[-1] if ld is None else ld, col0, D, _p(cos_sin), cos_sin.shape[0], dtype,
+    _check(lib().vv_rope_apply(_p(x), rows_rope, x.shape[-1] if ld is None else ld, col0, D, _p(cos_sin), cos_sin.shape[0], dtype,
                                _stream()), "vv_rope_apply")
     return x
 
@@ -938,13 +1017,13 @@ def mask_mem_input(dtype, logits, binarize, scale, bias):
     _need_cuda(logits)
     n = logits.numel()
     out = torch.empty((n, 8), dtype=h16(dtype), device=logits.device)
-    _check(lib().vv_mask_mem_input(_p(logits), C.c_int64(n), int(bool(binarize)), _f(scale), _f(bias), _p(out), dtype, _stream()), "vv_mask_mem_input")
+    _check(lib().vv_mask_mem_input(_p(logits), n, int(bool(binarize)), scale, bias, _p(out), dtype, _stream()), "vv_mask_mem_input")
     return out
 
 
 def act_inplace(x, act):
     _need_cuda(x)
-    _check(lib().vv_act(_p(x), dt_of(x), C.c_int64(x.numel()), act, _stream()), "vv_act")
+    _check(lib().vv_act(_p(x), dt_of(x), x.numel(), act, _stream()), "vv_act")
     return x
 
 
@@ -952,21 +1031,21 @@ def prompt_points(coords, labels, inv_size, gauss, table):
     _need_cuda(coords, labels, gauss, table)
     P, D = labels.numel(), table.shape[-1]
     out = torch.empty((P, D), dtype=torch.float32, device=coords.device)
-    _check(lib().vv_prompt_points(_p(coords), _p(labels), P, _f(inv_size), _p(gauss), _p(table), D, _p(out), _stream()), "vv_prompt_points")
+    _check(lib().vv_prompt_points(_p(coords), _p(labels), P, inv_size, _p(gauss), _p(table), D, _p(out), _stream()), "vv_prompt_points")
     return out
 
 
 def sine_pe_1d(pos, dim, temperature=10000.0):
     _need_cuda(pos)
     out = torch.empty((pos.numel(), dim), dtype=torch.float32, device=pos.device)
-    _check(lib().vv_sine_pe_1d(_p(pos), pos.numel(), dim, _f(temperature), _p(out), _stream()), "vv_sine_pe_1d")
+    _check(lib().vv_sine_pe_1d(_p(pos), pos.numel(), dim, temperature, _p(out), _stream()), "vv_sine_pe_1d")
     return out
 
 
 def sam_select(masks, iou, obj_logit, multimask, delta, thresh):
     _need_cuda(masks, iou, obj_logit)
     sel = torch.empty(4, dtype=torch.int32, device=masks.device)
-    _check(lib().vv_sam_select(_p(masks), masks.shape[-1], masks.shape[0], _p(iou), _p(obj_logit), int(bool(multimask)), _f(delta), _f(thresh), _p(sel),
+    _check(lib().vv_sam_select(_p(masks), masks.shape[-1], masks.shape[0], _p(iou), _p(obj_logit), int(bool(multimask)), delta, thresh, _p(sel),
                                _stream()), "vv_sam_select")
     return sel
 
@@ -974,28 +1053,28 @@ def sam_select(masks, iou, obj_logit, multimask, delta, thresh):
 def sam_pick(masks, sel, no_obj_score):
     _need_cuda(masks, sel)
     out = torch.empty(masks.shape[-1], dtype=torch.float32, device=masks.device)
-    _check(lib().vv_sam_pick(_p(masks), masks.shape[-1], _p(sel), _f(no_obj_score), _p(out), _stream()), "vv_sam_pick")
+    _check(lib().vv_sam_pick(_p(masks), masks.shape[-1], _p(sel), no_obj_score, _p(out), _stream()), "vv_sam_pick")
     return out
 
 
 def select_f32(a, b, flag):
     _need_cuda(a, b, flag)
     out = torch.empty_like(a)
-    _check(lib().vv_select_f32(_p(a), _p(b), _p(flag), C.c_int64(a.numel()), _p(out), _stream()), "vv_select_f32")
+    _check(lib().vv_select_f32(_p(a), _p(b), _p(flag), a.numel(), _p(out), _stream()), "vv_select_f32")
     return out
 
 
 def add_rowvec_unless(x, vec, score):
     """x[m] += vec unless score[0] > 0 (score: fp32 on the device)."""
     _need_cuda(x, vec, score)
-    _check(lib().vv_add_rowvec_unless(_p(x), _p(vec), _p(score), C.c_int64(x.shape[0]), x.shape[1], _stream()), "vv_add_rowvec_unless")
+    _check(lib().vv_add_rowvec_unless(_p(x), _p(vec), _p(score), x.shape[0], x.shape[1], _stream()), "vv_add_rowvec_unless")
     return x
 
 
 def clamp_f32(x, lo, hi):
     _need_cuda(x)
     out = torch.empty_like(x)
-    _check(lib().vv_clamp_f32(_p(x), C.c_int64(x.numel()), _f(lo), _f(hi), _p(out), _stream()), "vv_clamp_f32")
+    _check(lib().vv_clamp_f32(_p(x), x.numel(), lo, hi, _p(out), _stream()), "vv_clamp_f32")
     return out
 
 
@@ -1044,6 +1123,6 @@ def sam2_maskdown(dtype, logits, lo, S, binarize, scale, bias, l1, l2, eps=1e-6)
     _need_cuda(logits, *l1, *l2)
     mid = torch.empty(((S // 2) ** 2, 8), dtype=h16(dtype), device=logits.device)
     out = torch.empty(((S // 4) ** 2, 16), dtype=h16(dtype), device=logits.device)
-    _check(lib().vv_sam2_maskdown(_p(logits), lo, S, int(bool(binarize)), _f(scale), _f(bias), _p(l1[0]), _p(l1[1]), _p(l1[2]), _p(l1[3]), _p(l2[0]), _p(l2[1]),
-                                  _p(l2[2]), _p(l2[3]), _f(eps), _p(mid), _p(out), dtype, _stream()), "vv_sam2_maskdown")
+    _check(lib().vv_sam2_maskdown(_p(logits), lo, S, int(bool(binarize)), scale, bias, _p(l1[0]), _p(l1[1]), _p(l1[2]), _p(l1[3]), _p(l2[0]), _p(l2[1]),
+                                  _p(l2[2]), _p(l2[3]), eps, _p(mid), _p(out), dtype, _stream()), "vv_sam2_maskdown")
     return out

@@ -93,7 +93,7 @@ class Conv:
         self.b = ctx.dev(bias_t.float()) if bias_t is not None else None
 
     def __call__(self, x0, F, H, W, x1=None, stride=1, Hv=None, Wv=None, Hout=None, Wout=None, pad=None, bias=True, rowvec=None,
-                 res0=None, res1=None, out_dtype=torch.float32, out=None, scale=1.0, bias_override=None, gn_partials=False):
+                 res0=None, res1=None, out_dtype=torch.float32, out=None, scale=1.0, bias_override=None, gn_partials=None):
         k = self.k
         pad = (k // 2) if pad is None else pad
         Hv = H if Hv is None else Hv
@@ -274,6 +274,7 @@ class ResBlock:
 
     def wants_gn_partials(self, H, W, res1, out_dtype):
         """conv2 can emit the GroupNorm partials of the block's output: the shapes the dispatcher sends to the 128 x 160 halo-tile kernel"""
+        # (restates the dispatcher's halo cover rule without its 256-row rule: asking vv_conv_gemm_route instead changes which kernel short C = 640 clips run -- a fix to measure)
         cover = ((H + 7) // 8) * 8 * ((W + 15) // 16) * 16
         return (ResBlock.GN_FROM_EPILOGUE and self.cout in (320, 640) and not self.conv2.precise and res1 is None and out_dtype == torch.float32
                 and cover * 100 <= H * W * 115 and H * W >= 2048)
@@ -289,16 +290,17 @@ class ResBlock:
             else:
                 b1 = self.temb_bias(silu_temb).view(-1)
         mid16 = self.h16_mid and ResBlock.H16_MID
-        h, _, _ = self.conv1(h, F, H, W, bias_override=b1, out_dtype=self.ctx.h16 if mid16 else torch.float32,
-                             gn_partials=not mid16 and not self.conv1.precise and self.wants_gn_partials(H, W, None, torch.float32))      # conv1's output feeds norm2 only
-        h = self.norm2(h, F, HW, silu=True, partials=getattr(h, "vv_gn", None))
+        ask1 = not mid16 and not self.conv1.precise and self.wants_gn_partials(H, W, None, torch.float32)      # conv1's output feeds norm2 only
+        gn1 = hip.GNPartials(F, H, W, self.cout, x0.device) if ask1 else None
+        h, _, _ = self.conv1(h, F, H, W, bias_override=b1, out_dtype=self.ctx.h16 if mid16 else torch.float32, gn_partials=gn1)
+        h = self.norm2(h, F, HW, silu=True, partials=gn1)
         if self.short is not None:
             xs, _, _ = self.short(x0, F, H, W, x1=x1)
         else:
             xs = x0
-        out, _, _ = self.conv2(h, F, H, W, res0=xs, res1=res1, out_dtype=out_dtype,
-                               gn_partials=bool(want_gn) and self.wants_gn_partials(H, W, res1, out_dtype))
-        return out
+        gn = hip.GNPartials(F, H, W, self.cout, x0.device) if want_gn and self.wants_gn_partials(H, W, res1, out_dtype) else None
+        out, _, _ = self.conv2(h, F, H, W, res0=xs, res1=res1, out_dtype=out_dtype, gn_partials=gn)
+        return (out, gn) if want_gn else out      # want_gn: (out, hip.GNPartials of out for the GroupNorm that reads it next, or None where conv2 cannot write them)
 
 
 class SelfAttention:
@@ -441,16 +443,15 @@ class SpatialTransformer:
             fs, fp = packing.pack_chain_front_stream(f, ctx.h16)
             self.front = (ctx.dev(fs), ctx.dev(fp))
 
-    def __call__(self, x, F, H, W, out_dtype=torch.float32):
-        HW = H * W
-        gn = getattr(x, "vv_gn", None)      # partial sums of x left by the convolution that produced it (ResBlock.GN_FROM_EPILOGUE)
+    def __call__(self, x, F, H, W, out_dtype=torch.float32, partials=None):
+        HW = H * W      # partials: the partial sums of x left by the convolution that produced it (ResBlock(want_gn=True)), or None
         if self.fused is not None and SpatialTransformer.FUSED and x.dtype == torch.float32:
             t, qkv = hip.spatial_chain_front_c320(self.ctx.dt, x, self.norm.g, self.norm.b, self.norm.groups, self.norm.eps, self.front[0], self.front[1],
-                                                  F=F, HW=HW, partials=gn)
+                                                  F=F, HW=HW, partials=partials)
             hm = SpatialTransformer.HEAD_MAJOR_O
             o = self.attn1.core_qkv(qkv, F, HW, head_major_out=hm)
             return hip.spatial_chain_c320(self.ctx.dt, o, t, x, self.fused[0], self.fused[1], out_dtype=out_dtype, o_hw=HW if hm else 0)
-        h = self.norm(x, F, HW, partials=gn)
+        h = self.norm(x, F, HW, partials=partials)
         t, _, _ = self.proj_in(h, F, H, W)
         t = self.attn1.spatial(self.n1(t), t, F, HW)
         t = self.attn2(self.n2(t), t, F, HW)
@@ -464,7 +465,6 @@ class MotionModule:
     (csrc/vv_motion.hip: one wave per pixel, trunk and activations in registers, weights streamed through an LDS ring); every other
     shape runs the layer-by-layer path below."""
     FUSED = True          # class-level switch (tests / A-B runs compare both paths on the same weights)
-    HEAD_MAJOR_O = True   # the self-attention core's output in head-major layout between the two fused kernels (round 6: whole 80-byte records per store)
 
     def __init__(self, ctx, name, C, cfg, pe_table):
         self.ctx = ctx

@@ -138,9 +138,10 @@ class _Backbone:
         L = len(self.cfg.block_out)
         for i, layers in enumerate(self.down):
             for (r, a, m) in layers:
-                x = r(x, F, H, W, silu_temb=st, want_gn=a is not None)      # (its output feeds the spatial transformer's GroupNorm)
+                x = r(x, F, H, W, silu_temb=st, want_gn=a is not None)      # (its output feeds the spatial transformer's GroupNorm: (x, partials of x))
                 if a is not None:
-                    x = a(x, F, H, W)
+                    x, gn = x
+                    x = a(x, F, H, W, partials=gn)
                 if m is not None:
                     x = m(x, F, H, W)
                 if hid is not None:
@@ -154,8 +155,8 @@ class _Backbone:
         return x, skips, (H, W)
 
     def run_mid(self, x, F, H, W, st):
-        x = self.mid_r0(x, F, H, W, silu_temb=st, want_gn=True)
-        x = self.mid_a(x, F, H, W)
+        x, gn = self.mid_r0(x, F, H, W, silu_temb=st, want_gn=True)
+        x = self.mid_a(x, F, H, W, partials=gn)
         if self.mid_m is not None:
             x = self.mid_m(x, F, H, W)
         return self.mid_r1(x, F, H, W, silu_temb=st)
@@ -177,7 +178,8 @@ class _Backbone:
                 od = self.ctx.h16 if (li == len(layers) - 1 and i < L - 1 and not (last == "a" and au is not None)) else f32
                 x = r(x, F, H, W, x1=s, silu_temb=st, res1=au if last == "r" else None, out_dtype=od if last == "r" else f32, want_gn=a is not None)
                 if a is not None:
-                    x = a(x, F, H, W, out_dtype=od if last == "a" else f32)
+                    x, gn = x
+                    x = a(x, F, H, W, out_dtype=od if last == "a" else f32, partials=gn)
                     if last == "a" and au is not None:
                         hip.add_inplace(self.ctx.dt, x, au)
                 if m is not None:
