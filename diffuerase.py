@@ -3,7 +3,9 @@
 with the hot path running on hand-written gfx950 HIP kernels (videovanish_amd/) instead of torch/cuDNN.
 
 Extra keyword-only knobs (old callers are unaffected): num_inference_steps, scheduler, chunk, overlap, dtype, seed,
-compat_reference_early_return, roi (mask-region inference: videovanish_amd/roi.py; also configure(roi=...) and $VV_ROI).  There is no CPU fallback: without the HIP extension / a GPU this raises.
+compat_reference_early_return, roi (mask-region inference: videovanish_amd/roi.py; also configure(roi=...) and $VV_ROI), spans / cuts (mask-span
+inference: only the runs of masked frames are processed, and nothing crosses a hard cut: videovanish_amd/spans.py; also configure(spans=...) and
+$VV_SPANS).  There is no CPU fallback: without the HIP extension / a GPU this raises.
 """
 import argparse
 import os
@@ -13,6 +15,8 @@ import torch
 
 from videovanish_amd import hip
 from videovanish_amd import roi as roi_plan
+from videovanish_amd import spans as span_plan
+from videovanish_amd import spans_hip
 from videovanish_amd.config import RunConfig
 from videovanish_amd.diffueraser import DiffuEraser
 from videovanish_amd.propainter import Propainter, get_device
@@ -29,9 +33,10 @@ _prior_stages = {}      # configure(prior=...): optional learned stages of the P
 _weights = None         # configure(weights=...) / $VV_WEIGHTS_DIR: a local model store (videovanish_amd/modelhub.py) or a CheckpointWeights
 _loaded = None          # (CheckpointWeights, prior stages) resolved from _weights, cached until configure() is called again
 _roi = None             # configure(roi=...): mask-region inference for calls that do not pass roi= themselves
+_spans = None           # configure(spans=...): mask-span inference for calls that do not pass spans= themselves
 
 
-def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None):
+def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -46,8 +51,10 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     COMPLETE ProPainter prior (recurrent flow completion + inpainting generator) when no prior is handed over -- instead of this build's defaults
     (independent 32 / 8 chunks that shard over GPUs; RAFT + propagation only).  `run` / `prior` given explicitly still win field by field.
     roi = None / "static" / "follow" / "static-regions" / "follow-regions" / a roi.RoiConfig: mask-region inference for calls that do not pass
-    roi= (run_infill_on_frames)."""
-    global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi
+    roi= (run_infill_on_frames).
+    spans = None / "masked" / "cuts" / "masked-cuts" / a spans.SpanConfig: mask-span inference for calls that do not pass spans=."""
+    global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi, _spans
+    span_plan.as_config(spans)
     roi_plan.as_config(roi)                 # validated now, kept as given: configure(roi="off") means the full frame whatever $VV_ROI says
     if reference_defaults:
         import dataclasses
@@ -57,6 +64,7 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     _prior_stages, propainter = dict(prior or {}), None
     _weights, _loaded = weights, None
     _roi = roi
+    _spans = spans
 
 
 def _resolve_weights(ckpt):
@@ -89,23 +97,134 @@ def roi_config(roi=None):
     return roi_plan.as_config(os.environ.get("VV_ROI"))
 
 
+def spans_config(spans=None, cuts=None):
+    """The mask-span setting a call runs with: its own spans= argument, else configure(spans=...), else $VV_SPANS (masked | cuts | masked-cuts | off).
+    None = the full clip.  spans="off" (or False) asks for the full clip whatever configure() or the environment say.  cuts (frame indices) replaces
+    the setting's own cuts: explicit cuts always override the detector; given alone it means "every frame, split at these cuts"."""
+    if spans is not None:
+        cfg = span_plan.as_config(spans)
+    elif _spans is not None:
+        cfg = span_plan.as_config(_spans)
+    else:
+        cfg = span_plan.as_config(os.environ.get("VV_SPANS"))
+    if cuts is not None and not (spans is not None and cfg is None):        # spans="off" wins over cuts=
+        import dataclasses
+        cfg = span_plan.SpanConfig("all", cuts=cuts) if cfg is None else dataclasses.replace(cfg, cuts=cuts)
+    return cfg
+
+
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
-                         *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None):
+                         *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
     "static-regions" / "follow-regions" (RoiConfig.max_regions > 1): one window per separate masked region (roi.plan_regions), each region an
-    ordinary clip call on its crop, the windows pasted one after another; with one region left this is the single-window path."""
+    ordinary clip call on its crop, the windows pasted one after another; with one region left this is the single-window path.
+    spans (mask-span inference, opt-in): "masked" / "cuts" / "masked-cuts" / a videovanish_amd.spans.SpanConfig splits the clip in time
+    (spans.plan_spans): at hard cuts (cuts=[...] frame indices, or found on the device: "cuts", "masked-cuts"), and in "masked" mode into spans
+    around the runs of masked frames only.  Each span is this call on frames[a:b] (its own roi windows, chunks and lanes); frames outside every
+    span are returned as the original arrays, also with keep_unmasked_original=False.  A clip without a mask pixel returns its input and loads
+    no model; one span that is the whole clip is the plain call."""
     rcfg = roi_config(roi)
+    scfg = spans_config(spans, cuts)
     if rcfg is not None and compat_reference_early_return:
         raise ValueError("roi= (mask-region inference) cannot be combined with compat_reference_early_return=True")
-    H0, W0 = frames_rgb[0].shape[:2]
+    if scfg is not None and compat_reference_early_return:
+        raise ValueError("spans= (mask-span inference) cannot be combined with compat_reference_early_return=True")
 
     if prog is not None: prog(5, "dilating frames")
     dev = get_device()
     m = torch.from_numpy(np.stack([mm if mm.ndim == 3 else mm[..., None] for mm in mask_frames])).to(dev)
     dil_t = hip.mask_collapse_dilate(m.contiguous(), mask_dilation_iter)       # reference :27-31
+
+    def body(frames, dil, prior, p):
+        return _clip_body(frames, dil, prior, rcfg, ckpt, dev, max_img_size, keep_unmasked_original, feather_px, p, num_inference_steps, scheduler,
+                          compat_reference_early_return)
+
+    if scfg is None:
+        return body(frames_rgb, dil_t, propainer_frames, prog)
+    plan = _span_plan(frames_rgb, dil_t, scfg)
+    return _run_spans(frames_rgb, dil_t, propainer_frames, plan, body, prog, load=lambda: _load_model(dev, ckpt))
+
+
+def _span_plan(frames_rgb, dil_t, scfg):
+    """spans.plan_spans for the dilated masks: the per-frame masked flags from mask_bbox (an empty box = unmasked) and, with cuts="auto", the cuts
+    spans.find_cuts reads from the device's pair statistics (every frame crosses to the device once for that)."""
+    bb = hip.mask_bbox(dil_t).cpu().numpy()
+    masked = (bb[:, 2] > bb[:, 0]) & (bb[:, 3] > bb[:, 1])
+    cuts = None
+    if scfg.cuts == "auto":
+        cuts = []
+        if len(frames_rgb) >= 2:
+            H0, W0 = frames_rgb[0].shape[:2]
+            sad, n, hist = spans_hip.frame_pair_stats(frames_rgb, dil_t)
+            cuts = span_plan.find_cuts(sad, n, hist, scfg, npix=H0 * W0)
+    return span_plan.plan_spans(masked, cuts, scfg)
+
+
+def _span_progress(prog, k, n, state):
+    """Progress of span k's sub-call: 10 (weights: loaded once, before the first span) is dropped, 20 and 50 are passed on the first time
+    they are seen, values in (20, 50) and (50, 90] go through _region_progress's mapping into span k's share with a "span k/n:" prefix.  A later
+    span's prior runs after an earlier span's model, so a value below the largest one shown so far is raised to it: the caller sees each of
+    5 / 10 / 20 / 50 / 90 once and non-decreasing values."""
+    if prog is None:
+        return None
+
+    def show(v, s):
+        if v < state["last"]:
+            v = state["last"]
+            if v in (10, 20, 50):       # nothing but a milestone shown so far: it is not shown twice
+                return
+        state["last"] = v
+        prog(v, s)
+
+    stages = {20: _region_progress(show, k, n, 20, 50, "span"), 50: _region_progress(show, k, n, 50, 90, "span")}
+
+    def cb(v, s=""):
+        if v in stages:
+            if v not in state["seen"]:
+                state["seen"].add(v)
+                show(v, s or "running")
+        elif 20 < v < 50:
+            stages[20](v, s)
+        elif 50 < v <= 90:              # the sub-call's own 90 closes span k's share; the call's 90 comes after the last span
+            stages[50](v, s)
+    return cb
+
+
+def _run_spans(frames_rgb, dil, propainer_frames, plan, body, prog, load=None):
+    """The temporal plan carried out: body(frames[a:b], dil[a:b], prior[a:b] | None, progress) per span (a, b), in order; every other frame is the
+    original array.  One span that is the whole clip: body on the clip as it is, with the caller's progress.  No span: the original frames, no
+    model (load is not called), the milestones 5 / 10 / 20 / 50 / 90 still delivered.  body is the per-clip computation (run_infill_on_frames
+    passes _clip_body); load loads the weights once, before the first span."""
+    T = len(frames_rgb)
+    if list(plan) == [(0, T)]:
+        return body(frames_rgb, dil, propainer_frames, prog)
+    out = list(frames_rgb)
+    if not plan:
+        if prog is not None:
+            for v, s in ((10, "no masked frame: no weights to load"), (20, "no masked frame: no prior"), (50, "no masked frame: no inference"),
+                         (90, "returning the original frames")):
+                prog(v, s)
+        return out
+    if prog is not None: prog(10, "loading weights")
+    if load is not None:
+        load()
+    state = {"last": 10, "seen": set()}
+    for k, (a, b) in enumerate(plan):
+        out[a:b] = body(frames_rgb[a:b], dil[a:b], None if propainer_frames is None else propainer_frames[a:b], _span_progress(prog, k, len(plan), state))
+    if prog is not None:
+        if 50 not in state["seen"]: prog(50, "running DiffuEraser")
+        prog(90, "resizing and merging finished frames")
+    return out
+
+
+def _clip_body(frames_rgb, dil_t, propainer_frames, rcfg, ckpt, dev, max_img_size, keep_unmasked_original, feather_px, prog, num_inference_steps,
+               scheduler, compat_reference_early_return=False):
+    """One clip after the dilation: roi planning (windows, regions), weights, prior, model, resize and composite.  The whole call without spans=, and
+    each span's call with it."""
+    H0, W0 = frames_rgb[0].shape[:2]
     if rcfg is not None and rcfg.max_regions > 1:
         plans = _region_plans(dil_t, H0, W0, feather_px, rcfg)
         if plans is not None and len(plans) > 1:
@@ -202,15 +321,15 @@ def _region_plans(dil_t, H0, W0, feather_px, cfg):
     return roi_plan.plan_regions(hip.mask_bbox_tiles(dil_t, tile, tiles, K).cpu().numpy(), H0, W0, feather_px, cfg)
 
 
-def _region_progress(prog, k, n, lo, hi):
-    """Progress of region k's sub-call (its own values in [lo, hi]) mapped into region k's share of (lo, hi), never onto lo or hi themselves,
+def _region_progress(prog, k, n, lo, hi, what="region"):
+    """Progress of region (or span: `what`) k's sub-call (its own values in [lo, hi]) mapped into region k's share of (lo, hi), never onto lo or hi themselves,
     so the caller still sees each of 5 / 10 / 20 / 50 / 90 once and non-decreasing values."""
     if prog is None:
         return None
 
     def cb(v, s):
         f = min(max((v - lo) / (hi - lo), 0.0), 1.0)
-        prog(min(max(lo + int((hi - lo) * (k + f) / n), lo + 1), hi - 1), f"region {k + 1}/{n}: {s}" if s else f"region {k + 1}/{n}")
+        prog(min(max(lo + int((hi - lo) * (k + f) / n), lo + 1), hi - 1), f"{what} {k + 1}/{n}: {s}" if s else f"{what} {k + 1}/{n}")
     return cb
 
 
@@ -302,6 +421,11 @@ def main():
                     help="Mask-region inference: run the model only on a window around the masks (static: one window per clip; follow: "
                          "a window that follows the mask; static-regions / follow-regions: one such window per separate masked region).  "
                          "Pixels outside the windows stay the original ones.")
+    ap.add_argument("--spans", choices=span_plan.SPELLINGS, default=None,
+                    help="Mask-span inference: masked = process only the frame runs that have a mask (with some context), the other frames stay "
+                         "the original ones; cuts = process every frame but split the clip at hard cuts found in the video; masked-cuts = both.")
+    ap.add_argument("--cuts", type=span_plan.parse_cuts, default=None, metavar="120,431",
+                    help="Frame indices (relative to --start_frame) where a new shot begins: used instead of the detector.")
     args = ap.parse_args()
 
     assert os.path.isfile(args.color_video), "input video missing"
@@ -316,7 +440,9 @@ def main():
         Hp, Wp = prior_frames[0].shape[:2]
         assert (H0 == Hp and W0 == Wp), "prior and color video are diffrent sizes"
     assert (H0 == Hm and W0 == Wm), "mask and color video are diffrent sizes"
-    kw = {"roi": args.roi} if args.roi is not None else {}      # pass roi= only when asked for: a default call stays the reference's call
+    kw = {"roi": args.roi} if args.roi is not None else {}      # pass roi= / spans= / cuts= only when asked for: a default call stays the reference's call
+    if args.spans is not None: kw["spans"] = args.spans
+    if args.cuts is not None: kw["cuts"] = args.cuts
     out_frames = run_infill_on_frames(frames, mask_frames, propainer_frames=prior_frames, **kw)
     tools.write_video_frames_to_path(out_video, out_frames, fps, H0, W0)
 
