@@ -6,6 +6,9 @@ Extra keyword-only knobs (old callers are unaffected): num_inference_steps, sche
 compat_reference_early_return, roi (mask-region inference: videovanish_amd/roi.py; also configure(roi=...) and $VV_ROI), spans / cuts (mask-span
 inference: only the runs of masked frames are processed, and nothing crosses a hard cut: videovanish_amd/spans.py; also configure(spans=...) and
 $VV_SPANS).  There is no CPU fallback: without the HIP extension / a GPU this raises.
+
+This file is the boundary: the reference's names and module state, the settings, and the stages (weights, prior, model) that read that state.
+What a call does with them -- spans, windows, crop -> prior -> model, resize / paste / composite -- is videovanish_amd/infill.py.
 """
 import argparse
 import os
@@ -13,10 +16,9 @@ import os
 import numpy as np
 import torch
 
-from videovanish_amd import hip
+from videovanish_amd import hip, infill
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
-from videovanish_amd import spans_hip
 from videovanish_amd.config import RunConfig
 from videovanish_amd.diffueraser import DiffuEraser
 from videovanish_amd.propainter import Propainter, get_device
@@ -120,7 +122,7 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
     "static-regions" / "follow-regions" (RoiConfig.max_regions > 1): one window per separate masked region (roi.plan_regions), each region an
-    ordinary clip call on its crop, the windows pasted one after another; with one region left this is the single-window path.
+    ordinary clip call on its crop, the windows pasted one after another; one region left is one window, as with "static" / "follow" (infill.run_clip: one path for 0, 1 and k windows).
     spans (mask-span inference, opt-in): "masked" / "cuts" / "masked-cuts" / a videovanish_amd.spans.SpanConfig splits the clip in time
     (spans.plan_spans): at hard cuts (cuts=[...] frame indices, or found on the device: "cuts", "masked-cuts"), and in "masked" mode into spans
     around the runs of masked frames only.  Each span is this call on frames[a:b] (its own roi windows, chunks and lanes); frames outside every
@@ -138,139 +140,15 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     m = torch.from_numpy(np.stack([mm if mm.ndim == 3 else mm[..., None] for mm in mask_frames])).to(dev)
     dil_t = hip.mask_collapse_dilate(m.contiguous(), mask_dilation_iter)       # reference :27-31
 
+    stages = infill.Stages(lambda: _load_model(dev, ckpt), _load_prior, _run_prior,
+                           lambda f, d, prior, p: _run_model(f, d, prior, max_img_size, p, num_inference_steps, scheduler))
+
     def body(frames, dil, prior, p):
-        return _clip_body(frames, dil, prior, rcfg, ckpt, dev, max_img_size, keep_unmasked_original, feather_px, p, num_inference_steps, scheduler,
-                          compat_reference_early_return)
+        return infill.run_clip(frames, dil, prior, rcfg, stages, p, dev, feather_px, keep_unmasked_original, compat_reference_early_return)
 
     if scfg is None:
         return body(frames_rgb, dil_t, propainer_frames, prog)
-    plan = _span_plan(frames_rgb, dil_t, scfg)
-    return _run_spans(frames_rgb, dil_t, propainer_frames, plan, body, prog, load=lambda: _load_model(dev, ckpt))
-
-
-def _span_plan(frames_rgb, dil_t, scfg):
-    """spans.plan_spans for the dilated masks: the per-frame masked flags from mask_bbox (an empty box = unmasked) and, with cuts="auto", the cuts
-    spans.find_cuts reads from the device's pair statistics (every frame crosses to the device once for that)."""
-    bb = hip.mask_bbox(dil_t).cpu().numpy()
-    masked = (bb[:, 2] > bb[:, 0]) & (bb[:, 3] > bb[:, 1])
-    cuts = None
-    if scfg.cuts == "auto":
-        cuts = []
-        if len(frames_rgb) >= 2:
-            H0, W0 = frames_rgb[0].shape[:2]
-            sad, n, hist = spans_hip.frame_pair_stats(frames_rgb, dil_t)
-            cuts = span_plan.find_cuts(sad, n, hist, scfg, npix=H0 * W0)
-    return span_plan.plan_spans(masked, cuts, scfg)
-
-
-def _span_progress(prog, k, n, state):
-    """Progress of span k's sub-call: 10 (weights: loaded once, before the first span) is dropped, 20 and 50 are passed on the first time
-    they are seen, values in (20, 50) and (50, 90] go through _region_progress's mapping into span k's share with a "span k/n:" prefix.  A later
-    span's prior runs after an earlier span's model, so a value below the largest one shown so far is raised to it: the caller sees each of
-    5 / 10 / 20 / 50 / 90 once and non-decreasing values."""
-    if prog is None:
-        return None
-
-    def show(v, s):
-        if v < state["last"]:
-            v = state["last"]
-            if v in (10, 20, 50):       # nothing but a milestone shown so far: it is not shown twice
-                return
-        state["last"] = v
-        prog(v, s)
-
-    stages = {20: _region_progress(show, k, n, 20, 50, "span"), 50: _region_progress(show, k, n, 50, 90, "span")}
-
-    def cb(v, s=""):
-        if v in stages:
-            if v not in state["seen"]:
-                state["seen"].add(v)
-                show(v, s or "running")
-        elif 20 < v < 50:
-            stages[20](v, s)
-        elif 50 < v <= 90:              # the sub-call's own 90 closes span k's share; the call's 90 comes after the last span
-            stages[50](v, s)
-    return cb
-
-
-def _run_spans(frames_rgb, dil, propainer_frames, plan, body, prog, load=None):
-    """The temporal plan carried out: body(frames[a:b], dil[a:b], prior[a:b] | None, progress) per span (a, b), in order; every other frame is the
-    original array.  One span that is the whole clip: body on the clip as it is, with the caller's progress.  No span: the original frames, no
-    model (load is not called), the milestones 5 / 10 / 20 / 50 / 90 still delivered.  body is the per-clip computation (run_infill_on_frames
-    passes _clip_body); load loads the weights once, before the first span."""
-    T = len(frames_rgb)
-    if list(plan) == [(0, T)]:
-        return body(frames_rgb, dil, propainer_frames, prog)
-    out = list(frames_rgb)
-    if not plan:
-        if prog is not None:
-            for v, s in ((10, "no masked frame: no weights to load"), (20, "no masked frame: no prior"), (50, "no masked frame: no inference"),
-                         (90, "returning the original frames")):
-                prog(v, s)
-        return out
-    if prog is not None: prog(10, "loading weights")
-    if load is not None:
-        load()
-    state = {"last": 10, "seen": set()}
-    for k, (a, b) in enumerate(plan):
-        out[a:b] = body(frames_rgb[a:b], dil[a:b], None if propainer_frames is None else propainer_frames[a:b], _span_progress(prog, k, len(plan), state))
-    if prog is not None:
-        if 50 not in state["seen"]: prog(50, "running DiffuEraser")
-        prog(90, "resizing and merging finished frames")
-    return out
-
-
-def _clip_body(frames_rgb, dil_t, propainer_frames, rcfg, ckpt, dev, max_img_size, keep_unmasked_original, feather_px, prog, num_inference_steps,
-               scheduler, compat_reference_early_return=False):
-    """One clip after the dilation: roi planning (windows, regions), weights, prior, model, resize and composite.  The whole call without spans=, and
-    each span's call with it."""
-    H0, W0 = frames_rgb[0].shape[:2]
-    if rcfg is not None and rcfg.max_regions > 1:
-        plans = _region_plans(dil_t, H0, W0, feather_px, rcfg)
-        if plans is not None and len(plans) > 1:
-            return _run_regions(frames_rgb, dil_t, plans, propainer_frames, ckpt, dev, max_img_size, feather_px if keep_unmasked_original else -1.0,
-                                prog, num_inference_steps, scheduler)
-        plan = None if plans is None else plans[0]          # one region (or none): the single-window (or full-frame) path below
-    else:
-        plan = roi_plan.plan_roi(hip.mask_bbox(dil_t).cpu().numpy(), H0, W0, feather_px, rcfg) if rcfg is not None else None
-    dilated_mask_frames = list(dil_t.cpu().numpy())
-    full_frames = frames_rgb
-    if plan is not None:      # the model, and the prior when it is computed here, see only the windows
-        frames_rgb, dilated_mask_frames = plan.crop(frames_rgb), plan.crop(dilated_mask_frames)
-        if propainer_frames is not None:
-            propainer_frames = plan.crop(propainer_frames)
-
-    if prog is not None: prog(10, "loading weights")
-    _load_model(dev, ckpt)
-
-    if propainer_frames is None:                                                # reference :47-57
-        _load_prior()
-        if prog is not None: prog(20, "running propainter prior")
-        propainer_frames = _run_prior(frames_rgb, dilated_mask_frames, prog)
-
-    if prog is not None: prog(50, "running DiffuEraser")
-    inpainted_frames = _run_model(frames_rgb, dilated_mask_frames, propainer_frames, max_img_size, prog, num_inference_steps, scheduler)
-
-    if prog is not None: prog(90, "resizing and merging finished frames")
-    if plan is not None:
-        return _paste_windows(inpainted_frames, full_frames, dil_t, plan, feather_px if keep_unmasked_original else -1.0, dev)
-    # reference :69-112.  The reference returns from inside its loop (:114) so only frame 0 is post-processed; the
-    # evident intent (all frames) is the default here, compat_reference_early_return=True reproduces the quirk.
-    n_post = 1 if compat_reference_early_return else len(inpainted_frames)
-    idx = [i for i in range(n_post) if inpainted_frames[i] is not None]        # multi-GPU "rank0" gather: other ranks hold only their own frames
-    if not idx:
-        return inpainted_frames
-    Hm, Wm = inpainted_frames[idx[0]].shape[:2]
-    out = torch.from_numpy(np.stack([inpainted_frames[i] for i in idx])).to(dev)
-    if (Hm, Wm) != (H0, W0):
-        out = hip.resize_u8(out.contiguous(), H0, W0, mode="bilinear")          # cv2.resize(f,(W0,H0)), :73
-    if keep_unmasked_original:
-        orig = torch.from_numpy(np.stack([frames_rgb[i] for i in idx])).to(dev)
-        out = hip.feather_composite(out.contiguous(), orig.contiguous(), dil_t[idx].contiguous(), float(feather_px))   # :77-112
-    out = out.cpu().numpy()
-    for j, i in enumerate(idx):
-        inpainted_frames[i] = out[j]
-    return inpainted_frames
+    return infill.run_spans(frames_rgb, dil_t, propainer_frames, infill.span_plan(frames_rgb, dil_t, scfg), body, prog, load=stages.load_model)
 
 
 def _load_model(dev, ckpt):
@@ -304,91 +182,6 @@ def _run_model(frames_rgb, dilated_mask_frames, propainer_frames, max_img_size, 
     guidance_scale = None
     return video_inpainting_sd.forward(frames_rgb, dilated_mask_frames, propainer_frames, max_img_size=max_img_size, mask_dilation_iter=0,
                                        guidance_scale=guidance_scale, progress=prog, num_inference_steps=num_inference_steps, scheduler=scheduler)
-
-
-REGION_TILE = 16        # px: the occupancy grid the regions are labelled on (roi.label_tiles coarsens it for salt-like masks)
-
-
-def _region_plans(dil_t, H0, W0, feather_px, cfg):
-    """roi.plan_regions for the dilated masks: tile occupancy on the device, its components on the host, then one box per (frame, component)
-    from the occupied tiles only (T * K * 16 bytes come back)."""
-    occ = hip.mask_tile_union(dil_t, REGION_TILE).cpu().numpy()
-    labels, K, tile = roi_plan.label_tiles(occ, tile=REGION_TILE)
-    if K == 0:
-        return None
-    ty, tx = np.nonzero(labels >= 0)
-    tiles = torch.from_numpy(np.stack([ty, tx, labels[ty, tx]], axis=1).astype(np.int32)).to(dil_t.device)
-    return roi_plan.plan_regions(hip.mask_bbox_tiles(dil_t, tile, tiles, K).cpu().numpy(), H0, W0, feather_px, cfg)
-
-
-def _region_progress(prog, k, n, lo, hi, what="region"):
-    """Progress of region (or span: `what`) k's sub-call (its own values in [lo, hi]) mapped into region k's share of (lo, hi), never onto lo or hi themselves,
-    so the caller still sees each of 5 / 10 / 20 / 50 / 90 once and non-decreasing values."""
-    if prog is None:
-        return None
-
-    def cb(v, s):
-        f = min(max((v - lo) / (hi - lo), 0.0), 1.0)
-        prog(min(max(lo + int((hi - lo) * (k + f) / n), lo + 1), hi - 1), f"{what} {k + 1}/{n}: {s}" if s else f"{what} {k + 1}/{n}")
-    return cb
-
-
-def _run_regions(frames_rgb, dil_t, plans, propainer_frames, ckpt, dev, max_img_size, feather_px, prog, num_inference_steps, scheduler):
-    """Several pairwise disjoint windows (roi.plan_regions): every region's prior, then every region's model, each an ordinary clip call on
-    that region's crop, one region after another; then the windows are pasted into the originals one after another."""
-    n = len(plans)
-    dil = list(dil_t.cpu().numpy())
-    crops = [(p.crop(frames_rgb), p.crop(dil)) for p in plans]
-    priors = [None if propainer_frames is None else p.crop(propainer_frames) for p in plans]
-    if prog is not None: prog(10, "loading weights")
-    _load_model(dev, ckpt)
-    if propainer_frames is None:
-        _load_prior()
-        if prog is not None: prog(20, "running propainter prior")
-        priors = [_run_prior(f, m, _region_progress(prog, k, n, 20, 50)) for k, (f, m) in enumerate(crops)]
-    if prog is not None: prog(50, "running DiffuEraser")
-    outs = [_run_model(f, m, priors[k], max_img_size, _region_progress(prog, k, n, 50, 90), num_inference_steps, scheduler)
-            for k, (f, m) in enumerate(crops)]
-    if prog is not None: prog(90, "resizing and merging finished frames")
-    return _paste_regions(outs, frames_rgb, dil_t, plans, feather_px, dev)
-
-
-def _paste_regions(outs, frames_rgb, dil_t, plans, feather_px, dev):
-    """Each region's window frames into the originals: roi_paste_composite once per region, the output of region k the original of region
-    k + 1 (two buffers, one upload, one download).  Exact because the windows are disjoint: inside window k the mask holds only region k's
-    pixels and no other region has touched the bytes."""
-    idx = [i for i in range(len(outs[0])) if outs[0][i] is not None]          # multi-GPU "rank0" gather, as in _paste_windows
-    if not idx:
-        return outs[0]
-    bufs = [torch.from_numpy(np.stack([frames_rgb[i] for i in idx])).to(dev).contiguous()]
-    bufs.append(torch.empty_like(bufs[0]))
-    mask = dil_t[idx].contiguous()
-    for k, (plan, o) in enumerate(zip(plans, outs)):
-        h, w = plan.size
-        patch = torch.from_numpy(np.stack([o[i] for i in idx])).to(dev)
-        offs = torch.from_numpy(np.ascontiguousarray(plan.offsets[idx])).to(dev)
-        hip.roi_paste_composite(patch.contiguous(), bufs[k % 2], mask, offs, h, w, float(feather_px), out=bufs[(k + 1) % 2])
-    out = bufs[len(plans) % 2].cpu().numpy()
-    res = list(outs[0])
-    for j, i in enumerate(idx):
-        res[i] = out[j]
-    return res
-
-
-def _paste_windows(inpainted_frames, frames_rgb, dil_t, plan, feather_px, dev):
-    """The model's window frames back into the full-size originals (resize to the window, paste, feathered composite: one kernel)."""
-    idx = [i for i in range(len(inpainted_frames)) if inpainted_frames[i] is not None]       # multi-GPU "rank0" gather, as below
-    if not idx:
-        return inpainted_frames
-    h, w = plan.size
-    patch = torch.from_numpy(np.stack([inpainted_frames[i] for i in idx])).to(dev)
-    orig = torch.from_numpy(np.stack([frames_rgb[i] for i in idx])).to(dev)
-    offs = torch.from_numpy(np.ascontiguousarray(plan.offsets[idx])).to(dev)
-    out = hip.roi_paste_composite(patch.contiguous(), orig.contiguous(), dil_t[idx].contiguous(), offs, h, w, float(feather_px)).cpu().numpy()
-    res = list(inpainted_frames)
-    for j, i in enumerate(idx):
-        res[i] = out[j]
-    return res
 
 
 def _frame_io():

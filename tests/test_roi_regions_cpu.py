@@ -1,6 +1,7 @@
 """Mask-region inference with one window per separate masked region, host side: the tile labelling (roi.label_tiles) against a brute-force flood
-fill, the region planner (roi.plan_regions) as properties over random sets of box tracks, worked examples, the new spellings of the setting, and
-the argument checks of the two new entry points.  No GPU."""
+fill, the region planner (roi.plan_regions) as properties over random sets of box tracks, worked examples, the new spellings of the setting, the
+one crop -> prior -> model sequence (infill.run_windows) for no, one and two windows with fake stages, and the argument checks of the two new
+entry points.  No GPU."""
 import ctypes
 import math
 import os
@@ -265,6 +266,103 @@ def test_cli_accepts_region_spellings(monkeypatch, tmp_path):
         monkeypatch.setattr(sys, "argv", base + ["--roi", bad])
         with pytest.raises(SystemExit):
             diffuerase.main()
+
+
+# ---- orchestration ------------------------------------------------------------------------------------------------------------------
+def _fake_clip(T=5, H=16, W=24):
+    """Frames, masks and a prior whose every pixel tells frame and position, so a crop at a wrong offset or of a wrong frame differs."""
+    y, x = np.mgrid[:H, :W]
+    frames = [((7 * t + 3 * y + x)[..., None] + np.arange(3)).astype(np.uint8) for t in range(T)]
+    for t, f in enumerate(frames):
+        f[0, 0, 0] = t
+    dil = [(100 + 5 * t + y + 2 * x).astype(np.uint8) for t in range(T)]
+    prior = [255 - f for f in frames]
+    return frames, dil, prior
+
+
+def _fake_stages(log, prior_vals, model_vals):
+    """An infill.Stages that records every call with its arguments and reports prior_vals / model_vals as progress (every other message empty)."""
+    from videovanish_amd import infill
+
+    def run(kind, vals, add):
+        def stage(f, m, *rest):
+            log.append((kind, f, m) + rest)
+            if rest[-1] is not None:
+                for i, v in enumerate(vals):
+                    rest[-1](v, f"{kind} {i}" if i % 2 == 0 else "")
+            return [x + add for x in f]
+        return stage
+    return infill.Stages(lambda: log.append(("load_model",)), lambda: log.append(("load_prior",)), run("prior", prior_vals, 1), run("model", model_vals, 2))
+
+
+def _same_frames(a, b):
+    return len(a) == len(b) and all(x.shape == y.shape and (x == y).all() for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("with_prior", [True, False])
+def test_run_windows_full_frame_and_one_window(with_prior):
+    from videovanish_amd import infill
+    frames, dil, prior = _fake_clip()
+    T = len(frames)
+    plan = roi.RoiPlan("follow", (8, 16), np.array([[2 + t, 3 + t] for t in range(T)], np.int32), np.zeros((T, 2)))
+    for plans in ([], [plan]):
+        log, progs = [], []
+        prog = lambda v, s: progs.append((v, s))
+        outs = infill.run_windows(frames, dil, prior if with_prior else None, plans, _fake_stages(log, (25, 35), (60, 75)), prog)
+        assert [c[0] for c in log] == (["load_model", "model"] if with_prior else ["load_model", "load_prior", "prior", "model"])
+        calls = [c for c in log if len(c) > 1]
+        model = calls[-1]
+        if plans:                                                       # one window: the crops the plan makes
+            for c in calls:
+                assert _same_frames(c[1], plan.crop(frames)) and _same_frames(c[2], plan.crop(dil))
+            if with_prior:
+                assert _same_frames(model[3], plan.crop(prior))
+        else:                                                           # the full frame: the very same list objects, no copy
+            for c in calls:
+                assert c[1] is frames and c[2] is dil
+            if with_prior:
+                assert model[3] is prior
+        if not with_prior:                                              # the prior stage's result goes to the model as it is
+            assert calls[0][0] == "prior" and _same_frames(model[3], [x + 1 for x in calls[0][1]]) and model[1] is calls[0][1] and model[2] is calls[0][2]
+        assert all(c[-1] is prog for c in calls)                        # the caller's progress itself: no prefix, no remapping
+        assert len(outs) == 1 and _same_frames(outs[0], [x + 2 for x in model[1]])
+        want = [(10, "loading weights")] + ([] if with_prior else [(20, "running propainter prior"), (25, "prior 0"), (35, "")])
+        assert progs == want + [(50, "running DiffuEraser"), (60, "model 0"), (75, ""), (90, "resizing and merging finished frames")]
+        outs = infill.run_windows(frames, dil, prior if with_prior else None, plans, _fake_stages([], (25,), (60,)), None)      # no callback: nothing is called
+        assert len(outs) == 1 and len(outs[0]) == T
+
+
+@pytest.mark.parametrize("with_prior", [True, False])
+def test_run_windows_two_windows(with_prior):
+    from videovanish_amd import infill
+    frames, dil, prior = _fake_clip()
+    T = len(frames)
+    plans = [roi.RoiPlan("static", (8, 8), np.tile(np.array([[0, 16]], np.int32), (T, 1)), np.zeros((T, 2))),
+             roi.RoiPlan("follow", (8, 16), np.array([[8, t] for t in range(T)], np.int32), np.zeros((T, 2)))]
+    log, progs = [], []
+    # the sub-calls report their own end points too (20 / 50, 50 / 90): these must not land on a milestone
+    outs = infill.run_windows(frames, dil, prior if with_prior else None, plans, _fake_stages(log, (20, 30, 40, 50), (50, 60, 80, 90)),
+                              lambda v, s: progs.append((v, s)))
+    kinds = [c[0] for c in log]
+    assert kinds == (["load_model"] if with_prior else ["load_model", "load_prior", "prior", "prior"]) + ["model", "model"]    # every prior before any model
+    for kind in ("model",) if with_prior else ("prior", "model"):
+        for p, c in zip(plans, [c for c in log if c[0] == kind]):
+            assert c[1][0].shape == p.size + (3,) and _same_frames(c[1], p.crop(frames)) and _same_frames(c[2], p.crop(dil))
+            if kind == "model":
+                assert _same_frames(c[3], p.crop(prior) if with_prior else [x + 1 for x in p.crop(frames)])
+    assert len(outs) == 2 and all(_same_frames(o, [x + 2 for x in p.crop(frames)]) for o, p in zip(outs, plans))
+    vals = [v for v, _ in progs]
+    assert [v for v in vals if v in (5, 10, 20, 50, 90)] == ([10, 50, 90] if with_prior else [10, 20, 50, 90])      # each once; 5 is run_infill_on_frames'
+    assert vals == sorted(vals) and all(isinstance(s, str) and s for _, s in progs)
+    assert progs[0] == (10, "loading weights") and vals[-1] == 90 and (with_prior or vals[1] == 20)
+    for a, b, kind in ((50, 90, "model"),) if with_prior else ((20, 50, "prior"), (50, 90, "model")):
+        got = progs[vals.index(a) + 1:vals.index(b)]
+        assert len(got) == 8 and all(a < v < b for v, _ in got)                               # four per region, strictly inside
+        for k in (0, 1):                                                                      # the prefix, also where the sub-call's message is empty
+            assert [s for _, s in got[4 * k:4 * k + 4]] == [f"region {k + 1}/2: {kind} 0", f"region {k + 1}/2", f"region {k + 1}/2: {kind} 2", f"region {k + 1}/2"]
+    # no progress callback: nothing is called
+    outs = infill.run_windows(frames, dil, None, plans, _fake_stages([], (30,), (60,)), None)
+    assert len(outs) == 2 and _same_frames(outs[1], [x + 2 for x in plans[1].crop(frames)])
 
 
 # ---- entry points -------------------------------------------------------------------------------------------------------------------

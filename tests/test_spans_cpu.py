@@ -195,7 +195,7 @@ def _fake(T=14):
 
 
 def test_run_spans_slices_reassembles_and_reports():
-    import diffuerase
+    from videovanish_amd import infill
     frames, dil, prior = _fake()
     for with_prior in (True, False):
         calls, loads, progs = [], [], []
@@ -211,8 +211,8 @@ def test_run_spans_slices_reassembles_and_reports():
             prog(90, "resizing and merging finished frames")
             return [x + 50 for x in f]
 
-        out = diffuerase._run_spans(frames, dil, prior if with_prior else None, [(1, 4), (8, 12)], body, lambda v, s: progs.append((v, s)),
-                                    load=lambda: loads.append(1))
+        out = infill.run_spans(frames, dil, prior if with_prior else None, [(1, 4), (8, 12)], body, lambda v, s: progs.append((v, s)),
+                               load=lambda: loads.append(1))
         want_p = (lambda a, b: list(range(200 + a, 200 + b))) if with_prior else (lambda a, b: None)
         assert calls == [([1, 2, 3], [101, 102, 103], want_p(1, 4)), ([8, 9, 10, 11], [108, 109, 110, 111], want_p(8, 12))]      # slices, in order
         assert loads == [1]
@@ -229,12 +229,12 @@ def test_run_spans_slices_reassembles_and_reports():
         if not with_prior:
             assert any(20 < v < 50 and s.startswith("span 1/2: ") for v, s in progs)
     # no progress callback: nothing is called
-    out = diffuerase._run_spans(frames, dil, None, [(0, 2)], lambda f, d, p, prog: [x + 1 for x in f] if prog is None else None, None)
+    out = infill.run_spans(frames, dil, None, [(0, 2)], lambda f, d, p, prog: [x + 1 for x in f] if prog is None else None, None)
     assert int(out[1][0, 0, 0]) == 2 and out[2] is frames[2]
 
 
 def test_run_spans_special_paths():
-    import diffuerase
+    from videovanish_amd import infill
     frames, dil, prior = _fake()
     loads, progs = [], []
     prog = lambda v, s: progs.append((v, s))
@@ -245,15 +245,15 @@ def test_run_spans_special_paths():
         got["args"] = (f, d, p, pr)
         return "whole"
 
-    assert diffuerase._run_spans(frames, dil, prior, [(0, 14)], body, prog, load=lambda: loads.append(1)) == "whole"
+    assert infill.run_spans(frames, dil, prior, [(0, 14)], body, prog, load=lambda: loads.append(1)) == "whole"
     assert got["args"][0] is frames and got["args"][1] is dil and got["args"][2] is prior and got["args"][3] is prog and not loads and not progs
     # an empty plan: the inputs, no body, no load, the milestones still delivered
     def never(*a):
         raise AssertionError("the body must not run")
-    out = diffuerase._run_spans(frames, dil, prior, [], never, prog, load=lambda: loads.append(1))
+    out = infill.run_spans(frames, dil, prior, [], never, prog, load=lambda: loads.append(1))
     assert len(out) == 14 and all(o is f for o, f in zip(out, frames)) and not loads
     assert [v for v, _ in progs] == [10, 20, 50, 90] and all(s for _, s in progs)
-    assert diffuerase._run_spans(frames, dil, None, [], never, None) == frames
+    assert infill.run_spans(frames, dil, None, [], never, None) == frames
 
 
 # ---- configuration, CLI, binding ----------------------------------------------------------------------------------------------------------

@@ -61,7 +61,7 @@ def main():
 
     import torch
     import diffuerase
-    from videovanish_amd import hip, roi
+    from videovanish_amd import hip, infill, roi
     from videovanish_amd.config import RunConfig
     from videovanish_amd.pipeline import model_size
     if not torch.cuda.is_available():
@@ -91,7 +91,7 @@ def main():
                 if cfg is None:
                     plans = None
                 elif cfg.max_regions > 1:
-                    plans = diffuerase._region_plans(dil, H, W, 3, cfg)
+                    plans = infill.region_plans(dil, H, W, 3, cfg)
                 else:
                     plans = roi.plan_roi(hip.mask_bbox(dil).cpu().numpy(), H, W, 3, cfg)
                     plans = None if plans is None else [plans]

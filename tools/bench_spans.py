@@ -59,7 +59,7 @@ def main():
 
     import torch
     import diffuerase
-    from videovanish_amd import hip, spans, spans_hip
+    from videovanish_amd import hip, infill, spans, spans_hip
     from videovanish_amd.config import RunConfig
     from videovanish_amd.pipeline import chunk_plan
     if not torch.cuda.is_available():
@@ -85,7 +85,7 @@ def main():
         for mode in args.modes.split(","):
             s = None if mode == "none" else mode
             cfg = spans.as_config(s)
-            plan = [(0, T)] if cfg is None else diffuerase._span_plan(frames, dil, cfg)      # the plan the call makes, on the side
+            plan = [(0, T)] if cfg is None else infill.span_plan(frames, dil, cfg)      # the plan the call makes, on the side
             processed = sum(b - a for a, b in plan)
             chunks = [len(chunk_plan(b - a, run.chunk, run.overlap)) for a, b in plan]
             diffuerase.run_infill_on_frames(frames, masks, spans=s or "off", **warm_kw)

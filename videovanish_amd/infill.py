@@ -1,0 +1,204 @@
+"""The orchestration of one diffuerase.run_infill_on_frames call after the dilation: the temporal plan (span_plan, run_spans), and for each
+clip the windows (region_plans, run_clip), ONE crop -> prior -> model sequence (run_windows) and ONE closing step (finish).  The full frame is
+no window, roi= "static" / "follow" one, the "-regions" spellings several.  The stages (weights, prior, model) come from the caller as a Stages
+record; nothing here is module state.  Rules and reasons: DESIGN.md §10, §11."""
+from typing import Callable, NamedTuple
+
+import numpy as np
+import torch
+
+from . import hip, spans_hip
+from . import roi as roi_plan
+from . import spans as span_planner
+
+
+class Stages(NamedTuple):
+    load_model: Callable    # ()
+    load_prior: Callable    # (), after load_model
+    run_prior: Callable     # (frames, masks, progress) -> prior frames
+    run_model: Callable     # (frames, masks, prior frames, progress) -> inpainted frames (None: a frame another rank holds)
+
+
+REGION_TILE = 16        # px: the occupancy grid the regions are labelled on (roi.label_tiles coarsens it for salt-like masks)
+
+
+def _share(prog, what, k, n, lo, hi):
+    """Progress of region / span (`what`) k's sub-call (its own values in [lo, hi]) mapped into k's share of (lo, hi), never onto lo or hi themselves,
+    so the caller still sees each of 5 / 10 / 20 / 50 / 90 once and non-decreasing values."""
+    if prog is None:
+        return None
+
+    def cb(v, s):
+        f = min(max((v - lo) / (hi - lo), 0.0), 1.0)
+        prog(min(max(lo + int((hi - lo) * (k + f) / n), lo + 1), hi - 1), f"{what} {k + 1}/{n}: {s}" if s else f"{what} {k + 1}/{n}")
+    return cb
+
+
+# ---- spans: the clip in time --------------------------------------------------------------------------------------------------------------
+def span_plan(frames_rgb, dil_t, scfg):
+    """spans.plan_spans for the dilated masks: the per-frame masked flags from mask_bbox (an empty box = unmasked) and, with cuts="auto", the cuts
+    spans.find_cuts reads from the device's pair statistics (every frame crosses to the device once for that)."""
+    bb = hip.mask_bbox(dil_t).cpu().numpy()
+    masked = (bb[:, 2] > bb[:, 0]) & (bb[:, 3] > bb[:, 1])
+    cuts = None
+    if scfg.cuts == "auto":
+        cuts = []
+        if len(frames_rgb) >= 2:
+            H0, W0 = frames_rgb[0].shape[:2]
+            sad, n, hist = spans_hip.frame_pair_stats(frames_rgb, dil_t)
+            cuts = span_planner.find_cuts(sad, n, hist, scfg, npix=H0 * W0)
+    return span_planner.plan_spans(masked, cuts, scfg)
+
+
+def _span_progress(prog, n):
+    """(span, seen): span(k) is the progress callback of span k's sub-call, seen the milestones passed on so far.  10 (weights: loaded once, before
+    the first span) is dropped, 20 and 50 are passed on the first time they are seen, values in (20, 50) and (50, 90] go through _share into span
+    k's share with a "span k/n:" prefix.  A later span's prior runs after an earlier span's model, so a value below the largest one shown so far
+    is raised to it: the caller sees each of 5 / 10 / 20 / 50 / 90 once and non-decreasing values."""
+    seen, last = set(), [10]
+
+    def show(v, s):
+        if v < last[0]:
+            v = last[0]
+            if v in (10, 20, 50):       # nothing but a milestone shown so far: it is not shown twice
+                return
+        last[0] = v
+        prog(v, s)
+
+    def span(k):
+        if prog is None:
+            return None
+        stages = {20: _share(show, "span", k, n, 20, 50), 50: _share(show, "span", k, n, 50, 90)}
+
+        def cb(v, s=""):
+            if v in stages:
+                if v not in seen:
+                    seen.add(v)
+                    show(v, s or "running")
+            elif 20 < v < 50:
+                stages[20](v, s)
+            elif 50 < v <= 90:              # the sub-call's own 90 closes span k's share; the call's 90 comes after the last span
+                stages[50](v, s)
+        return cb
+    return span, seen
+
+
+def run_spans(frames_rgb, dil, propainer_frames, plan, body, prog, load=None):
+    """The temporal plan carried out: body(frames[a:b], dil[a:b], prior[a:b] | None, progress) per span (a, b), in order; every other frame is the
+    original array.  One span that is the whole clip: body on the clip as it is, with the caller's progress.  No span: the original frames, no
+    model (load is not called), the milestones 5 / 10 / 20 / 50 / 90 still delivered.  body is the per-clip computation (run_infill_on_frames
+    passes run_clip); load loads the weights once, before the first span."""
+    T = len(frames_rgb)
+    if list(plan) == [(0, T)]:
+        return body(frames_rgb, dil, propainer_frames, prog)
+    out = list(frames_rgb)
+    if not plan:
+        if prog is not None:
+            for v, s in ((10, "no masked frame: no weights to load"), (20, "no masked frame: no prior"), (50, "no masked frame: no inference"),
+                         (90, "returning the original frames")):
+                prog(v, s)
+        return out
+    if prog is not None: prog(10, "loading weights")
+    if load is not None:
+        load()
+    span, seen = _span_progress(prog, len(plan))
+    for k, (a, b) in enumerate(plan):
+        out[a:b] = body(frames_rgb[a:b], dil[a:b], None if propainer_frames is None else propainer_frames[a:b], span(k))
+    if prog is not None:
+        if 50 not in seen: prog(50, "running DiffuEraser")
+        prog(90, "resizing and merging finished frames")
+    return out
+
+
+# ---- windows: one clip in space -----------------------------------------------------------------------------------------------------------
+def region_plans(dil_t, H0, W0, feather_px, cfg):
+    """roi.plan_regions for the dilated masks: tile occupancy on the device, its components on the host, then one box per (frame, component)
+    from the occupied tiles only (T * K * 16 bytes come back)."""
+    occ = hip.mask_tile_union(dil_t, REGION_TILE).cpu().numpy()
+    labels, K, tile = roi_plan.label_tiles(occ, tile=REGION_TILE)
+    if K == 0:
+        return None
+    ty, tx = np.nonzero(labels >= 0)
+    tiles = torch.from_numpy(np.stack([ty, tx, labels[ty, tx]], axis=1).astype(np.int32)).to(dil_t.device)
+    return roi_plan.plan_regions(hip.mask_bbox_tiles(dil_t, tile, tiles, K).cpu().numpy(), H0, W0, feather_px, cfg)
+
+
+def run_clip(frames_rgb, dil_t, propainer_frames, rcfg, stages, prog, dev, feather_px=3, keep_unmasked_original=True,
+             compat_reference_early_return=False):
+    """One clip after the dilation: the windows rcfg asks for (none without it, or where the planner falls back to the full frame), run_windows,
+    finish.  The whole call without spans=, and each span's call with it."""
+    H0, W0 = frames_rgb[0].shape[:2]
+    if rcfg is None:
+        plans = []
+    elif rcfg.max_regions > 1:
+        plans = region_plans(dil_t, H0, W0, feather_px, rcfg) or []
+    else:
+        plan = roi_plan.plan_roi(hip.mask_bbox(dil_t).cpu().numpy(), H0, W0, feather_px, rcfg)
+        plans = [] if plan is None else [plan]
+    outs = run_windows(frames_rgb, list(dil_t.cpu().numpy()), propainer_frames, plans, stages, prog)
+    return finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return)
+
+
+def run_windows(frames_rgb, dil, propainer_frames, plans, stages, prog):
+    """Weights, then every window's prior (unless one is supplied), then every window's model, each an ordinary clip call on that window's crop of
+    the frames, the masks and a supplied prior; one list of output frames per window.  No plan: one "window" that is the full frame, the lists
+    as they are.  Up to one window the stages get the caller's progress as it is; several windows each get their share of (20, 50) and (50, 90)
+    with a "region k/n:" prefix."""
+    n = len(plans)
+    crops = [p.crop for p in plans] or [lambda x: x]
+    share = (lambda k, lo, hi: _share(prog, "region", k, n, lo, hi)) if n > 1 else (lambda k, lo, hi: prog)
+    clips = [(crop(frames_rgb), crop(dil)) for crop in crops]      # the model, and the prior when it is computed here, see only the windows
+    priors = [None if propainer_frames is None else crop(propainer_frames) for crop in crops]
+    if prog is not None: prog(10, "loading weights")
+    stages.load_model()
+    if propainer_frames is None:                                                # reference :47-57
+        stages.load_prior()
+        if prog is not None: prog(20, "running propainter prior")
+        priors = [stages.run_prior(f, m, share(k, 20, 50)) for k, (f, m) in enumerate(clips)]
+    if prog is not None: prog(50, "running DiffuEraser")
+    outs = [stages.run_model(f, m, priors[k], share(k, 50, 90)) for k, (f, m) in enumerate(clips)]
+    if prog is not None: prog(90, "resizing and merging finished frames")
+    return outs
+
+
+def _on_device(res, n, dev, fn):
+    """res[i] = fn(idx, up)[j] for idx = the frames among res[:n] that this rank holds (multi-GPU "rank0" gather: the other ranks' frames are None
+    and stay None); up(frames) = frames[idx] stacked on the device; fn returns a [len(idx),H,W,3] device tensor, downloaded once.  Returns res."""
+    idx = [i for i in range(n) if res[i] is not None]
+    if idx:
+        out = fn(idx, lambda frames: torch.from_numpy(np.stack([frames[i] for i in idx])).to(dev)).cpu().numpy()
+        for j, i in enumerate(idx):
+            res[i] = out[j]
+    return res
+
+
+def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return=False):
+    """The model's frames into frames of the original size.  No plan (reference :69-112): resize when the model ran at another size, feathered
+    composite with the originals when keep_unmasked_original, in place in outs[0].  The reference returns from inside its loop (:114) so only
+    frame 0 is post-processed; the evident intent (all frames) is the default here, compat_reference_early_return=True reproduces the quirk.
+    With plans: each window's frames into the originals (resize to the window, paste, feathered composite: roi_paste_composite once per window,
+    the output of window k the original of window k + 1: two buffers, one upload, one download).  Exact because the windows are disjoint: inside
+    window k the mask holds only region k's pixels and no other window has touched the bytes.  keep_unmasked_original=False: the plain paste."""
+    H0, W0 = frames_rgb[0].shape[:2]
+
+    def full_frame(idx, up):
+        out = up(outs[0])
+        if tuple(out.shape[1:3]) != (H0, W0):
+            out = hip.resize_u8(out.contiguous(), H0, W0, mode="bilinear")          # cv2.resize(f,(W0,H0)), :73
+        if keep_unmasked_original:
+            out = hip.feather_composite(out.contiguous(), up(frames_rgb).contiguous(), dil_t[idx].contiguous(), float(feather_px))   # :77-112
+        return out
+
+    def windows(idx, up):
+        bufs = [up(frames_rgb).contiguous()]
+        bufs.append(torch.empty_like(bufs[0]))
+        mask = dil_t[idx].contiguous()
+        for k, (plan, o) in enumerate(zip(plans, outs)):
+            offs = torch.from_numpy(np.ascontiguousarray(plan.offsets[idx])).to(dev)
+            hip.roi_paste_composite(up(o).contiguous(), bufs[k % 2], mask, offs, *plan.size, float(feather_px if keep_unmasked_original else -1.0),
+                                    out=bufs[(k + 1) % 2])
+        return bufs[len(plans) % 2]
+
+    if not plans:
+        return _on_device(outs[0], 1 if compat_reference_early_return else len(outs[0]), dev, full_frame)
+    return _on_device(list(outs[0]), len(outs[0]), dev, windows)
