@@ -231,7 +231,9 @@ int vv_spatial_chain_c320(const vv_chain_params* host_p, int dtype, void* stream
  * proj_in); qkv = Wqkv LN1(t), stored head-major [frame][q|k|v][head][token][40] (what vv_attention reads with q_rs = 40, q_hs = HW * 40; the
  * query rows of the packed weights carry scale * log2 e: q_prescaled = 1).  gn_affine: [F][2][320] per-frame scale / shift from
  * vv_groupnorm_stats + vv_gn_affine_frames.  stream / params: packing.pack_chain_front_stream (100 slabs; 960 floats).
- * Replaces vv_groupnorm's apply pass, two vv_conv_gemm and one vv_layernorm of nn.SpatialTransformer. */
+ * Replaces vv_groupnorm's apply pass, two vv_conv_gemm and one vv_layernorm of nn.SpatialTransformer.
+ * One kernel, the row-split pair form (chain_front_rs_c320_kernel).  HW >= 9: the affine rows of the frames a 128-token block touches (at most
+ * 127 / HW + 2) are staged in a 16-frame LDS buffer; smaller frames are refused with VV_E_UNSUPPORTED (hip.CHAIN_FRONT_MIN_HW). */
 typedef struct {
     const float* x; const float* gn_affine;
     float* t_out; void* qkv;

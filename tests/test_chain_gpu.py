@@ -14,7 +14,9 @@ def _rel(a, b):
 
 
 @pytest.mark.parametrize("dname,tol", [("fp16", 3e-3), ("bf16", 2.5e-2)])
-@pytest.mark.parametrize("Fr,H,W", [(2, 8, 8), (3, 6, 7), (1, 16, 24)])          # 128 tokens (one full block), 126 (ragged), 384
+# 128 tokens (one full block), 126 (ragged), 384; 72 frames of 3 x 3 = the smallest frame the fused front accepts (hip.CHAIN_FRONT_MIN_HW): block 4 starts at
+# row 512 = 9 * 56 + 8 and touches 16 frames, exactly the front's affine staging buffer, M = 648 ragged; 16 frames of 2 x 4: below it, the block runs layer by layer
+@pytest.mark.parametrize("Fr,H,W", [(2, 8, 8), (3, 6, 7), (1, 16, 24), (72, 3, 3), (16, 2, 4)])
 def test_fused_spatial_chain_vs_oracle_and_unfused(gpu, dname, tol, Fr, H, W):
     from oracle import model_ref as M
     from videovanish_amd import nn as vnn
@@ -47,6 +49,23 @@ def test_fused_spatial_chain_vs_oracle_and_unfused(gpu, dname, tol, Fr, H, W):
     assert e_f <= tol and e_f <= 2.0 * e_p + 1e-4
     out16 = mod(xin, Fr, H, W, out_dtype=ctx.h16)
     assert out16.dtype == ctx.h16 and _rel(back(out16), fused) <= (2e-3 if dname == "fp16" else 1.6e-2)
+
+
+def test_fused_front_refuses_frames_it_cannot_stage(gpu):
+    """The front stages the GroupNorm affine rows of every frame a 128-token block touches (at most 127 / HW + 2) in a 16-frame buffer: HW <= 8 is refused
+    by name before the kernel is launched, HW = 9 (16 frames in block 4 of 72 x 9 tokens) is accepted."""
+    from videovanish_amd import hip, nn as vnn
+    cfg = UNetConfig()
+    assert hip.CHAIN_FRONT_MIN_HW == 9
+    g = torch.Generator().manual_seed(7)
+    ctx = vnn.Ctx("cuda:0", "fp16", 0)
+    mod = vnn.SpatialTransformer(ctx, "unet.down_blocks.0.attentions.0", 320, cfg, ctx.dev(torch.randn(77, 768, generator=g), ctx.h16))
+    front = lambda Fr, HW: hip.spatial_chain_front_c320(ctx.dt, torch.randn(Fr * HW, 320, generator=g).to(gpu), mod.norm.g, mod.norm.b, mod.norm.groups,
+                                                        mod.norm.eps, mod.front[0], mod.front[1], F=Fr, HW=HW)
+    with pytest.raises(RuntimeError, match="HW >= 9"):
+        front(16, 8)
+    t, qkv = front(72, 9)
+    assert t.shape == (648, 320) and qkv.shape == (72, 3, 8, 9, 40) and torch.isfinite(t).all() and torch.isfinite(qkv.float()).all()
 
 
 def test_fused_chain_kernels_are_run_to_run_deterministic(gpu):

@@ -9,44 +9,14 @@
 // A block = 128 tokens shares the weight stream: 462 pre-swizzled [64 x 64] h16 slabs (packing.pack_chain_stream) through the 10-slot LDS ring by LDS-DMA;
 // a pair of waves owns 32 consecutive tokens end to end (chain_rs_c320_kernel below).
 // Fragment conventions, PERM32 and the ring protocol: vv_motion.hip.
-#include <type_traits>
-#include "vv_common.h"
+#include "vv_chain_rs.h"
 
 namespace {
 
 constexpr int CC = 320, CH = 8, CD = 40, NKEY = 77;      // CD: head dim
-constexpr int NSLOT = 10, AHEAD = 6, SLAB = 8192;
 // fp32 parameter block (floats): offsets
 constexpr int Q_BO1 = 0, Q_LN2G = 320, Q_LN2B = 640, Q_BO2 = 960, Q_LN3G = 1280, Q_LN3B = 1600, Q_B1 = 1920, Q_B2 = 4480, Q_BOUT = 4800, Q_TOTAL = 5120;
 constexpr int N_SLABS = 25 + CH * (5 + 2 + 2 + 5) + 20 * 15 + 25;      // 462
-
-__device__ __forceinline__ void glds16_asm(const void* gptr, void* lds_wave_base) {
-    typedef void __attribute__((address_space(3))) * lp_t;
-    const unsigned dst = (unsigned)(size_t)(lp_t)lds_wave_base;
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gptr), "s"(dst) : "memory");
-}
-
-// two GELUs at once on packed fp32 math (exact erf GELU through Abramowitz-Stegun 7.1.26; see vv_motion.hip)
-__device__ __forceinline__ vv_f32x2 gelu2(vv_f32x2 x) {
-    const vv_f32x2 ax = {fabsf(x.x), fabsf(x.y)};
-    const vv_f32x2 z = ax * 0.70710678118654752f;
-    const vv_f32x2 d = __builtin_elementwise_fma(z, (vv_f32x2){0.3275911f, 0.3275911f}, (vv_f32x2){1.0f, 1.0f});
-    const vv_f32x2 t = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-    vv_f32x2 q = __builtin_elementwise_fma(t, (vv_f32x2){1.061405429f, 1.061405429f}, (vv_f32x2){-1.453152027f, -1.453152027f});
-    q = __builtin_elementwise_fma(q, t, (vv_f32x2){1.421413741f, 1.421413741f});
-    q = __builtin_elementwise_fma(q, t, (vv_f32x2){-0.284496736f, -0.284496736f});
-    q = __builtin_elementwise_fma(q, t, (vv_f32x2){0.254829592f, 0.254829592f});
-    q = q * t;
-    const vv_f32x2 ez = z * z * -1.4426950408889634f;
-    const vv_f32x2 e = {__builtin_amdgcn_exp2f(ez.x), __builtin_amdgcn_exp2f(ez.y)};
-    const vv_f32x2 erfc = q * e;
-    return __builtin_elementwise_fma(ax * 0.5f, (vv_f32x2){1.0f, 1.0f} - erfc, x * 0.5f);
-}
-// The fused kernels evaluate this A&S form.  gelu_poly2 (vv_common.h: packed fp32 polynomial, no v_rcp / v_exp -- the GEMM kernels' GEGLU epilogue since
-// round 6, +4.5..6.6 % there) was measured here too: the motion module LOSES 3 % (3.04 -> 3.13 ms), the chain tail is unchanged -- these kernels
-// run one or two waves per SIMD beside the matrix pipe, the transcendental unit is otherwise idle and the polynomial's 14 extra packed FMAs are not (profiles/r6_gelu_ab.txt)
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // ROW-SPLIT form of the tail (round 5), the only one built.  What the counters said about the token-split forms it replaced (4 waves x 32 tokens,
@@ -64,14 +34,12 @@ __device__ __forceinline__ vv_f32x2 gelu2(vv_f32x2 x) {
 // Cross-attention (77 text keys): per head the q projection, S^T, softmax and V^T P^T run on ONE token tile per wave (tile hf: the 16-token form, 9 of a
 // head's 14 slabs), the head's O goes through LDS and its output projection is row-split again; stream order per head pair: q K V^T | q K V^T | Wo | Wo.
 // Synchronisation: explicit steps (LDS-DMA issue of the slabs about to be consumed + counted vmcnt + one barrier) in front of every slab pair of a group.
-constexpr int RS_NS = 10, RS_AH = 6, RS_XBUF = 40960;
-#define VV_WAIT6 asm volatile("s_waitcnt vmcnt(6)" ::: "memory")
 
 template <typename T>
 __global__ __launch_bounds__(512, 2) void chain_rs_c320_kernel(const vv_chain_params p) {
-    __shared__ __attribute__((aligned(1024))) unsigned char ring[RS_NS * SLAB];
+    __shared__ __attribute__((aligned(1024))) unsigned char ring[RS_NS * RS_SLAB];
     __shared__ __attribute__((aligned(16))) unsigned char xbuf[RS_XBUF];
-    __shared__ __attribute__((aligned(16))) float sbuf[8 * 2 * 64 * 2];
+    __shared__ __attribute__((aligned(16))) float sbuf[2048];
     __shared__ __attribute__((aligned(16))) float prm[Q_TOTAL];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -84,92 +52,25 @@ __global__ __launch_bounds__(512, 2) void chain_rs_c320_kernel(const vv_chain_pa
     // ---- weight stream: every wave copies 1 KB of every slab
     const unsigned char* sbase = (const unsigned char*)p.stream + wave * 1024 + lane * 16;
     int issued = 0, islot = 0, cslot = 0;
-    auto issue = [&]() {
-        glds16_asm(sbase + (int64_t)issued * SLAB, ring + islot * SLAB + wave * 1024);
-        ++issued;
-        islot = islot + 1 == RS_NS ? 0 : islot + 1;
-    };
-    using BODY = std::false_type; using TAIL = std::true_type;
-    using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>; using I4 = std::integral_constant<int, 4>;
-    // one synchronisation step in front of NI slabs: issue NI more, wait until all but the newest RS_AH have landed (this wave's share), meet.
-    // XCH: the step also publishes LDS writes of this wave (an exchange): they have to be complete before the barrier.
-    auto sync = [&](auto ni_tag, auto tail_tag, auto xch_tag) {
-        constexpr int NI = decltype(ni_tag)::value;
-        if constexpr (decltype(tail_tag)::value) {
-            if (issued + NI <= N_SLABS) {
-#pragma unroll
-                for (int i = 0; i < NI; ++i) issue();
-                VV_WAIT6;
-            } else {
-                while (issued < N_SLABS) issue();
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NI; ++i) issue();
-            VV_WAIT6;
-        }
-        if constexpr (decltype(xch_tag)::value) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    };
-    using NOX = std::false_type; using XCH = std::true_type;
-    auto slab = [&]() -> const unsigned char* {
-        const unsigned char* s = ring + cslot * SLAB;
-        cslot = cslot + 1 == RS_NS ? 0 : cslot + 1;
-        return s;
-    };
-    auto meet = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); };      // exchange-only barrier (no slab)
+    auto issue = [&]() { rs_issue(sbase, ring, wave, issued, islot); };
+    auto sync = [&](auto ni, auto tail, auto xch) { rs_sync<N_SLABS, decltype(ni)::value, decltype(tail)::value, decltype(xch)::value>(issue, issued); };
+    auto slab = [&]() -> const unsigned char* { return rs_slab(ring, cslot); };
 
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-    auto frag = [&](const f32x4& lo, const f32x4& hi_) -> uint4 {
-        return make_uint4(pack2<T>(lo[0], lo[1]), pack2<T>(lo[2], lo[3]), pack2<T>(hi_[0], hi_[1]), pack2<T>(hi_[2], hi_[3]));
-    };
-    auto sel = [&](const uint4& a_, const uint4& b_) -> uint4 { return hi ? b_ : a_; };      // wave-uniform select
+    auto frag = [](const f32x4& lo, const f32x4& hi_) -> uint4 { return rs_frag<T>(lo, hi_); };
+    auto sel = [&](const uint4& a_, const uint4& b_) -> uint4 { return rs_sel(hi, a_, b_); };
 
     // ---- row-split slab groups: this wave's two row tiles (2 hf, 2 hf + 1) of N [64 x 64] slabs
-    struct WF2 { uint4 w[2][2]; };      // [kk][rt]
     const int rs_off = hf * 4096 + li * 128, sw = li & 7;
-    auto load_rs = [&](const unsigned char* s, WF2& f) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const int off = ((kk * 4 + lg) ^ sw) << 4;
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt) f.w[kk][rt] = *(const uint4*)(s + rs_off + rt * 2048 + off);
-        }
+    auto next_rs = [&](WF2& f) { rs_load(slab(), rs_off, lg, sw, f); };
+    auto group_rs = [&](auto n, auto pre, auto&& acc_of, auto&& x0_of, auto&& x1_of, auto tail) {
+        rs_group<T, decltype(n)::value, decltype(pre)::value>(sync, next_rs, acc_of, x0_of, x1_of, tail);
     };
-    auto fma_rs = [&](const WF2& f, f32x4* acc /* [2][2] = [rt][tt] */, const uint4 (&x0)[2], const uint4 (&x1)[2]) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt) acc[rt * 2 + tt] = T::mfma(f.w[kk][rt], kk ? x1[tt] : x0[tt], acc[rt * 2 + tt]);
-    };
-    // N slabs, a step in front of every pair (PRE: the caller has already made the first one)
-    auto group_rs = [&](auto n_tag, auto pre_tag, auto&& acc_of, auto&& x0_of, auto&& x1_of, auto tail) {
-        constexpr int N = decltype(n_tag)::value;
-        WF2 f[2];
-        if constexpr (!decltype(pre_tag)::value) { if constexpr (N >= 2) sync(I2{}, tail, NOX{}); else sync(I1{}, tail, NOX{}); }
-        load_rs(slab(), f[0]);
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            if (i + 1 < N) {
-                if (((i + 1) & 1) == 0) { if (i + 2 < N) sync(I2{}, tail, NOX{}); else sync(I1{}, tail, NOX{}); }
-                load_rs(slab(), f[(i + 1) & 1]);
-            }
-            fma_rs(f[i & 1], acc_of(i), x0_of(i), x1_of(i));
-            if (i + 1 < N) __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-        }
-    };
-    using N5 = std::integral_constant<int, 5>; using N10 = std::integral_constant<int, 10>; using N25 = std::integral_constant<int, 25>;
-    using NOPRE = std::false_type; using PRE = std::true_type;
 
     // ---- state: trunk t[2 rb + rt][tt] (own channels), activations a0[kt][tt] / a1[kt][tt] = k steps 2 kt / 2 kt + 1 of the full row
     f32x4 t[10][2];
     uint4 a0[5][2], a1[5][2];
-    auto chan = [&](const int j) -> int { return 64 * (j >> 1) + 32 * hf + 16 * (j & 1) + 4 * lg; };      // first of the 4 channels of t[j][.][0..3]
+    auto chan = [&](const int j) -> int { return rs_chan(j, hf, lg); };
     {
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
@@ -217,63 +118,10 @@ __global__ __launch_bounds__(512, 2) void chain_rs_c320_kernel(const vv_chain_pa
                  [&](int i) -> const uint4 (&)[2] { return a1[i % 5]; }, tail);
     };
     // own[rb][tt] = h16(LN(t) g + b) of this wave's channels = k step 2 rb + hf of the row; statistics merged with the partner's
-    auto layer_norm = [&](const int goff, const int boff, uint4 (&own)[5][2]) {
-        float mloc[2], m2loc[2];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            float s = 0.f;
-#pragma unroll
-            for (int j = 0; j < 10; ++j) s += (t[j][tt][0] + t[j][tt][1]) + (t[j][tt][2] + t[j][tt][3]);
-            s += __shfl_xor(s, 16); s += __shfl_xor(s, 32);
-            mloc[tt] = s * (1.0f / 160);
-            float q = 0.f;
-#pragma unroll
-            for (int j = 0; j < 10; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { const float d = t[j][tt][r] - mloc[tt]; q += d * d; }
-            q += __shfl_xor(q, 16); q += __shfl_xor(q, 32);
-            m2loc[tt] = q;
-        }
-        *(float4*)(sbuf + (wave * 64 + lane) * 4) = make_float4(mloc[0], m2loc[0], mloc[1], m2loc[1]);
-        meet();
-        const float4 o4 = *(const float4*)(sbuf + (pw * 64 + lane) * 4);
-        const float om[2] = {o4.x, o4.z}, oq[2] = {o4.y, o4.w};
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            const float mean = 0.5f * (mloc[tt] + om[tt]), dm = mloc[tt] - om[tt];
-            const float rstd = rsqrtf((m2loc[tt] + oq[tt] + 80.0f * dm * dm) * (1.0f / CC) + 1e-5f);
-#pragma unroll
-            for (int rb = 0; rb < 5; ++rb) {
-                f32x4 y[2];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int j = 2 * rb + h, c = chan(j);
-                    const float4 g = *(const float4*)(prm + goff + c), b = *(const float4*)(prm + boff + c);
-                    y[h][0] = (t[j][tt][0] - mean) * rstd * g.x + b.x; y[h][1] = (t[j][tt][1] - mean) * rstd * g.y + b.y;
-                    y[h][2] = (t[j][tt][2] - mean) * rstd * g.z + b.z; y[h][3] = (t[j][tt][3] - mean) * rstd * g.w + b.w;
-                }
-                own[rb][tt] = frag(y[0], y[1]);
-            }
-        }
-    };
+    auto layer_norm = [&](const int goff, const int boff, uint4 (&own)[5][2]) { rs_layer_norm<T>(t, prm, goff, boff, sbuf, wave, pw, lane, hf, lg, own); };
     unsigned char* const xmine = xbuf + wave * 5120 + lane * 16;
     const unsigned char* const xpart = xbuf + pw * 5120 + lane * 16;
-    // full swap of the partners' halves: a0 / a1 <- (own, partner's) for both token tiles (two rounds through the 40 KB buffer)
-    auto swap_full = [&](const uint4 (&own)[5][2]) {
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            if (tt) meet();      // the partner has read round 0
-#pragma unroll
-            for (int rb = 0; rb < 5; ++rb) *(uint4*)(xmine + rb * 1024) = own[rb][tt];
-            meet();
-#pragma unroll
-            for (int rb = 0; rb < 5; ++rb) {
-                const uint4 o = *(const uint4*)(xpart + rb * 1024);
-                a0[rb][tt] = sel(own[rb][tt], o);
-                a1[rb][tt] = sel(o, own[rb][tt]);
-            }
-        }
-    };
+    auto swap_full = [&](const uint4 (&own)[5][2]) { rs_swap_full(own, a0, a1, xmine, xpart, hi); };
 
     // ---- attn1 output projection: t = t_in + Wo1 o + bo1        (stream slabs 0..24)
     dense320(t, BODY{});
@@ -287,14 +135,14 @@ __global__ __launch_bounds__(512, 2) void chain_rs_c320_kernel(const vv_chain_pa
         // the partner needs my k steps of ITS tile (1 - hf); I need its k steps of mine
 #pragma unroll
         for (int rb = 0; rb < 5; ++rb) *(uint4*)(xmine + rb * 1024) = sel(own[rb][1], own[rb][0]);
-        meet();
+        rs_meet();
 #pragma unroll
         for (int rb = 0; rb < 5; ++rb) {
             const uint4 o = *(const uint4*)(xpart + rb * 1024), m = sel(own[rb][0], own[rb][1]);
             x0[rb] = sel(m, o);
             x1[rb] = sel(o, m);
         }
-        meet();      // everybody has read: the buffer is free for the heads' O
+        rs_meet();      // everybody has read: the buffer is free for the heads' O
         const float sc = 0.15811388300841897f * 1.4426950408889634f;      // 40^-1/2 * log2(e)
         struct WF { uint4 w[2][4]; };
         auto load_full = [&](const unsigned char* s, auto rt_tag, auto kk_tag, WF& f) {
@@ -444,7 +292,7 @@ __global__ __launch_bounds__(512, 2) void chain_rs_c320_kernel(const vv_chain_pa
         for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
             for (int rb = 0; rb < 5; ++rb) own[rb][tt] = frag(t[2 * rb][tt], t[2 * rb + 1][tt]);
-        meet();      // the last FF exchange buffer has been read by everybody
+        rs_meet();      // the last FF exchange buffer has been read by everybody
         swap_full(own);
     }
 #pragma unroll
@@ -501,193 +349,15 @@ __global__ __launch_bounds__(512, 2) void chain_rs_c320_kernel(const vv_chain_pa
 constexpr int F_BIN = 0, F_LN1G = 320, F_LN1B = 640, F_TOTAL = 960;
 constexpr int NF_SLABS = 25 + 15 * 5;      // 100
 
-template <typename T>
-__global__ __launch_bounds__(256, 1) void chain_front_c320_kernel(const vv_chain_front_params p) {
-    __shared__ __attribute__((aligned(1024))) unsigned char ring[NSLOT * SLAB];
-    __shared__ __attribute__((aligned(16))) float prm[F_TOTAL];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 15, lg = lane >> 4;
-    const int64_t row0 = (int64_t)blockIdx.x * 128 + wave * 32;
-
-    for (int i = tid * 4; i < F_TOTAL; i += 256 * 4) *(float4*)(prm + i) = *(const float4*)(p.params + i);
-    const unsigned char* sbase = (const unsigned char*)p.stream + (wave * 2) * 1024 + lane * 16;
-    int issued = 0, consumed = 0;
-    auto issue = [&]() {
-        unsigned char* dst = ring + (issued % NSLOT) * SLAB + (wave * 2) * 1024;
-        const unsigned char* src = sbase + (int64_t)issued * SLAB;
-        glds16_asm(src, dst);
-        glds16_asm(src + 1024, dst + 1024);
-        ++issued;
-    };
-    auto next_slab = [&](auto even_tag, auto tail_tag) -> const unsigned char* {
-        if constexpr (decltype(even_tag)::value) {
-            if (!decltype(tail_tag)::value || issued < NF_SLABS) { issue(); issue(); asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); }
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-        const unsigned char* s = ring + (consumed % NSLOT) * SLAB;
-        ++consumed;
-        return s;
-    };
-
-    // ---- x -> GroupNorm apply (scale / shift of the token's own frame) -> activation fragments a[ks][tt]
-    uint4 a[10][2];
-    int64_t rows[2];
-    {
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            int64_t row = row0 + tt * 16 + li;
-            if (row >= p.M) row = p.M - 1;
-            rows[tt] = row;
-            const float* xrow = p.x + row * CC;
-            const float* aff = p.gn_affine + (row / p.HW) * (2 * CC);
-#pragma unroll
-            for (int s = 0; s < 10; ++s) {
-                const int c0 = 32 * s + 4 * lg, c1 = c0 + 16;
-                const float4 x0 = *(const float4*)(xrow + c0), x1 = *(const float4*)(xrow + c1);
-                const float4 a0 = *(const float4*)(aff + c0), b0 = *(const float4*)(aff + CC + c0);
-                const float4 a1 = *(const float4*)(aff + c1), b1 = *(const float4*)(aff + CC + c1);
-                a[s][tt] = make_uint4(pack2<T>(x0.x * a0.x + b0.x, x0.y * a0.y + b0.y), pack2<T>(x0.z * a0.z + b0.z, x0.w * a0.w + b0.w),
-                                      pack2<T>(x1.x * a1.x + b1.x, x1.y * a1.y + b1.y), pack2<T>(x1.z * a1.z + b1.z, x1.w * a1.w + b1.w));
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();       // parameter block visible
-#pragma unroll 1
-        for (int i = 0; i < AHEAD; ++i) issue();
-    }
-
-    struct WF { uint4 w[2][4]; };
-    auto slab_load = [&](const unsigned char* s, WF& f) {
-        const int sw = li & 7;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const int off = ((kk * 4 + lg) ^ sw) << 4;
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt) f.w[kk][rt] = *(const uint4*)(s + (rt * 16 + li) * 128 + off);
-        }
-    };
-    auto slab_fma = [&](const WF& f, f32x4* acc /* [4][2] */, const uint4 (&x0)[2], const uint4 (&x1)[2]) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-                for (int tt = 0; tt < 2; ++tt) acc[rt * 2 + tt] = T::mfma(f.w[kk][rt], kk ? x1[tt] : x0[tt], acc[rt * 2 + tt]);
-    };
-    using EVEN = std::true_type; using ODD = std::false_type; using BODY = std::false_type; using TAIL = std::true_type;
-    // N slabs [64 rows x 64 k] (5 k tiles per 64-row block) starting at stream-index parity P0
-    auto slab_group = [&](auto p0_tag, auto n_tag, auto&& acc_of, auto tail) {
-        constexpr int P0 = decltype(p0_tag)::value, N = decltype(n_tag)::value;
-        WF f[2];
-        slab_load(next_slab(std::bool_constant<P0 == 0>{}, tail), f[0]);
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            if (i + 1 < N) {
-                if (((P0 + i + 1) & 1) == 0) slab_load(next_slab(EVEN{}, tail), f[(i + 1) & 1]);
-                else slab_load(next_slab(ODD{}, tail), f[(i + 1) & 1]);
-            }
-            slab_fma(f[i & 1], acc_of(i), a[2 * (i % 5)], a[2 * (i % 5) + 1]);
-            if (i + 1 < N) __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 16, 0);
-        }
-    };
-    using P0E = std::integral_constant<int, 0>; using P0O = std::integral_constant<int, 1>;
-    using N5 = std::integral_constant<int, 5>; using N25 = std::integral_constant<int, 25>;
-    auto frag = [&](const f32x4& lo, const f32x4& hi) -> uint4 {
-        return make_uint4(pack2<T>(lo[0], lo[1]), pack2<T>(lo[2], lo[3]), pack2<T>(hi[0], hi[1]), pack2<T>(hi[2], hi[3]));
-    };
-
-    // ---- proj_in: t = Win a + bin, stored (the tail kernel and the residual read it back)
-    f32x4 t[20][2];
-#pragma unroll
-    for (int j = 0; j < 20; ++j)
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) t[j][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    slab_group(P0E{}, N25{}, [&](int i) { return &t[(i / 5) * 4][0]; }, BODY{});
-#pragma unroll
-    for (int j = 0; j < 20; ++j) {
-        const float4 b = *(const float4*)(prm + F_BIN + 16 * j + 4 * lg);
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) { t[j][tt][0] += b.x; t[j][tt][1] += b.y; t[j][tt][2] += b.z; t[j][tt][3] += b.w; }
-    }
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-        if (row0 + tt * 16 + li < p.M) {
-            float* trow = p.t_out + rows[tt] * CC;
-#pragma unroll
-            for (int j = 0; j < 20; ++j) *(float4*)(trow + 16 * j + 4 * lg) = make_float4(t[j][tt][0], t[j][tt][1], t[j][tt][2], t[j][tt][3]);
-        }
-    }
-    // ---- LN1 -> a
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < 20; ++j) s += (t[j][tt][0] + t[j][tt][1]) + (t[j][tt][2] + t[j][tt][3]);
-        s += __shfl_xor(s, 16); s += __shfl_xor(s, 32);
-        const float mean = s * (1.0f / CC);
-        float q = 0.f;
-#pragma unroll
-        for (int j = 0; j < 20; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { const float d = t[j][tt][r] - mean; q += d * d; }
-        q += __shfl_xor(q, 16); q += __shfl_xor(q, 32);
-        const float rstd = rsqrtf(q * (1.0f / CC) + 1e-5f);
-#pragma unroll
-        for (int s2 = 0; s2 < 10; ++s2) {
-            f32x4 y[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int j = 2 * s2 + h, c = 16 * j + 4 * lg;
-                const float4 g = *(const float4*)(prm + F_LN1G + c), b = *(const float4*)(prm + F_LN1B + c);
-                y[h][0] = (t[j][tt][0] - mean) * rstd * g.x + b.x; y[h][1] = (t[j][tt][1] - mean) * rstd * g.y + b.y;
-                y[h][2] = (t[j][tt][2] - mean) * rstd * g.z + b.z; y[h][3] = (t[j][tt][3] - mean) * rstd * g.w + b.w;
-            }
-            a[s2][tt] = frag(y[0], y[1]);
-        }
-    }
-    // ---- fused q | k | v projection: 15 blocks of 64 output channels, stored head-major.  Channel c = 64 rb + 16 rt + 4 lg + r is element
-    //      (which = c / 320, head = (c % 320) / 40, d = c % 40) of the token's row; 4 consecutive channels never straddle a head (40 % 4 == 0)
-    unsigned short* qkv = (unsigned short*)p.qkv;
-    int64_t tokbase[2];
-#pragma unroll
-    for (int tt = 0; tt < 2; ++tt) {
-        const int64_t fr = rows[tt] / p.HW, tk = rows[tt] - fr * p.HW;
-        tokbase[tt] = fr * (3 * (int64_t)p.HW * CC) + tk * CD;          // + which * HW * 320 + head * HW * 40 + d
-    }
-    auto qkv_block = [&](const int rb, auto p0_tag, auto tail) {
-        f32x4 acc[4][2];
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt) acc[rt][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        slab_group(p0_tag, N5{}, [&](int) { return &acc[0][0]; }, tail);
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt) {
-            const int c = 64 * rb + 16 * rt + 4 * lg;
-            const int which = c / CC, cc = c - which * CC, head = cc / CD, d = cc - head * CD;
-            const int64_t off = ((int64_t)which * CC + (int64_t)head * CD) * p.HW + d;
-#pragma unroll
-            for (int tt = 0; tt < 2; ++tt)
-                if (row0 + tt * 16 + li < p.M)
-                    *(uint2*)(qkv + tokbase[tt] + off) = make_uint2(pack2<T>(acc[rt][tt][0], acc[rt][tt][1]), pack2<T>(acc[rt][tt][2], acc[rt][tt][3]));
-        }
-    };
-    // (row block rb is 5 slabs and starts at stream index 25 + 5 rb: odd for even rb -> two row blocks per loop iteration)
-#pragma unroll 1
-    for (int rb = 0; rb < 12; rb += 2) { qkv_block(rb, P0O{}, BODY{}); qkv_block(rb + 1, P0E{}, BODY{}); }
-    qkv_block(12, P0O{}, TAIL{}); qkv_block(13, P0E{}, TAIL{}); qkv_block(14, P0O{}, TAIL{});
-}
-
 // ROW-SPLIT pair form of the block front (round 5; design: chain_rs_c320_kernel above).  All 100 slabs are dense layers, so every slab is read as two row
-// tiles per wave (4 fragment reads feed 8 MFMAs) at two waves per SIMD; the partners swap the LayerNorm output once.  Same stream as the 4 x 32 form.
+// tiles per wave (4 fragment reads feed 8 MFMAs) at two waves per SIMD; the partners swap the LayerNorm output once.
+// The ring, the fragment loads, the pair exchange and the channel map are those of the tail (vv_chain_rs.h).  Two pieces stay spelled in place, the MFMA
+// loop of group_rs and LN1: through rs_fma / rs_layer_norm (or any function or lambda) this kernel's register allocation moves (profiles/fused_shared_isa.txt).
 template <typename T>
 __global__ __launch_bounds__(512, 2) void chain_front_rs_c320_kernel(const vv_chain_front_params p) {
-    __shared__ __attribute__((aligned(1024))) unsigned char ring[RS_NS * SLAB];
+    __shared__ __attribute__((aligned(1024))) unsigned char ring[RS_NS * RS_SLAB];
     __shared__ __attribute__((aligned(16))) unsigned char xbuf[RS_XBUF];
-    __shared__ __attribute__((aligned(16))) float sbuf[8 * 64 * 4];
+    __shared__ __attribute__((aligned(16))) float sbuf[2048];
     __shared__ __attribute__((aligned(16))) float prm[F_TOTAL];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -700,63 +370,22 @@ __global__ __launch_bounds__(512, 2) void chain_front_rs_c320_kernel(const vv_ch
     for (int i = tid * 4; i < F_TOTAL; i += 512 * 4) *(float4*)(prm + i) = *(const float4*)(p.params + i);
     const unsigned char* sbase = (const unsigned char*)p.stream + wave * 1024 + lane * 16;
     int issued = 0, islot = 0, cslot = 0;
-    auto issue = [&]() {
-        glds16_asm(sbase + (int64_t)issued * SLAB, ring + islot * SLAB + wave * 1024);
-        ++issued;
-        islot = islot + 1 == RS_NS ? 0 : islot + 1;
-    };
-    using BODY = std::false_type; using TAIL = std::true_type;
-    using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-    auto sync = [&](auto ni_tag, auto tail_tag) {
-        constexpr int NI = decltype(ni_tag)::value;
-        if constexpr (decltype(tail_tag)::value) {
-            if (issued + NI <= NF_SLABS) {
-#pragma unroll
-                for (int i = 0; i < NI; ++i) issue();
-                asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            } else {
-                while (issued < NF_SLABS) issue();
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NI; ++i) issue();
-            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();
-    };
-    auto slab = [&]() -> const unsigned char* {
-        const unsigned char* s = ring + cslot * SLAB;
-        cslot = cslot + 1 == RS_NS ? 0 : cslot + 1;
-        return s;
-    };
-    auto meet = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); };
-    auto frag = [&](const f32x4& lo, const f32x4& hi_) -> uint4 {
-        return make_uint4(pack2<T>(lo[0], lo[1]), pack2<T>(lo[2], lo[3]), pack2<T>(hi_[0], hi_[1]), pack2<T>(hi_[2], hi_[3]));
-    };
-    auto sel = [&](const uint4& a_, const uint4& b_) -> uint4 { return hi ? b_ : a_; };
-    struct WF2 { uint4 w[2][2]; };
+    auto issue = [&]() { rs_issue(sbase, ring, wave, issued, islot); };
+    auto sync = [&](auto ni, auto tail, auto xch) { rs_sync<NF_SLABS, decltype(ni)::value, decltype(tail)::value, decltype(xch)::value>(issue, issued); };
     const int rs_off = hf * 4096 + li * 128, sw = li & 7;
-    auto load_rs = [&](const unsigned char* s, WF2& f) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const int off = ((kk * 4 + lg) ^ sw) << 4;
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt) f.w[kk][rt] = *(const uint4*)(s + rs_off + rt * 2048 + off);
-        }
-    };
+    auto next_rs = [&](WF2& f) { rs_load(rs_slab(ring, cslot), rs_off, lg, sw, f); };
     uint4 a0[5][2], a1[5][2];
-    // N slabs (5 k tiles per 64-row block), a step in front of every pair: acc_of(i)[rt][tt] += own row tiles x the full activation row
+    // N slabs (5 k tiles per 64-row block): acc_of(i)[rt][tt] += own row tiles x the full activation row.  rs_group with its MFMA loop in place (see above)
     auto group_rs = [&](auto n_tag, auto&& acc_of, auto tail) {
         constexpr int N = decltype(n_tag)::value;
         WF2 f[2];
-        if constexpr (N >= 2) sync(I2{}, tail); else sync(I1{}, tail);
-        load_rs(slab(), f[0]);
+        if constexpr (N >= 2) sync(I2{}, tail, NOX{}); else sync(I1{}, tail, NOX{});
+        next_rs(f[0]);
 #pragma unroll
         for (int i = 0; i < N; ++i) {
             if (i + 1 < N) {
-                if (((i + 1) & 1) == 0) { if (i + 2 < N) sync(I2{}, tail); else sync(I1{}, tail); }
-                load_rs(slab(), f[(i + 1) & 1]);
+                if (((i + 1) & 1) == 0) { if (i + 2 < N) sync(I2{}, tail, NOX{}); else sync(I1{}, tail, NOX{}); }
+                next_rs(f[(i + 1) & 1]);
             }
             f32x4* acc = acc_of(i);
 #pragma unroll
@@ -769,27 +398,11 @@ __global__ __launch_bounds__(512, 2) void chain_front_rs_c320_kernel(const vv_ch
             __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
         }
     };
-    using N5 = std::integral_constant<int, 5>; using N25 = std::integral_constant<int, 25>;
-    auto chan = [&](const int j) -> int { return 64 * (j >> 1) + 32 * hf + 16 * (j & 1) + 4 * lg; };
+    auto chan = [&](const int j) -> int { return rs_chan(j, hf, lg); };
 
     unsigned char* const xmine = xbuf + wave * 5120 + lane * 16;
     const unsigned char* const xpart = xbuf + pw * 5120 + lane * 16;
-    // full swap of the partners' halves: a0 / a1 <- (own k steps, partner's) for both token tiles (two rounds through the 40 KB buffer)
-    auto swap_full = [&](const uint4 (&own)[5][2]) {
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            if (tt) meet();
-#pragma unroll
-            for (int rb = 0; rb < 5; ++rb) *(uint4*)(xmine + rb * 1024) = own[rb][tt];
-            meet();
-#pragma unroll
-            for (int rb = 0; rb < 5; ++rb) {
-                const uint4 o = *(const uint4*)(xpart + rb * 1024);
-                a0[rb][tt] = sel(own[rb][tt], o);
-                a1[rb][tt] = sel(o, own[rb][tt]);
-            }
-        }
-    };
+    auto swap_full = [&](const uint4 (&own)[5][2]) { rs_swap_full(own, a0, a1, xmine, xpart, hi); };
     // ---- x -> GroupNorm apply (scale / shift of the token's own frame) -> activation fragments.  Each wave converts ITS k steps (2 rb + hf) of both
     //      token tiles and the partners swap (no duplicate reads of x); the per-frame affine rows the block touches are staged in LDS first
     int64_t rows[2];
@@ -820,7 +433,7 @@ __global__ __launch_bounds__(512, 2) void chain_front_rs_c320_kernel(const vv_ch
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll 1
         for (int i = 0; i < RS_AH; ++i) issue();
-        meet();                // everybody has read its affine rows: the buffer turns into the exchange buffer
+        rs_meet();                // everybody has read its affine rows: the buffer turns into the exchange buffer
         swap_full(own);
     }
     // ---- proj_in: t = Win a + bin (own channels), stored for the tail kernel and the residual
@@ -844,7 +457,7 @@ __global__ __launch_bounds__(512, 2) void chain_front_rs_c320_kernel(const vv_ch
             for (int j = 0; j < 10; ++j) *(float4*)(trow + chan(j)) = make_float4(t[j][tt][0], t[j][tt][1], t[j][tt][2], t[j][tt][3]);
         }
     }
-    // ---- LN1 (statistics merged with the partner's) -> own k steps -> swap -> full rows
+    // ---- LN1 (statistics merged with the partner's) -> own k steps -> swap -> full rows.  rs_layer_norm in place (see above)
     {
         float mloc[2], m2loc[2];
 #pragma unroll
@@ -863,7 +476,7 @@ __global__ __launch_bounds__(512, 2) void chain_front_rs_c320_kernel(const vv_ch
             m2loc[tt] = q;
         }
         *(float4*)(sbuf + (wave * 64 + lane) * 4) = make_float4(mloc[0], m2loc[0], mloc[1], m2loc[1]);
-        meet();
+        rs_meet();
         const float4 o4 = *(const float4*)(sbuf + (pw * 64 + lane) * 4);
         const float om[2] = {o4.x, o4.z}, oq[2] = {o4.y, o4.w};
         uint4 own[5][2];
@@ -881,7 +494,7 @@ __global__ __launch_bounds__(512, 2) void chain_front_rs_c320_kernel(const vv_ch
                     y[h][0] = (t[j][tt][0] - mean) * rstd * g.x + b.x; y[h][1] = (t[j][tt][1] - mean) * rstd * g.y + b.y;
                     y[h][2] = (t[j][tt][2] - mean) * rstd * g.z + b.z; y[h][3] = (t[j][tt][3] - mean) * rstd * g.w + b.w;
                 }
-                own[rb][tt] = frag(y[0], y[1]);
+                own[rb][tt] = rs_frag<T>(y[0], y[1]);
             }
         }
         swap_full(own);
@@ -962,18 +575,14 @@ extern "C" int vv_spatial_chain_front_c320(const vv_chain_front_params* pp, int 
     if (p.C != CC || p.heads != CH) VV_FAIL(VV_E_UNSUPPORTED, "vv_spatial_chain_front_c320: built for C = 320, 8 heads (got %d, %d)", p.C, p.heads);
     if (p.M <= 0 || p.HW <= 0 || p.M % p.HW) VV_FAIL(VV_E_ARG, "vv_spatial_chain_front_c320: M must be a positive multiple of HW");
     if (p.n_slabs != NF_SLABS || p.n_params != F_TOTAL) VV_FAIL(VV_E_ARG, "vv_spatial_chain_front_c320: stream / parameter block size mismatch (%d slabs, %d floats)", p.n_slabs, p.n_params);
+    // a block of 128 tokens touches at most 127 / HW + 2 frames, and their affine rows are staged in the exchange buffer: 16 frames x 2 x 320 floats
+    if (127 / p.HW + 2 > RS_XBUF / (2 * CC * 4))
+        VV_FAIL(VV_E_UNSUPPORTED, "vv_spatial_chain_front_c320: HW >= 9 required (got %d): the GroupNorm affine rows of a 128-token block must fit the 16-frame staging buffer", p.HW);
     const int64_t nblk = (p.M + 127) / 128;
     if (nblk > 0x7fffffff) VV_FAIL(VV_E_ARG, "vv_spatial_chain_front_c320: grid too large");
     hipStream_t st = (hipStream_t)stream;
-    if (127 / p.HW + 2 <= 16) {      // the block's per-frame affine rows fit the staging buffer (always, beyond toy frame sizes)
-        if (dtype == VV_BF16) hipLaunchKernelGGL(chain_front_rs_c320_kernel<BF16>, dim3((unsigned)nblk), dim3(512), 0, st, p);
-        else if (dtype == VV_F16) hipLaunchKernelGGL(chain_front_rs_c320_kernel<F16>, dim3((unsigned)nblk), dim3(512), 0, st, p);
-        else VV_FAIL(VV_E_ARG, "vv_spatial_chain_front_c320: bad dtype");
-        VV_CHECK_LAUNCH("vv_spatial_chain_front_c320");
-        return VV_OK;
-    }
-    if (dtype == VV_BF16) hipLaunchKernelGGL(chain_front_c320_kernel<BF16>, dim3((unsigned)nblk), dim3(256), 0, st, p);
-    else if (dtype == VV_F16) hipLaunchKernelGGL(chain_front_c320_kernel<F16>, dim3((unsigned)nblk), dim3(256), 0, st, p);
+    if (dtype == VV_BF16) hipLaunchKernelGGL(chain_front_rs_c320_kernel<BF16>, dim3((unsigned)nblk), dim3(512), 0, st, p);
+    else if (dtype == VV_F16) hipLaunchKernelGGL(chain_front_rs_c320_kernel<F16>, dim3((unsigned)nblk), dim3(512), 0, st, p);
     else VV_FAIL(VV_E_ARG, "vv_spatial_chain_front_c320: bad dtype");
     VV_CHECK_LAUNCH("vv_spatial_chain_front_c320");
     return VV_OK;

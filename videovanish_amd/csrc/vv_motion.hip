@@ -20,7 +20,7 @@
 //   A[m][k]: lane holds row m = li, k = 8 lg .. 8 lg + 7;  B[k][n]: column n = li, same k;  D[m][n]: n = li, m = 4 lg + r (r = 0..3).
 //   PERM32: position p = 8 lg + e of a 32-wide k step holds logical index 16 (e >> 2) + 4 lg + (e & 3)  (two D tiles -> one operand).
 #include <type_traits>
-#include "vv_common.h"
+#include "vv_fused_common.h"
 
 namespace {
 
@@ -30,36 +30,6 @@ constexpr int NSLOT = 10, AHEAD = 6, SLAB = 8192;     // slabs are consumed in P
 constexpr int P_GN_A = 0, P_GN_B = 320, P_BIN = 640, P_LN1G = 960, P_LN1B = 1280, P_BO1 = 1600, P_LN2G = 1920, P_LN2B = 2240, P_BO2 = 2560,
               P_LN3G = 2880, P_LN3B = 3200, P_B1 = 3520, P_B2 = 6080, P_BOUT = 6400, P_PE = 6720, P_TOTAL = 6720 + MF * MC;   // 16960 floats
 constexpr int N_SLABS = 25 + 2 * MH * 20 + 20 * 15 + 25;      // 670
-
-__device__ __forceinline__ void glds16_asm(const void* gptr, void* lds_wave_base) {
-    typedef void __attribute__((address_space(3))) * lp_t;
-    const unsigned dst = (unsigned)(size_t)(lp_t)lds_wave_base;
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gptr), "s"(dst) : "memory");
-}
-
-// exact (erf) GELU through Abramowitz-Stegun 7.1.26 (|erf error| <= 1.5e-7, far below the h16 rounding that follows): 2 transcendentals
-// + ~12 VALU instead of the ~30 of erff -- with ONE wave per SIMD the activation is not hidden behind another wave's MFMAs
-// (two GELUs at once on packed fp32 math: v_pk_fma_f32)
-__device__ __forceinline__ vv_f32x2 gelu2(vv_f32x2 x) {
-    const vv_f32x2 ax = {fabsf(x.x), fabsf(x.y)};
-    const vv_f32x2 z = ax * 0.70710678118654752f;
-    const vv_f32x2 d = __builtin_elementwise_fma(z, (vv_f32x2){0.3275911f, 0.3275911f}, (vv_f32x2){1.0f, 1.0f});
-    const vv_f32x2 t = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-    vv_f32x2 q = __builtin_elementwise_fma(t, (vv_f32x2){1.061405429f, 1.061405429f}, (vv_f32x2){-1.453152027f, -1.453152027f});
-    q = __builtin_elementwise_fma(q, t, (vv_f32x2){1.421413741f, 1.421413741f});
-    q = __builtin_elementwise_fma(q, t, (vv_f32x2){-0.284496736f, -0.284496736f});
-    q = __builtin_elementwise_fma(q, t, (vv_f32x2){0.254829592f, 0.254829592f});
-    q = q * t;
-    const vv_f32x2 ez = z * z * -1.4426950408889634f;
-    const vv_f32x2 e = {__builtin_amdgcn_exp2f(ez.x), __builtin_amdgcn_exp2f(ez.y)};
-    const vv_f32x2 erfc = q * e;                                       // 1 - erf(|x| / sqrt 2)
-    return __builtin_elementwise_fma(ax * 0.5f, (vv_f32x2){1.0f, 1.0f} - erfc, x * 0.5f);      // 0.5 x (1 + sign(x) (1 - erfc))
-}
-// The fused kernel evaluates this A&S form.  gelu_poly2 (vv_common.h: packed fp32 polynomial, no v_rcp / v_exp -- the GEMM kernels' GEGLU epilogue since
-// round 6, +4.5..6.6 % there) was measured here too: the motion module LOSES 3 % (3.04 -> 3.13 ms), the chain tail is unchanged -- these kernels
-// run one or two waves per SIMD beside the matrix pipe, the transcendental unit is otherwise idle and the polynomial's 14 extra packed FMAs are not (profiles/r6_gelu_ab.txt)
 
 template <typename T>
 __global__ __launch_bounds__(256, 1) void motion_c320_kernel(const vv_motion_params p) {

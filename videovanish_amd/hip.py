@@ -769,10 +769,13 @@ def spatial_chain_c320(dtype, o, t_in, x, stream_w, params, *, res1=None, out_dt
     return out
 
 
+CHAIN_FRONT_MIN_HW = 9      # vv_spatial_chain_front_c320 stages the GroupNorm affine rows of the <= 127 / HW + 2 frames a 128-token block touches: 16 fit
+
+
 def spatial_chain_front_c320(dtype, x, gamma, beta, groups, eps, stream_w, params, *, F, HW, partials=None):
     """The fused front of a level-0 spatial transformer block (vv_chain.hip): per-frame GroupNorm statistics -> per-channel affine -> ONE kernel for
     GroupNorm apply + proj_in + LayerNorm + the fused q|k|v projection.  Returns (t fp32 [M,320] = the block's residual stream, qkv h16 head-major
-    [F][3][8][HW][40])."""
+    [F][3][8][HW][40]).  HW >= CHAIN_FRONT_MIN_HW tokens per frame: the library refuses smaller frames (nn.SpatialTransformer runs them layer by layer)."""
     _need_cuda(x, gamma, beta, stream_w, params)
     M, Cc = x.shape
     assert M == F * HW and x.dtype == torch.float32

@@ -401,7 +401,8 @@ class FeedForward:
 class SpatialTransformer:
     """Transformer2D block.  At C = 320, 8 heads and 77 text tokens (level 0: 14 blocks per denoise step) everything after the self-attention
     core runs as ONE kernel (csrc/vv_chain.hip: output projection, cross-attention, GEGLU feed-forward, proj_out, all residuals; the token's row
-    stays in registers, weights and the per-head text K / V stream through an LDS ring); other widths run layer by layer."""
+    stays in registers, weights and the per-head text K / V stream through an LDS ring); other widths, and frames of fewer than hip.CHAIN_FRONT_MIN_HW tokens,
+    run layer by layer."""
     FUSED = True          # class-level switch (tests / A-B runs compare both paths on the same weights)
     HEAD_MAJOR_O = True   # the self-attention core's output in head-major layout between the two fused kernels (round 6: whole 80-byte records per store)
 
@@ -445,7 +446,7 @@ class SpatialTransformer:
 
     def __call__(self, x, F, H, W, out_dtype=torch.float32, partials=None):
         HW = H * W      # partials: the partial sums of x left by the convolution that produced it (ResBlock(want_gn=True)), or None
-        if self.fused is not None and SpatialTransformer.FUSED and x.dtype == torch.float32:
+        if self.fused is not None and SpatialTransformer.FUSED and x.dtype == torch.float32 and HW >= hip.CHAIN_FRONT_MIN_HW:
             t, qkv = hip.spatial_chain_front_c320(self.ctx.dt, x, self.norm.g, self.norm.b, self.norm.groups, self.norm.eps, self.front[0], self.front[1],
                                                   F=F, HW=HW, partials=partials)
             hm = SpatialTransformer.HEAD_MAJOR_O

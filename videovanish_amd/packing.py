@@ -207,7 +207,7 @@ def pack_chain_stream(w, h16, heads=8):
 def pack_chain_front_stream(w, h16):
     """w: dict of fp32 tensors of the FRONT of one spatial transformer block at C = 320 -- in.w [C, C] / in.b (proj_in), ln1.g / ln1.b, qkv.w [3C, C]
     (attn1 to_q | to_k | to_v stacked; the query rows already carry scale * log2 e).  Returns (stream [100, 64, 64] h16, params [960] fp32) in
-    the consumption order of vv_chain.hip::chain_front_c320_kernel: proj_in (5 x 5 slabs), then 15 row blocks x 5 k tiles of the fused projection."""
+    the consumption order of vv_chain.hip::chain_front_rs_c320_kernel: proj_in (5 x 5 slabs), then 15 row blocks x 5 k tiles of the fused projection."""
     C = w["in.w"].shape[0]
     assert C == 320 and w["qkv.w"].shape == (3 * C, C)
     slabs = _dense_slabs(_permute_k(w["in.w"]), h16, 64) + _dense_slabs(_permute_k(w["qkv.w"]), h16, 64)
