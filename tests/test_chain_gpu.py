@@ -96,13 +96,14 @@ def test_head_major_attention_output_is_bit_identical(gpu):
     """Round 6: between the self-attention core and the fused tail the O tensor is head-major [frame][head][token][40]
     (vv_attn_params.o_hs / vv_chain_params.o_hw): the attention kernels store whole contiguous 80-byte records instead of an 80-byte slice of a 640-byte
     row.  Same values at other addresses: the attention output permuted back equals the row-major output bit for bit (d = 40 spatial kernels incl. a ragged
-    token count, and the generic kernel at d = 64), and the block's result is bit-identical with either layout -- also when a 128-token block of the tail
+    token count, and N = 1115: attn40q2_kernel's LDS-staged store on full waves, its direct store on the ragged last wave and waves past Nq in one launch;
+    the generic kernel at d = 64), and the block's result is bit-identical with either layout -- also when a 128-token block of the tail
     straddles two frames (HW = 1000) and at the bench geometry's frame size."""
     from videovanish_amd import hip, nn as vnn
     cfg = UNetConfig()
     g = torch.Generator().manual_seed(9)
     ctx = vnn.Ctx("cuda:0", "fp16", 0)
-    for (B, heads, N, D) in ((2, 8, 1000, 40), (1, 8, 4096, 40), (3, 4, 200, 64), (2, 8, 900, 80)):
+    for (B, heads, N, D) in ((2, 8, 1000, 40), (1, 8, 4096, 40), (2, 8, 1115, 40), (3, 4, 200, 64), (2, 8, 900, 80)):
         C = heads * D
         qkv = (torch.randn(B, 3, heads, N, D, generator=g) * 0.5).to(gpu).to(ctx.h16)
         outs = []

@@ -416,7 +416,7 @@ def test_attention_online_softmax_rescale(gpu):
     assert (got - ref).abs().max().item() <= 2 ** -6 * max(1.0, ref.abs().max().item())
 
 
-@pytest.mark.parametrize("N", [64 * 9 - 37, 64 * 18 - 37, 64 * 17])      # 32 queries per wave (N < 1024) / 64 queries per wave, ragged and whole last tile
+@pytest.mark.parametrize("N", [64 * 9 - 37, 64 * 9, 64 * 18 - 37, 64 * 17])      # 32 queries per wave (N < 1024) / 64 queries per wave, each with a ragged and a whole last tile
 @pytest.mark.parametrize("D", [40, 80])                                   # d = 80: attn80_kernel (N >= 512; the reference enters through the MFMA's C operand)
 @pytest.mark.parametrize("dname,td,ulp", [("bf16", torch.bfloat16, 2 ** -8), ("fp16", torch.float16, 2 ** -11)])
 def test_attention_d40_lazy_reference_maximum(gpu, dname, td, ulp, N, D):

@@ -39,4 +39,6 @@ if os.environ.get("VV_BENCH_CHECK"):               # one (frame, head) against a
     ref = torch.softmax((q @ k.t()) * 0.6931471805599453, -1) @ v
     err = (out.view(B, N, heads, D)[b, :, h].float() - ref).abs().max().item()
     print(f"check (b={b}, h={h}): max-abs {err:.3e} (output range {ref.abs().max().item():.2f})")
+    import hashlib                                 # A/B of two libraries: the arithmetic and its order are the same when the hashes are
+    print(f"sha256 of out: {hashlib.sha256(out.cpu().view(torch.int16).numpy().tobytes()).hexdigest()}")
 print(f"{dname} spatial attention d{D} N{N} x{B} frames: {t * 1e3:.3f} ms = {4.0 * B * heads * N * N * D / t / 1e12:.1f} TFLOP/s")

@@ -43,23 +43,12 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn_kernel(const vv_attn_params
 
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int li = lane & 15, lg = lane >> 4;
-    // XCD-aware decode: blocks i and i+8 share an XCD (and its L2).  Give every XCD its own (batch, head) pairs and walk
-    // that pair's query tiles on it, so the pair's K/V (re-read by every query tile) stays resident in ONE 4 MiB L2.
     int qt, h, b;
-    {
-        const int nbh = p.B * p.heads;
-        const int full = (nbh / 8) * 8;                       // pairs handled in XCD-striped rounds of 8
-        const int bid = blockIdx.x;
-        int bh;
-        if (bid < full * nqt) { const int xcd = bid & 7, idx = bid >> 3; bh = (idx / nqt) * 8 + xcd; qt = idx % nqt; }
-        else { const int r = bid - full * nqt; bh = full + r / nqt; qt = r % nqt; }
-        h = bh % p.heads; b = bh / p.heads;
-    }
-
-    const unsigned short* Q = (const unsigned short*)p.q + (int64_t)b * p.q_bs + (int64_t)h * (p.q_hs ? p.q_hs : D);
-    const unsigned short* Kp = (const unsigned short*)p.k + (int64_t)b * p.k_bs + (int64_t)h * (p.k_hs ? p.k_hs : D);
-    const unsigned short* Vp = (const unsigned short*)p.v + (int64_t)b * p.v_bs + (int64_t)h * (p.v_hs ? p.v_hs : D);
-    unsigned short* O = (unsigned short*)p.o + (int64_t)b * p.o_bs + (int64_t)h * (p.o_hs ? p.o_hs : D);
+    attn_block_decode(p, nqt, qt, h, b);
+    const unsigned short* Q = attn_head_base<D>(p.q, b, p.q_bs, h, p.q_hs);
+    const unsigned short* Kp = attn_head_base<D>(p.k, b, p.k_bs, h, p.k_hs);
+    const unsigned short* Vp = attn_head_base<D>(p.v, b, p.v_bs, h, p.v_hs);
+    unsigned short* O = attn_head_base<D>(p.o, b, p.o_bs, h, p.o_hs);
 
     const int q0 = qt * BQ + wave * QT * 16;
     // ---- Q fragments (B operand of S^T): lane holds Q[q0 + j*16 + li][s*32 + lg*8 .. +7]

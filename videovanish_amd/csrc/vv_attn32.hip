@@ -10,11 +10,11 @@ namespace {
 // d = 40 spatial self-attention on the FULL-SIZE matrix instruction (v_mfma_f32_32x32x16): the dominant kernel of the denoise step.
 //
 // Why another kernel: on the 16x16x32 form an MFMA occupies the SIMD's vector-issue port for 8 of its 16 cycles, and the 28 MFMAs of a
-// 32-query x 64-key tile then take as much issue time as the 32 v_exp_f32 the tile also needs -- the kernel above is issue bound at ~48 % matrix
+// 32-query x 64-key tile then take as much issue time as the 32 v_exp_f32 the tile also needs -- attn_kernel (vv_attn.hip) is issue bound at ~48 % matrix
 // pipe.  A 32x32x16 MFMA does twice the work per issue (8 of 32 cycles), and its K step of 16 pads d = 40 + the two lazy-maximum slots to 48
 // instead of 64: QK^T is 6 MFMAs per tile instead of 16, PV 8 (M = d padded to 64) instead of 12, with 6 + 16 LDS fragment reads instead of 8 + 12.
 //
-// Per wave: 32 queries (lane & 31 = the query, like the kernel above a lane owns its query's softmax row; lane >> 5 = h splits the keys).
+// Per wave: 32 queries (lane & 31 = the query, as in attn_kernel of vv_attn.hip a lane owns its query's softmax row; lane >> 5 = h splits the keys).
 //   S^T[32 keys][32 q] = K Q^T:  A = K rows (ds_read_b128, 16 B = k slots 16s + 8h .. +7), B = Q in registers (3 k steps: 40 data + slots 40,41 =
 //   -m hi/lo against 1.0 in K + 6 zeros).  Accumulator register i of a lane holds key (i & 3) + 8 (i >> 2) + 4 h.
 //   P = exp2(S^T) packed pairwise IS the B operand of O^T += V^T P^T (k order of step s': key 16 s' + 8 (j >> 2) + 4 h + (j & 3), j = 0..7):
@@ -35,6 +35,133 @@ template <> struct Mfma32<F16> {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     }
 };
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The toolkit of the three kernels below (a32_: all three, a40_: attn40_kernel and attn40q2_kernel).  Everything here leaves the device code of all
+// twelve instantiations byte for byte as it was with the text written out in each kernel.  What the two d = 40 kernels still carry twice -- the four LDS arrays
+// and their fill, the DMA piece table and the `dma` lambda, the lane-constant read addresses, the output stores -- moved their code in every spelling
+// tried (function, struct, arguments by value or by reference: profiles/attn32_shared_isa.txt), so it stays in place, marked "(twice: ...)" at attn40q2_kernel.
+
+// d = 40, both kernels.  LDS: dense 80-byte rows (5 chunks of 8 h16) -- a K or V tile is exactly 5 KB = 5 LDS-DMA wave instructions with EVERY lane
+// active (no exec masking, no pad slots), 10 per 64-key tile.  The constant operand slots come from a region of 1.0 instead of from the rows:
+//   K slots 40..47 (Q carries -m hi, -m lo, 0 x 6 there)  and  V columns 40..43 (O^T rows 40.. = sum_k P, the softmax denominator).
+// Row orders: K natural (80-byte pitch: 16 consecutive rows x one chunk hit 16 different 16-byte bank slots);
+//             V key 16 g + 4 j + q at row 16 g + 4 q + j (the 4 rows of one transposed read are 4 apart: conflict free at 80 bytes).
+namespace a40 {
+constexpr int D = 40, KVT = 64, PR = 80, NCH = 5;
+constexpr int TILE = KVT * PR;                            // 5120
+constexpr int NPC = 2 * TILE / 1024;                      // 10 DMA pieces (1 KB each) per tile: 0..4 = K, 5..9 = V
+constexpr int KONES = 32 * PR + 64, VONES = 4096 + 64;   // bytes of 1.0 behind each tile buffer (reached with the key-block / k-step immediates)
+constexpr float MARGIN = -4.0f;     // P = 2^4 at the sample maximum: see the comment above attn40_kernel
+}  // namespace a40
+
+// rows 32.. of O^T on the 16x16x32 form (M = 16 instead of a second, three-quarters empty 32-row block): v_permlane16_swap turns the
+// (s2 = 0, s2 = 1) dword pairs of P -- rows {q 0..15 | q 16..31} x {h = 0 | h = 1} -- into the B operands of the two query tiles:
+// every 16-lane row then holds queries 0..15 (pa; pq: 16..31) and k group g = (h, s2) = keys 32 kb + 16 s2 + 4 h + {0..3, 8..11}
+__device__ __forceinline__ void a32_swap16(const uint4& p0, const uint4& p1, uint4& pa, uint4& pq) {
+    auto s0 = __builtin_amdgcn_permlane16_swap(p0.x, p1.x, false, false);
+    auto s1 = __builtin_amdgcn_permlane16_swap(p0.y, p1.y, false, false);
+    auto s2 = __builtin_amdgcn_permlane16_swap(p0.z, p1.z, false, false);
+    auto s3 = __builtin_amdgcn_permlane16_swap(p0.w, p1.w, false, false);
+    pa = make_uint4(s0[0], s1[0], s2[0], s3[0]);
+    pq = make_uint4(s0[1], s1[1], s2[1], s3[1]);
+}
+
+// d = 40: keys past Nkv of the ragged last tile: -inf scores (P = 0)
+__device__ __forceinline__ void a40_mask_last(f32x16 (&sacc)[2], const int h, const int nlast) {
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if (kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h >= nlast) sacc[kb][i] = -1e30f;
+}
+__device__ __forceinline__ float a40_row_max(const f32x16 (&sacc)[2]) {
+    float mx = sacc[0][0];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sacc[kb][i]);
+    return fmaxf(mx, __shfl_xor(mx, 32));
+}
+
+// d = 40, the second half of a tile for one 32-query block: P = exp2(S) packed (in place: sc), O^T += V(tile at cV)^T P^T.  va0 / va1: the lane's
+// transposed-read addresses of d block 0 / 1 (at the kernels)
+template <typename T>
+__device__ __forceinline__ void a40_pv(const unsigned char* cV, f32x16 (&sc)[2], f32x16& oacc, f32x4 (&o2)[2], const int& va0, const int& va1) {
+    constexpr int PR = a40::PR;
+    uint4 pb[2][2];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sc[kb][i] = __builtin_amdgcn_exp2f(sc[kb][i]);
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2)
+            pb[kb][s2] = make_uint4(pack2<T>(sc[kb][8 * s2 + 0], sc[kb][8 * s2 + 1]), pack2<T>(sc[kb][8 * s2 + 2], sc[kb][8 * s2 + 3]),
+                                    pack2<T>(sc[kb][8 * s2 + 4], sc[kb][8 * s2 + 5]), pack2<T>(sc[kb][8 * s2 + 6], sc[kb][8 * s2 + 7]));
+    }
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+            // rows 0..31 of O^T: keys 32 kb + 16 s2 + 8 j4 + 4 h + q, j4 = 0 (elements 0..3), 1 (elements 4..7): V rows 16 (2 kb + s2) + 4 q + 2 j4 + h
+            const int g0 = 16 * (2 * kb + s2) * PR;
+            const uint2 lo = ds_read_tr16(cV + g0 + va0), hi = ds_read_tr16(cV + g0 + 2 * PR + va0);
+            const uint4 vf = make_uint4(lo.x, lo.y, hi.x, hi.y);
+            oacc = Mfma32<T>::run(vf, pb[kb][s2], oacc);
+        }
+        uint4 pa, pq;                                             // rows 32..47
+        a32_swap16(pb[kb][0], pb[kb][1], pa, pq);
+        const uint2 lo = ds_read_tr16(cV + kb * 32 * PR + va1), hi = ds_read_tr16(cV + kb * 32 * PR + 2 * PR + va1);
+        const uint4 vf = make_uint4(lo.x, lo.y, hi.x, hi.y);
+        o2[0] = T::mfma(vf, pa, o2[0]); o2[1] = T::mfma(vf, pq, o2[1]);
+    }
+}
+
+// d = 40: the pad slots 40, 41 of Q (first dword of the pad chunk) = -target as the nearest h16 hi + lo pair
+template <typename T>
+__device__ __forceinline__ unsigned a40_ref_slots(const float target) {
+    const unsigned short hi = T::from_f32(-target);
+    const unsigned short lo = T::from_f32(-target - T::to_f32(hi));
+    return (unsigned)hi | ((unsigned)lo << 16);
+}
+
+// d = 40: S^T = K Q^T for the 64 keys of the K tile at sK (2 key blocks x 3 k steps); ka0 / ka2: the lane's read addresses (at the kernels)
+template <typename T>
+__device__ __forceinline__ void a40_qk(const unsigned char* sK, const uint4 q0, const uint4 q1, const uint4 q2, f32x16 (&sacc)[2], const int ka0, const int ka2) {
+    const uint4 qf[3] = {q0, q1, q2};
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sacc[kb][i] = 0.f;
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            const uint4 kf = s < 2 ? *(const uint4*)(sK + kb * 32 * a40::PR + ka0 + 32 * s) : *(const uint4*)(sK + kb * 32 * a40::PR + ka2);
+            sacc[kb] = Mfma32<T>::run(kf, qf[s], sacc[kb]);
+        }
+    }
+}
+
+// a Q fragment times scale * log2(e) (and rounded to h16 again), for callers that did not fold the factor into Q (q_prescaled = 0)
+template <typename T>
+__device__ __forceinline__ uint4 a32_scale_q(const uint4 f, const float scale) {
+    float qv[8];
+    unpack8<T>(f, qv);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) qv[e] *= scale * 1.4426950408889634f;
+    return pack8<T>(qv);
+}
+
+// one launcher: `ragged` / `whole` = the kernel's instantiations for a last key tile of fewer than 64 keys / whole tiles, BQ = queries per block
+typedef void (*a32_kernel_t)(const vv_attn_params, const int);
+template <int NW, int BQ>
+int a32_launch(const a32_kernel_t ragged, const a32_kernel_t whole, const vv_attn_params& p, hipStream_t st, const char* what) {
+    const int nqt = (p.Nq + BQ - 1) / BQ;
+    const int64_t nblk = (int64_t)p.B * p.heads * nqt;
+    if (nblk > 0x7fffffff) VV_FAIL(VV_E_ARG, "vv_attention: grid too large");
+    hipLaunchKernelGGL(p.Nkv % 64 ? ragged : whole, dim3((unsigned)nblk), dim3(NW * 64), 0, st, p, nqt);
+    VV_CHECK_LAUNCH(what);
+    return VV_OK;
+}
 
 // self-attention (Nq == Nkv): the score of query q against ITS OWN key, from the lane's Q fragments (lane half h holds the 16 s + 8 h .. +7 slots of
 // the three k steps: 24 + 16 of the 40 products); -1e30 when there is no such key
@@ -60,7 +187,7 @@ __device__ __forceinline__ float attn40_diag_score(const vv_attn_params& p, cons
 // OPTIMISTIC reference (this kernel) instead of the lazy running one: the softmax reference m of a query is fixed ONCE, before the key loop, from
 // the exact maximum of its scores against a 64-key sample spread over the whole sequence -- plus, for self-attention (Nq == Nkv), the query's OWN
 // key: trained self-attention maps are often diagonal dominant, and a dominant key outside the sample is what forces the slow repeat below -- (+ MARGIN),
-// and rides in the pad slots as before.  MARGIN = -4 since round 4 (was +4): the sample maximum maps to P = 2^4, so a later score may beat it by 12
+// and rides in the pad slots 40, 41 of Q.  MARGIN = -4 since round 4 (was +4): the sample maximum maps to P = 2^4, so a later score may beat it by 12
 // binary orders before fp16 overflows (the repeat below makes any input correct), while scores down to 18 orders BELOW the sample maximum keep the full
 // 11-bit precision and 28 orders stay representable -- with +4 a bulk of keys 12..20 orders below one sampled outlier went subnormal / to zero although
 // thousands of them still carry part of the softmax mass (tests/test_kernels_gpu.py::test_attention_d40_heavy_tail).  The
@@ -72,18 +199,9 @@ __device__ __forceinline__ float attn40_diag_score(const vv_attn_params& p, cons
 // exact maximum (a QK^T-only sweep first): correct for any input, slow only for the blocks that hit it.  bf16 cannot overflow at all.
 template <typename T, int NW, int OCC, bool RAGGED>
 __global__ __launch_bounds__(NW * 64, OCC) void attn40_kernel(const vv_attn_params p, const int nqt) {
-    // LDS: dense 80-byte rows (5 chunks of 8 h16) -- a K or V tile is exactly 5 KB = 5 LDS-DMA wave instructions with EVERY lane active (no
-    // exec masking, no pad slots), 10 per 64-key tile.  The constant operand slots come from a region of 1.0 instead of from the rows:
-    //   K slots 40..47 (Q carries -m hi, -m lo, 0 x 6 there)  and  V columns 40..43 (O^T rows 40.. = sum_k P, the softmax denominator).
-    // Row orders: K natural (80-byte pitch: 16 consecutive rows x one chunk hit 16 different 16-byte bank slots);
-    //             V key 16 g + 4 j + q at row 16 g + 4 q + j (the 4 rows of one transposed read are 4 apart: conflict free at 80 bytes).
-    constexpr int D = 40, KVT = 64, PR = 80, NCH = 5;
+    using namespace a40;
     constexpr int NT = NW * 64, BQ = NW * 32;
-    constexpr int TILE = KVT * PR;                            // 5120
-    constexpr int NPC = 2 * TILE / 1024;                      // 10 DMA pieces (1 KB each) per tile: 0..4 = K, 5..9 = V
     constexpr int PPW = (NPC + NW - 1) / NW;                  // pieces per wave (piece j -> wave j % NW)
-    constexpr int KONES = 32 * PR + 64, VONES = 4096 + 64;   // bytes of 1.0 behind each tile buffer (reached with the key-block / k-step immediates)
-    constexpr float MARGIN = -4.0f;     // P = 2^4 at the sample maximum: see the comment above attn40_kernel (round 4)
     // FOUR arrays, not one: hipcc drains vmcnt(0) in front of a ds_read that may alias an LDS-DMA in flight, and tells buffers apart only as
     // distinct __shared__ objects (the DMA of step `it` targets the buffers the step does not read)
     __shared__ __attribute__((aligned(1024))) unsigned char dK0[TILE + KONES];
@@ -94,19 +212,11 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn40_kernel(const vv_attn_para
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int r = lane & 31, h = lane >> 5;
     int qt, hd, b;
-    {
-        const int nbh = p.B * p.heads;
-        const int full = (nbh / 8) * 8;
-        const int bid = blockIdx.x;
-        int bh;
-        if (bid < full * nqt) { const int xcd = bid & 7, idx = bid >> 3; bh = (idx / nqt) * 8 + xcd; qt = idx % nqt; }
-        else { const int rr = bid - full * nqt; bh = full + rr / nqt; qt = rr % nqt; }
-        hd = bh % p.heads; b = bh / p.heads;
-    }
-    const unsigned short* Q = (const unsigned short*)p.q + (int64_t)b * p.q_bs + (int64_t)hd * (p.q_hs ? p.q_hs : D);
-    const unsigned char* Kp = (const unsigned char*)((const unsigned short*)p.k + (int64_t)b * p.k_bs + (int64_t)hd * (p.k_hs ? p.k_hs : D));
-    const unsigned char* Vp = (const unsigned char*)((const unsigned short*)p.v + (int64_t)b * p.v_bs + (int64_t)hd * (p.v_hs ? p.v_hs : D));
-    unsigned short* O = (unsigned short*)p.o + (int64_t)b * p.o_bs + (int64_t)hd * (p.o_hs ? p.o_hs : D);
+    attn_block_decode(p, nqt, qt, hd, b);
+    const unsigned short* Q = attn_head_base<D>(p.q, b, p.q_bs, hd, p.q_hs);
+    const unsigned char* Kp = (const unsigned char*)attn_head_base<D>(p.k, b, p.k_bs, hd, p.k_hs);      // (bytes: the DMA source addresses)
+    const unsigned char* Vp = (const unsigned char*)attn_head_base<D>(p.v, b, p.v_bs, hd, p.v_hs);
+    unsigned short* O = attn_head_base<D>(p.o, b, p.o_bs, hd, p.o_hs);
 
     // ---- Q fragments: lane (r, h) holds Q[q0 + r][16 s + 8 h .. +7]; chunk 5 (s = 2, h = 1) is the pad chunk: slots 40, 41 = -m (hi, lo)
     const int q0 = qt * BQ + wave * 32;
@@ -115,13 +225,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn40_kernel(const vv_attn_para
     for (int s = 0; s < 3; ++s) {
         const int q = q0 + r, d0 = 16 * s + 8 * h;
         qf[s] = (q < p.Nq && d0 < D) ? *(const uint4*)(Q + (int64_t)q * p.q_rs + d0) : make_uint4(0, 0, 0, 0);
-        if (!p.q_prescaled) {
-            float qv[8];
-            unpack8<T>(qf[s], qv);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) qv[e] *= p.scale * 1.4426950408889634f;
-            qf[s] = pack8<T>(qv);
-        }
+        if (!p.q_prescaled) qf[s] = a32_scale_q<T>(qf[s], p.scale);
     }
     const float dg = attn40_diag_score<T>(p, Kp, qf, q0 + r, h);      // self-attention: score against the query's own key (part of the reference sample)
     // ---- constant regions (written once): 1.0 everywhere; the tile buffers start as zeros (rows of a ragged tile that are never loaded stay finite)
@@ -176,38 +280,10 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn40_kernel(const vv_attn_para
     const int va1 = vpp == 2 ? TILE : (16 * vcb + 4 * vq + h) * PR + 64 + 8 * (vpp & 1);
 
     // S^T = K Q^T for the 64 keys of the K tile at byte offset kb0 (2 key blocks x 3 k steps)
-    auto qk = [&](const unsigned char* sK, f32x16 (&sacc)[2]) {
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) sacc[kb][i] = 0.f;
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                const uint4 kf = s < 2 ? *(const uint4*)(sK + kb * 32 * PR + ka0 + 32 * s) : *(const uint4*)(sK + kb * 32 * PR + ka2);
-                sacc[kb] = Mfma32<T>::run(kf, qf[s], sacc[kb]);
-            }
-        }
-    };
-    auto mask_last = [&](f32x16 (&sacc)[2]) {                     // keys past Nkv of the ragged last tile: -inf scores (P = 0)
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-                if (kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h >= nlast) sacc[kb][i] = -1e30f;
-    };
-    auto row_max = [&](const f32x16 (&sacc)[2]) {
-        float mx = sacc[0][0];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sacc[kb][i]);
-        return fmaxf(mx, __shfl_xor(mx, 32));
-    };
-    auto set_reference = [&](const float target) {                // pad slots 40, 41 of Q <- -target as the nearest h16 hi + lo pair
-        const unsigned short hi = T::from_f32(-target);
-        const unsigned short lo = T::from_f32(-target - T::to_f32(hi));
-        qf[2].x = h == 1 ? ((unsigned)hi | ((unsigned)lo << 16)) : qf[2].x;
-    };
+    auto qk = [&](const unsigned char* sK, f32x16 (&sacc)[2]) { a40_qk<T>(sK, qf[0], qf[1], qf[2], sacc, ka0, ka2); };
+    auto mask_last = [&](f32x16 (&sacc)[2]) { a40_mask_last(sacc, h, nlast); };
+    auto row_max = [&](const f32x16 (&sacc)[2]) { return a40_row_max(sacc); };
+    auto set_reference = [&](const float target) { qf[2].x = h == 1 ? a40_ref_slots<T>(target) : qf[2].x; };
 
     f32x16 oacc;              // O^T rows 0..31 (32x32x16 layout: lane = query, registers + h = d)
     f32x4 o2[2];              // O^T rows 32..47 for the queries 0..15 / 16..31 of the wave (16x16x32 layout: lane & 15 = query, 4 (lane >> 4) + reg = d - 32)
@@ -254,42 +330,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn40_kernel(const vv_attn_para
         // one pipeline step: S_next = K(it+1) Q^T  |  P = exp2(S_cur), packed  |  O^T += V(it)^T P^T     -- ONE basic block, no branch
         auto body = [&](const unsigned char* nK, const unsigned char* cV, f32x16 (&sc)[2], f32x16 (&sn)[2]) {
             qk(nK, sn);
-            uint4 pb[2][2];
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) sc[kb][i] = __builtin_amdgcn_exp2f(sc[kb][i]);
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
-                    pb[kb][s2] = make_uint4(pack2<T>(sc[kb][8 * s2 + 0], sc[kb][8 * s2 + 1]), pack2<T>(sc[kb][8 * s2 + 2], sc[kb][8 * s2 + 3]),
-                                            pack2<T>(sc[kb][8 * s2 + 4], sc[kb][8 * s2 + 5]), pack2<T>(sc[kb][8 * s2 + 6], sc[kb][8 * s2 + 7]));
-            }
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    // rows 0..31 of O^T: keys 32 kb + 16 s2 + 8 j4 + 4 h + q, j4 = 0 (elements 0..3), 1 (elements 4..7): V rows 16 (2 kb + s2) + 4 q + 2 j4 + h
-                    const int g0 = 16 * (2 * kb + s2) * PR;
-                    const uint2 lo = ds_read_tr16(cV + g0 + va0), hi = ds_read_tr16(cV + g0 + 2 * PR + va0);
-                    const uint4 vf = make_uint4(lo.x, lo.y, hi.x, hi.y);
-                    oacc = Mfma32<T>::run(vf, pb[kb][s2], oacc);
-                }
-                // rows 32..47 on the 16x16x32 form (M = 16 instead of a second, three-quarters empty 32-row block): v_permlane16_swap turns the
-                // (s2 = 0, s2 = 1) dword pairs of P -- rows {q 0..15 | q 16..31} x {h = 0 | h = 1} -- into the B operands of the two query tiles:
-                // every 16-lane row then holds queries 0..15 (resp. 16..31) and k group g = (h, s2) = keys 32 kb + 16 s2 + 4 h + {0..3, 8..11}
-                uint4 pa, pq;
-                {
-                    auto s0 = __builtin_amdgcn_permlane16_swap(pb[kb][0].x, pb[kb][1].x, false, false);
-                    auto s1 = __builtin_amdgcn_permlane16_swap(pb[kb][0].y, pb[kb][1].y, false, false);
-                    auto s2_ = __builtin_amdgcn_permlane16_swap(pb[kb][0].z, pb[kb][1].z, false, false);
-                    auto s3 = __builtin_amdgcn_permlane16_swap(pb[kb][0].w, pb[kb][1].w, false, false);
-                    pa = make_uint4(s0[0], s1[0], s2_[0], s3[0]);
-                    pq = make_uint4(s0[1], s1[1], s2_[1], s3[1]);
-                }
-                const uint2 lo = ds_read_tr16(cV + kb * 32 * PR + va1), hi = ds_read_tr16(cV + kb * 32 * PR + 2 * PR + va1);
-                const uint4 vf = make_uint4(lo.x, lo.y, hi.x, hi.y);
-                o2[0] = T::mfma(vf, pa, o2[0]); o2[1] = T::mfma(vf, pq, o2[1]);
-            }
+            a40_pv<T>(cV, sc, oacc, o2, va0, va1);
         };
         // step `it`: K(it+1) and V(it) have landed (issued one step ago); issue K(it+2) over K(it) and V(it+1) over V(it-1)
         auto step = [&](const int it, unsigned char* kA, unsigned char* kB, unsigned char* vA, unsigned char* vB, f32x16 (&sc)[2], f32x16 (&sn)[2]) {
@@ -337,16 +378,10 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn40q2_kernel(const vv_attn_pa
     // TWO 32-query blocks per wave (a, b): every K / V fragment read from LDS and every LDS-DMA piece serves 64 queries -- half the LDS and L2 -> LDS
     // bytes per FLOP of attn40_kernel (the chip is power limited on this kernel: fewer bytes moved = a higher clock).  Not pipelined across
     // tiles; the two blocks overlap each other instead: QK_a, QK_b | exp_a, PV_a | exp_b, PV_b in ONE basic block per tile.
-    // LDS images, constant regions and row orders: as attn40_kernel above.
-    constexpr int D = 40, KVT = 64, PR = 80, NCH = 5;
+    using namespace a40;
     constexpr int NT = NW * 64, QB = 2, BQ = NW * 32 * QB;
-    constexpr int TILE = KVT * PR;                            // 5120
-    constexpr int NPC = 2 * TILE / 1024;                      // 10 DMA pieces (1 KB each) per tile: 0..4 = K, 5..9 = V
     constexpr int PPW = (NPC + NW - 1) / NW;                  // pieces per wave (piece j -> wave j % NW)
-    constexpr int KONES = 32 * PR + 64, VONES = 4096 + 64;   // bytes of 1.0 behind each tile buffer (reached with the key-block / k-step immediates)
-    constexpr float MARGIN = -4.0f;     // P = 2^4 at the sample maximum: see the comment above attn40_kernel (round 4)
-    // FOUR arrays, not one: hipcc drains vmcnt(0) in front of a ds_read that may alias an LDS-DMA in flight, and tells buffers apart only as
-    // distinct __shared__ objects (the DMA of step `it` targets the buffers the step does not read)
+    // (twice: four arrays, not one, for the reason given at attn40_kernel)
     __shared__ __attribute__((aligned(1024))) unsigned char dK0[TILE + KONES];
     __shared__ __attribute__((aligned(1024))) unsigned char dK1[TILE + KONES];
     __shared__ __attribute__((aligned(1024))) unsigned char dV0[TILE + VONES];
@@ -355,19 +390,11 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn40q2_kernel(const vv_attn_pa
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int r = lane & 31, h = lane >> 5;
     int qt, hd, b;
-    {
-        const int nbh = p.B * p.heads;
-        const int full = (nbh / 8) * 8;
-        const int bid = blockIdx.x;
-        int bh;
-        if (bid < full * nqt) { const int xcd = bid & 7, idx = bid >> 3; bh = (idx / nqt) * 8 + xcd; qt = idx % nqt; }
-        else { const int rr = bid - full * nqt; bh = full + rr / nqt; qt = rr % nqt; }
-        hd = bh % p.heads; b = bh / p.heads;
-    }
-    const unsigned short* Q = (const unsigned short*)p.q + (int64_t)b * p.q_bs + (int64_t)hd * (p.q_hs ? p.q_hs : D);
-    const unsigned char* Kp = (const unsigned char*)((const unsigned short*)p.k + (int64_t)b * p.k_bs + (int64_t)hd * (p.k_hs ? p.k_hs : D));
-    const unsigned char* Vp = (const unsigned char*)((const unsigned short*)p.v + (int64_t)b * p.v_bs + (int64_t)hd * (p.v_hs ? p.v_hs : D));
-    unsigned short* O = (unsigned short*)p.o + (int64_t)b * p.o_bs + (int64_t)hd * (p.o_hs ? p.o_hs : D);
+    attn_block_decode(p, nqt, qt, hd, b);
+    const unsigned short* Q = attn_head_base<D>(p.q, b, p.q_bs, hd, p.q_hs);
+    const unsigned char* Kp = (const unsigned char*)attn_head_base<D>(p.k, b, p.k_bs, hd, p.k_hs);      // (bytes: the DMA source addresses)
+    const unsigned char* Vp = (const unsigned char*)attn_head_base<D>(p.v, b, p.v_bs, hd, p.v_hs);
+    unsigned short* O = attn_head_base<D>(p.o, b, p.o_bs, hd, p.o_hs);
 
     // ---- Q fragments: lane (r, h) holds Q[q0 + r][16 s + 8 h .. +7]; chunk 5 (s = 2, h = 1) is the pad chunk: slots 40, 41 = -m (hi, lo)
     const int q0 = qt * BQ + wave * 32 * QB;
@@ -379,13 +406,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn40q2_kernel(const vv_attn_pa
     for (int s = 0; s < 3; ++s) {
         const int q = q0 + 32 * x + r, d0 = 16 * s + 8 * h;
         qf[x][s] = (q < p.Nq && d0 < D) ? *(const uint4*)(Q + (int64_t)q * p.q_rs + d0) : make_uint4(0, 0, 0, 0);
-        if (!p.q_prescaled) {
-            float qv[8];
-            unpack8<T>(qf[x][s], qv);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) qv[e] *= p.scale * 1.4426950408889634f;
-            qf[x][s] = pack8<T>(qv);
-        }
+        if (!p.q_prescaled) qf[x][s] = a32_scale_q<T>(qf[x][s], p.scale);
     }
     float dg[QB];                                              // self-attention: score against the query's own key (part of the reference sample)
 #pragma unroll
@@ -394,15 +415,14 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn40q2_kernel(const vv_attn_pa
     {
         const unsigned one2 = (unsigned)T::from_f32(1.0f) * 0x10001u;
         const uint4 ones = make_uint4(one2, one2, one2, one2), zero = make_uint4(0, 0, 0, 0);
-        // (two loops per region, not `i < TILE / 16 ? zero : ones`: hipcc turned that select into a 32-byte SCRATCH array indexed by the condition -- every thread of the
-        //  launch wrote and re-read it: 0.12 GB of HBM writes per level-0 launch, 29 % of the kernel's WRITE_SIZE; found in round 6 through private_segment_fixed_size = 48)
+        // (twice: as in attn40_kernel -- two loops per region for the reason given there)
         for (int i = t; i < TILE / 16; i += NT) { *(uint4*)(dK0 + i * 16) = zero; *(uint4*)(dK1 + i * 16) = zero; *(uint4*)(dV0 + i * 16) = zero; *(uint4*)(dV1 + i * 16) = zero; }
         for (int i = TILE / 16 + t; i < (TILE + KONES) / 16; i += NT) { *(uint4*)(dK0 + i * 16) = ones; *(uint4*)(dK1 + i * 16) = ones; }
         for (int i = TILE / 16 + t; i < (TILE + VONES) / 16; i += NT) { *(uint4*)(dV0 + i * 16) = ones; *(uint4*)(dV1 + i * 16) = ones; }
     }
     __syncthreads();
 
-    // ---- this wave's DMA pieces: piece j = wave + NW * i; slot = (j % 5) * 64 + lane = row * 5 + chunk of the K (j < 5) or V tile
+    // ---- this wave's DMA pieces (twice: down to the `dma` lambda as in attn40_kernel): piece j = wave + NW * i; slot = (j % 5) * 64 + lane = row * 5 + chunk of the K (j < 5) or V tile
     unsigned doff[PPW];          // byte offset of the slot's source inside a tile (K: key = row; V: key = 16 g + 4 (row & 3) + ((row >> 2) & 3))
     int dkey[PPW];               // key index inside the tile (ragged last tile)
 #pragma unroll
@@ -431,7 +451,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn40q2_kernel(const vv_attn_pa
         }
     };
 
-    // ---- lane-constant LDS read addresses (byte offsets into a tile buffer; the key block / k step are instruction immediates)
+    // ---- lane-constant LDS read addresses (twice: as in attn40_kernel; byte offsets into a tile buffer; the key block / k step are instruction immediates)
     const int ka0 = r * PR + 16 * h;                             // K chunks h (s = 0) and 2 + h (s = 1: + 32)
     const int ka2 = h ? TILE : r * PR + 64;                     // s = 2: chunk 4 for h = 0, the constant chunk (1.0: slots 40..47) for h = 1
     // transposed V read: 16-lane group g = lane >> 4 (g & 1 = cb: which 16 columns, g >> 1 = h); lane 4 q + pp of the group addresses row q, columns 4 pp ..
@@ -442,38 +462,10 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn40q2_kernel(const vv_attn_pa
     const int va1 = vpp == 2 ? TILE : (16 * vcb + 4 * vq + h) * PR + 64 + 8 * (vpp & 1);
 
     // S^T = K Q^T for the 64 keys of the K tile at byte offset kb0 (2 key blocks x 3 k steps)
-    auto qk = [&](const unsigned char* sK, const int x, f32x16 (&sacc)[2]) {      // (the second block's fragment reads are the first block's: CSE'd)
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) sacc[kb][i] = 0.f;
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                const uint4 kf = s < 2 ? *(const uint4*)(sK + kb * 32 * PR + ka0 + 32 * s) : *(const uint4*)(sK + kb * 32 * PR + ka2);
-                sacc[kb] = Mfma32<T>::run(kf, qf[x][s], sacc[kb]);
-            }
-        }
-    };
-    auto mask_last = [&](f32x16 (&sacc)[2]) {                     // keys past Nkv of the ragged last tile: -inf scores (P = 0)
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-                if (kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h >= nlast) sacc[kb][i] = -1e30f;
-    };
-    auto row_max = [&](const f32x16 (&sacc)[2]) {
-        float mx = sacc[0][0];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) mx = fmaxf(mx, sacc[kb][i]);
-        return fmaxf(mx, __shfl_xor(mx, 32));
-    };
-    auto set_reference = [&](const int x, const float target) {   // pad slots 40, 41 of Q <- -target as the nearest h16 hi + lo pair
-        const unsigned short hi = T::from_f32(-target);
-        const unsigned short lo = T::from_f32(-target - T::to_f32(hi));
-        qf[x][2].x = h == 1 ? ((unsigned)hi | ((unsigned)lo << 16)) : qf[x][2].x;
-    };
+    auto qk = [&](const unsigned char* sK, const int x, f32x16 (&sacc)[2]) { a40_qk<T>(sK, qf[x][0], qf[x][1], qf[x][2], sacc, ka0, ka2); };      // (the second block's fragment reads are the first block's: CSE'd)
+    auto mask_last = [&](f32x16 (&sacc)[2]) { a40_mask_last(sacc, h, nlast); };
+    auto row_max = [&](const f32x16 (&sacc)[2]) { return a40_row_max(sacc); };
+    auto set_reference = [&](const int x, const float target) { qf[x][2].x = h == 1 ? a40_ref_slots<T>(target) : qf[x][2].x; };
 
     f32x16 oacc[QB];          // O^T rows 0..31 per query block (32x32x16 layout: lane = query, registers + h = d)
     f32x4 o2[QB][2];          // O^T rows 32..47 for the queries 0..15 / 16..31 of each block (16x16x32 layout)
@@ -522,39 +514,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn40q2_kernel(const vv_attn_pa
 #pragma unroll
             for (int x = 0; x < QB; ++x) { qk(cK, x, sc[x]); if (RAGGED && last) mask_last(sc[x]); }
 #pragma unroll
-            for (int x = 0; x < QB; ++x) {
-                uint4 pb[2][2];
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) sc[x][kb][i] = __builtin_amdgcn_exp2f(sc[x][kb][i]);
-#pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2)
-                        pb[kb][s2] = make_uint4(pack2<T>(sc[x][kb][8 * s2 + 0], sc[x][kb][8 * s2 + 1]), pack2<T>(sc[x][kb][8 * s2 + 2], sc[x][kb][8 * s2 + 3]),
-                                                pack2<T>(sc[x][kb][8 * s2 + 4], sc[x][kb][8 * s2 + 5]), pack2<T>(sc[x][kb][8 * s2 + 6], sc[x][kb][8 * s2 + 7]));
-                }
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2) {
-                        const int g0 = 16 * (2 * kb + s2) * PR;
-                        const uint2 lo = ds_read_tr16(cV + g0 + va0), hi = ds_read_tr16(cV + g0 + 2 * PR + va0);
-                        oacc[x] = Mfma32<T>::run(make_uint4(lo.x, lo.y, hi.x, hi.y), pb[kb][s2], oacc[x]);
-                    }
-                    uint4 pa, pq;
-                    {
-                        auto s0 = __builtin_amdgcn_permlane16_swap(pb[kb][0].x, pb[kb][1].x, false, false);
-                        auto s1 = __builtin_amdgcn_permlane16_swap(pb[kb][0].y, pb[kb][1].y, false, false);
-                        auto s2_ = __builtin_amdgcn_permlane16_swap(pb[kb][0].z, pb[kb][1].z, false, false);
-                        auto s3 = __builtin_amdgcn_permlane16_swap(pb[kb][0].w, pb[kb][1].w, false, false);
-                        pa = make_uint4(s0[0], s1[0], s2_[0], s3[0]);
-                        pq = make_uint4(s0[1], s1[1], s2_[1], s3[1]);
-                    }
-                    const uint2 lo = ds_read_tr16(cV + kb * 32 * PR + va1), hi = ds_read_tr16(cV + kb * 32 * PR + 2 * PR + va1);
-                    const uint4 vf = make_uint4(lo.x, lo.y, hi.x, hi.y);
-                    o2[x][0] = T::mfma(vf, pa, o2[x][0]); o2[x][1] = T::mfma(vf, pq, o2[x][1]);
-                }
-            }
+            for (int x = 0; x < QB; ++x) a40_pv<T>(cV, sc[x], oacc[x], o2[x], va0, va1);
         };
         // step `it`: tile `it` (K and V) has landed; issue tile it+1 into the other buffers
         auto step = [&](const int it, unsigned char* cK, unsigned char* cV, unsigned char* nK, unsigned char* nV) {
@@ -608,6 +568,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn40q2_kernel(const vv_attn_pa
             return;
         }
     }
+    // (twice: the direct store of attn40_kernel per query block; the same row stores aim at LDS above)
 #pragma unroll
     for (int x = 0; x < QB; ++x) {
         {
@@ -669,19 +630,11 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn80_kernel(const vv_attn_para
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int r = lane & 31, h = lane >> 5;
     int qt, hd, b;
-    {
-        const int nbh = p.B * p.heads;
-        const int full = (nbh / 8) * 8;
-        const int bid = blockIdx.x;
-        int bh;
-        if (bid < full * nqt) { const int xcd = bid & 7, idx = bid >> 3; bh = (idx / nqt) * 8 + xcd; qt = idx % nqt; }
-        else { const int rr = bid - full * nqt; bh = full + rr / nqt; qt = rr % nqt; }
-        hd = bh % p.heads; b = bh / p.heads;
-    }
-    const unsigned short* Q = (const unsigned short*)p.q + (int64_t)b * p.q_bs + (int64_t)hd * (p.q_hs ? p.q_hs : D);
-    const unsigned char* Kp = (const unsigned char*)((const unsigned short*)p.k + (int64_t)b * p.k_bs + (int64_t)hd * (p.k_hs ? p.k_hs : D));
-    const unsigned char* Vp = (const unsigned char*)((const unsigned short*)p.v + (int64_t)b * p.v_bs + (int64_t)hd * (p.v_hs ? p.v_hs : D));
-    unsigned short* O = (unsigned short*)p.o + (int64_t)b * p.o_bs + (int64_t)hd * (p.o_hs ? p.o_hs : D);
+    attn_block_decode(p, nqt, qt, hd, b);
+    const unsigned short* Q = (const unsigned short*)p.q + (int64_t)b * p.q_bs + (int64_t)hd * (p.q_hs ? p.q_hs : D);      // (written out: through attn_head_base the ragged instantiations move two scalar loads)
+    const unsigned char* Kp = (const unsigned char*)attn_head_base<D>(p.k, b, p.k_bs, hd, p.k_hs);
+    const unsigned char* Vp = (const unsigned char*)attn_head_base<D>(p.v, b, p.v_bs, hd, p.v_hs);
+    unsigned short* O = attn_head_base<D>(p.o, b, p.o_bs, hd, p.o_hs);
 
     // ---- Q fragments: lane (r, h) holds Q[q0 + 32 x + r][16 s + 8 h .. +7], s = 0..4
     const int q0 = qt * BQ + wave * 32 * QB;
@@ -876,12 +829,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn80_kernel(const vv_attn_para
                 const uint4 vf = make_uint4(lo.x, lo.y, hi.x, hi.y);
 #pragma unroll
                 for (int x = 0; x < QB; ++x) {
-                    auto s0 = __builtin_amdgcn_permlane16_swap(pb[x][0].x, pb[x][1].x, false, false);
-                    auto s1 = __builtin_amdgcn_permlane16_swap(pb[x][0].y, pb[x][1].y, false, false);
-                    auto s2_ = __builtin_amdgcn_permlane16_swap(pb[x][0].z, pb[x][1].z, false, false);
-                    auto s3 = __builtin_amdgcn_permlane16_swap(pb[x][0].w, pb[x][1].w, false, false);
-                    const uint4 pa = make_uint4(s0[0], s1[0], s2_[0], s3[0]);
-                    const uint4 pq = make_uint4(s0[1], s1[1], s2_[1], s3[1]);
+                    uint4 pa, pq;
+                    a32_swap16(pb[x][0], pb[x][1], pa, pq);
                     o2[x][0] = T::mfma(vf, pa, o2[x][0]); o2[x][1] = T::mfma(vf, pq, o2[x][1]);
                 }
             }
@@ -945,40 +894,15 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn80_kernel(const vv_attn_para
     }
 }
 
-template <typename T, int NW, int OCC>
-int attn80_launch(const vv_attn_params& p, hipStream_t st) {
-    constexpr int BQ = NW * 64;
-    const int nqt = (p.Nq + BQ - 1) / BQ;
-    const int64_t nblk = (int64_t)p.B * p.heads * nqt;
-    if (nblk > 0x7fffffff) VV_FAIL(VV_E_ARG, "vv_attention: grid too large");
-    if (p.Nkv % 64) hipLaunchKernelGGL((attn80_kernel<T, NW, OCC, true>), dim3((unsigned)nblk), dim3(NW * 64), 0, st, p, nqt);
-    else hipLaunchKernelGGL((attn80_kernel<T, NW, OCC, false>), dim3((unsigned)nblk), dim3(NW * 64), 0, st, p, nqt);
-    VV_CHECK_LAUNCH("vv_attention(d80, 64 queries per wave)");
-    return VV_OK;
-}
-
-template <typename T, int NW, int OCC>
-int attn40q2_launch(const vv_attn_params& p, hipStream_t st) {
-    constexpr int BQ = NW * 64;
-    const int nqt = (p.Nq + BQ - 1) / BQ;
-    const int64_t nblk = (int64_t)p.B * p.heads * nqt;
-    if (nblk > 0x7fffffff) VV_FAIL(VV_E_ARG, "vv_attention: grid too large");
-    if (p.Nkv % 64) hipLaunchKernelGGL((attn40q2_kernel<T, NW, OCC, true>), dim3((unsigned)nblk), dim3(NW * 64), 0, st, p, nqt);
-    else hipLaunchKernelGGL((attn40q2_kernel<T, NW, OCC, false>), dim3((unsigned)nblk), dim3(NW * 64), 0, st, p, nqt);
-    VV_CHECK_LAUNCH("vv_attention(d40, 64 queries per wave)");
-    return VV_OK;
-}
-
-template <typename T, int NW, int OCC>
+// four waves per block; d = 40: 64 queries per wave at 2 waves per SIMD on long sequences, 32 queries at 3 waves per SIMD below 1024
+template <typename T>
 int attn40_launch(const vv_attn_params& p, hipStream_t st) {
-    constexpr int BQ = NW * 32;
-    const int nqt = (p.Nq + BQ - 1) / BQ;
-    const int64_t nblk = (int64_t)p.B * p.heads * nqt;
-    if (nblk > 0x7fffffff) VV_FAIL(VV_E_ARG, "vv_attention: grid too large");
-    if (p.Nkv % 64) hipLaunchKernelGGL((attn40_kernel<T, NW, OCC, true>), dim3((unsigned)nblk), dim3(NW * 64), 0, st, p, nqt);
-    else hipLaunchKernelGGL((attn40_kernel<T, NW, OCC, false>), dim3((unsigned)nblk), dim3(NW * 64), 0, st, p, nqt);
-    VV_CHECK_LAUNCH("vv_attention(d40, 32x32x16)");
-    return VV_OK;
+    if (p.Nq >= 1024) return a32_launch<4, 256>(attn40q2_kernel<T, 4, 2, true>, attn40q2_kernel<T, 4, 2, false>, p, st, "vv_attention(d40, 64 queries per wave)");
+    return a32_launch<4, 128>(attn40_kernel<T, 4, 3, true>, attn40_kernel<T, 4, 3, false>, p, st, "vv_attention(d40, 32x32x16)");
+}
+template <typename T>
+int attn80_launch(const vv_attn_params& p, hipStream_t st) {
+    return a32_launch<4, 256>(attn80_kernel<T, 4, 2, true>, attn80_kernel<T, 4, 2, false>, p, st, "vv_attention(d80, 64 queries per wave)");
 }
 
 }  // namespace
@@ -991,10 +915,7 @@ extern "C" int vv_attention_mfma32(const vv_attn_params* pp, int dtype, void* st
     hipStream_t st = (hipStream_t)stream;
     const bool cross = p.Nkv < 128 && p.Nq != p.Nkv;
     if ((p.Nq <= 32 && p.Nkv <= 32) || cross || p.Nkv < 64) return -1000;
-    if (p.D == 40) {
-        if (dtype == VV_BF16) return p.Nq >= 1024 ? attn40q2_launch<BF16, 4, 2>(p, st) : attn40_launch<BF16, 4, 3>(p, st);
-        return p.Nq >= 1024 ? attn40q2_launch<F16, 4, 2>(p, st) : attn40_launch<F16, 4, 3>(p, st);
-    }
-    if (p.D == 80 && p.Nq >= 512) return dtype == VV_BF16 ? attn80_launch<BF16, 4, 2>(p, st) : attn80_launch<F16, 4, 2>(p, st);
+    if (p.D == 40) return dtype == VV_BF16 ? attn40_launch<BF16>(p, st) : attn40_launch<F16>(p, st);
+    if (p.D == 80 && p.Nq >= 512) return dtype == VV_BF16 ? attn80_launch<BF16>(p, st) : attn80_launch<F16>(p, st);
     return -1000;
 }

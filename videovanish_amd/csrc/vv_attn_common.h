@@ -1,27 +1,25 @@
-// LDS / LDS-DMA helpers shared by the attention translation units (vv_attn.hip, vv_attn32.hip).
+// Shared by the attention translation units (vv_attn.hip, vv_attn32.hip): which (batch, head, query tile) a block works on and where its tensors start.
 #pragma once
-#include "vv_common.h"
+#include "vv_lds_dma.h"
 
 namespace {
 
-__device__ __forceinline__ uint2 ds_read_tr16(const unsigned char* lds_ptr) {
-    typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_p;
-    s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)lds_ptr);
-    return __builtin_bit_cast(uint2, v);
+// XCD-aware decode: blocks i and i+8 share an XCD (and its L2).  Give every XCD its own (batch, head) pairs and walk
+// that pair's query tiles on it, so the pair's K/V (re-read by every query tile) stays resident in ONE 4 MiB L2.
+__device__ __forceinline__ void attn_block_decode(const vv_attn_params& p, const int nqt, int& qt, int& hd, int& b) {
+    const int nbh = p.B * p.heads;
+    const int full = (nbh / 8) * 8;                       // pairs handled in XCD-striped rounds of 8
+    const int bid = blockIdx.x;
+    int bh;
+    if (bid < full * nqt) { const int xcd = bid & 7, idx = bid >> 3; bh = (idx / nqt) * 8 + xcd; qt = idx % nqt; }
+    else { const int r = bid - full * nqt; bh = full + r / nqt; qt = r % nqt; }
+    hd = bh % p.heads; b = bh / p.heads;
 }
 
-__device__ __forceinline__ void glds16(const void* gptr, void* lds_wave_base) {
-    typedef const void __attribute__((address_space(1))) * gp_t;
-    typedef void __attribute__((address_space(3))) * lp_t;
-    __builtin_amdgcn_global_load_lds((gp_t)gptr, (lp_t)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ void glds16_asm(const void* gptr, void* lds_wave_base) {
-    typedef void __attribute__((address_space(3))) * lp_t;
-    const unsigned dst = (unsigned)(size_t)(lp_t)lds_wave_base;
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gptr), "s"(dst) : "memory");
+// where (batch b, head hd) of a q / k / v / o tensor starts, in elements; a head stride of 0 = heads side by side inside a row (D apart)
+template <int D>
+__device__ __forceinline__ unsigned short* attn_head_base(const void* base, const int b, const int64_t bs, const int hd, const int64_t hs) {
+    return (unsigned short*)base + (int64_t)b * bs + (int64_t)hd * (hs ? hs : D);
 }
 
 }  // namespace

@@ -1,15 +1,6 @@
 // Shared by the slab-streaming fused kernels (vv_motion.hip, vv_chain.hip): the LDS-DMA copy of the weight ring and the GELU of the GEGLU feed-forward.
 #pragma once
-#include "vv_common.h"
-
-// one 16-byte LDS-DMA per lane: 1 KB per wave from gptr (per lane) to lds_wave_base + 16 lane (m0 holds the wave's LDS base for the instruction)
-__device__ __forceinline__ void glds16_asm(const void* gptr, void* lds_wave_base) {
-    typedef void __attribute__((address_space(3))) * lp_t;
-    const unsigned dst = (unsigned)(size_t)(lp_t)lds_wave_base;
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gptr), "s"(dst) : "memory");
-}
+#include "vv_lds_dma.h"
 
 // exact (erf) GELU through Abramowitz-Stegun 7.1.26 (|erf error| <= 1.5e-7, far below the h16 rounding that follows): 2 transcendentals
 // + ~12 VALU instead of the ~30 of erff -- with ONE wave per SIMD the activation is not hidden behind another wave's MFMAs

@@ -15,7 +15,7 @@
 // of one output row: the epilogue (bias, time-embedding vector, residuals, GEGLU, cast) is 16-byte vectorised.
 // The block index is remapped so that the column tiles of one row panel run on the same XCD (shared L2).
 #include <type_traits>
-#include "vv_common.h"
+#include "vv_lds_dma.h"
 #include "vv_gemm_epilogue.h"
 
 extern "C" int vv_gemm256_route(const vv_conv_params* pp, int force);
@@ -28,12 +28,6 @@ enum { MODE_H16 = 0, MODE_F32 = 1, MODE_FAST = 2, MODE_FAST32 = 3, MODE_HALO = 4
 constexpr int HALO_PX = 184;   // (8+2) x (16+2) = 180 halo pixels of an 8x16 output patch, padded to whole 1 KB DMA blocks
 
 __device__ __attribute__((aligned(64))) const unsigned int g_zero_page[16] = {0};
-
-__device__ __forceinline__ void glds16(const void* gptr, void* lds_wave_base) {
-    typedef const void __attribute__((address_space(1))) * gp_t;
-    typedef void __attribute__((address_space(3))) * lp_t;
-    __builtin_amdgcn_global_load_lds((gp_t)gptr, (lp_t)lds_wave_base, 16, 0, 0);
-}
 
 template <typename T, int WR, int WC, int MT, int NT, int MODE, int OCCW = 2, bool GN = false>
 __global__ __launch_bounds__(256, OCCW) void conv_gemm_kernel(const vv_conv_params p, const int M, const int tilesM, const int tilesN) {

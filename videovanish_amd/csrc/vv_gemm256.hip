@@ -16,7 +16,7 @@
 //   LIN  : plain [M][K] h16 matrix (linear layers, 1x1 stride-1 convs)
 //   CONV : im2col gather, <= 9 taps, stride 1/2, zero padding, two-source channel concat, no fused resize; per row only the
 //          pixel index of tap (0,0) and a tap-validity bit mask are kept (out-of-image taps read a zero page)
-#include "vv_common.h"
+#include "vv_lds_dma.h"
 #include "vv_gemm_epilogue.h"
 
 namespace {
@@ -24,12 +24,6 @@ namespace {
 enum { G256_LIN = 0, G256_CONV = 1 };
 
 __device__ __attribute__((aligned(64))) const unsigned int g256_zero_page[16] = {0};
-
-__device__ __forceinline__ void glds16(const void* gptr, void* lds_wave_base) {
-    typedef const void __attribute__((address_space(1))) * gp_t;
-    typedef void __attribute__((address_space(3))) * lp_t;
-    __builtin_amdgcn_global_load_lds((gp_t)gptr, (lp_t)lds_wave_base, 16, 0, 0);
-}
 
 template <typename T, int NT, int MODE>
 __global__ __launch_bounds__(512, 2) void gemm256_kernel(const vv_conv_params p, const int M, const int tilesM, const int tilesN) {
@@ -178,17 +172,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const vv_conv_params p,
 //     waits until all but the 3 newest have landed (vmcnt(6): 2 DMA instructions per half tile and wave), so S[g+1], S[g+2] -- what
 //     phase g+1 reads -- are retired one barrier before they are read, and 3 half tiles stay in flight across the barriers.
 //   * 8 LDS slots (2 k tiles x 4 half tiles) in distinct __shared__ arrays, k loop unrolled by two so every slot is static.
-// LDS-DMA issued from inline asm: hipcc does not see the LDS write, so it inserts no conservative vmcnt(0) before the ds_reads at
-// the loop head (it cannot count DMA instructions across the back edge); every wait is the hand-placed counted one.
-// M0 = wave-uniform LDS destination, written in the same statement that reads it (cdna_hip_programming.md 5.7).
-__device__ __forceinline__ void glds16_asm(const void* gptr, void* lds_wave_base) {
-    typedef void __attribute__((address_space(3))) * lp_t;
-    const unsigned dst = (unsigned)(size_t)(lp_t)lds_wave_base;
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gptr), "s"(dst) : "memory");
-}
-
+// LDS-DMA issued from inline asm (glds16_asm, vv_lds_dma.h): hipcc does not see the LDS write, so it inserts no conservative vmcnt(0) before the
+// ds_reads at the loop head (it cannot count DMA instructions across the back edge); every wait is the hand-placed counted one.
 template <typename T, int MODE, bool ASMDMA>
 __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const vv_conv_params p, const int M, const int tilesM, const int tilesN) {
     constexpr int MT = 8, NT = 4;
