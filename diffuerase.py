@@ -5,7 +5,8 @@ with the hot path running on hand-written gfx950 HIP kernels (videovanish_amd/) 
 Extra keyword-only knobs (old callers are unaffected): num_inference_steps, scheduler, chunk, overlap, dtype, seed,
 compat_reference_early_return, roi (mask-region inference: videovanish_amd/roi.py; also configure(roi=...) and $VV_ROI), spans / cuts (mask-span
 inference: only the runs of masked frames are processed, and nothing crosses a hard cut: videovanish_amd/spans.py; also configure(spans=...) and
-$VV_SPANS).  There is no CPU fallback: without the HIP extension / a GPU this raises.
+$VV_SPANS), mask_clean (mask clean-up between the dilation and the planners: speckles dropped, dropouts bridged, the mask grown in time:
+videovanish_amd/maskclean.py; also configure(mask_clean=...) and $VV_MASK_CLEAN).  There is no CPU fallback: without the HIP extension / a GPU this raises.
 
 This file is the boundary: the reference's names and module state, the settings, and the stages (weights, prior, model) that read that state.
 What a call does with them -- spans, windows, crop -> prior -> model, resize / paste / composite -- is videovanish_amd/infill.py.
@@ -17,6 +18,7 @@ import numpy as np
 import torch
 
 from videovanish_amd import hip, infill
+from videovanish_amd import maskclean
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
 from videovanish_amd.config import RunConfig
@@ -36,9 +38,12 @@ _weights = None         # configure(weights=...) / $VV_WEIGHTS_DIR: a local mode
 _loaded = None          # (CheckpointWeights, prior stages) resolved from _weights, cached until configure() is called again
 _roi = None             # configure(roi=...): mask-region inference for calls that do not pass roi= themselves
 _spans = None           # configure(spans=...): mask-span inference for calls that do not pass spans= themselves
+_mask_clean = None      # configure(mask_clean=...): mask clean-up for calls that do not pass mask_clean= themselves
+last_mask_clean = None  # the infill.MaskCleanReport of the last run_infill_on_frames call; None when the stage did not run
 
 
-def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None):
+def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
+              mask_clean=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -54,8 +59,11 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     (independent 32 / 8 chunks that shard over GPUs; RAFT + propagation only).  `run` / `prior` given explicitly still win field by field.
     roi = None / "static" / "follow" / "static-regions" / "follow-regions" / a roi.RoiConfig: mask-region inference for calls that do not pass
     roi= (run_infill_on_frames).
-    spans = None / "masked" / "cuts" / "masked-cuts" / a spans.SpanConfig: mask-span inference for calls that do not pass spans=."""
-    global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi, _spans
+    spans = None / "masked" / "cuts" / "masked-cuts" / a spans.SpanConfig: mask-span inference for calls that do not pass spans=.
+    mask_clean = None / "on" / "area=64,bridge=2,grow=1" (any subset) / a maskclean.MaskCleanConfig: mask clean-up for calls that do not pass
+    mask_clean=."""
+    global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi, _spans, _mask_clean
+    maskclean.as_config(mask_clean)
     span_plan.as_config(spans)
     roi_plan.as_config(roi)                 # validated now, kept as given: configure(roi="off") means the full frame whatever $VV_ROI says
     if reference_defaults:
@@ -67,6 +75,7 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     _weights, _loaded = weights, None
     _roi = roi
     _spans = spans
+    _mask_clean = mask_clean
 
 
 def _resolve_weights(ckpt):
@@ -115,9 +124,20 @@ def spans_config(spans=None, cuts=None):
     return cfg
 
 
+def mask_clean_config(mask_clean=None):
+    """The mask clean-up setting a call runs with: its own mask_clean= argument, else configure(mask_clean=...), else $VV_MASK_CLEAN (on | off |
+    area=N,bridge=N,grow=N).  None = no clean-up.  mask_clean="off" (or False) asks for none whatever configure() or the environment say."""
+    if mask_clean is not None:
+        return maskclean.as_config(mask_clean)
+    if _mask_clean is not None:
+        return maskclean.as_config(_mask_clean)
+    return maskclean.as_config(os.environ.get("VV_MASK_CLEAN"))
+
+
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
-                         *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None):
+                         *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
+                         mask_clean=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -127,18 +147,35 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     (spans.plan_spans): at hard cuts (cuts=[...] frame indices, or found on the device: "cuts", "masked-cuts"), and in "masked" mode into spans
     around the runs of masked frames only.  Each span is this call on frames[a:b] (its own roi windows, chunks and lanes); frames outside every
     span are returned as the original arrays, also with keep_unmasked_original=False.  A clip without a mask pixel returns its input and loads
-    no model; one span that is the whole clip is the plain call."""
+    no model; one span that is the whole clip is the plain call.
+    mask_clean (mask clean-up, opt-in): "on" / "area=64,bridge=2,grow=1" / a videovanish_amd.maskclean.MaskCleanConfig cleans the dilated masks
+    on the device before anything reads them (infill.clean_masks): components holding fewer than min_area raw mask pixels are cleared, dropouts
+    of at most `bridge` frames are filled per pixel, the mask is held `grow` frames longer at both ends; the temporal steps stay inside the
+    segments between the cuts of spans= / cuts= (found on the despeckled masks when they are "auto").  The result replaces the dilated masks
+    for the span and window planners, the prior, the model and the composite; what it changed is kept in last_mask_clean.  Masks that need
+    nothing give the bytes of the call without it."""
+    global last_mask_clean
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
+    ccfg = mask_clean_config(mask_clean)
+    last_mask_clean = None
     if rcfg is not None and compat_reference_early_return:
         raise ValueError("roi= (mask-region inference) cannot be combined with compat_reference_early_return=True")
     if scfg is not None and compat_reference_early_return:
         raise ValueError("spans= (mask-span inference) cannot be combined with compat_reference_early_return=True")
+    if ccfg is not None and compat_reference_early_return:
+        raise ValueError("mask_clean= (mask clean-up) cannot be combined with compat_reference_early_return=True")
 
     if prog is not None: prog(5, "dilating frames")
     dev = get_device()
     m = torch.from_numpy(np.stack([mm if mm.ndim == 3 else mm[..., None] for mm in mask_frames])).to(dev)
     dil_t = hip.mask_collapse_dilate(m.contiguous(), mask_dilation_iter)       # reference :27-31
+    if ccfg is not None:
+        find = None if scfg is None else (lambda despeckled: infill.clip_cuts(frames_rgb, despeckled, scfg))
+        dil_t, last_mask_clean = infill.clean_masks(m.contiguous(), dil_t, ccfg, find)
+        if scfg is not None and scfg.cuts == "auto":        # the detector has run, on the despeckled masks: the span plan takes its cuts
+            import dataclasses
+            scfg = dataclasses.replace(scfg, cuts=last_mask_clean.cuts)
 
     stages = infill.Stages(lambda: _load_model(dev, ckpt), _load_prior, _run_prior,
                            lambda f, d, prior, p: _run_model(f, d, prior, max_img_size, p, num_inference_steps, scheduler))
@@ -198,6 +235,16 @@ def _frame_io():
     return frameio
 
 
+def _mask_clean_arg(text):
+    """--mask-clean's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --roi / --spans)."""
+    try:
+        if maskclean.as_config(text) is None:
+            raise ValueError("not a setting")
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return text
+
+
 # =============================
 # CLI entry point (reference diffuerase.py:121-155)
 # =============================
@@ -217,6 +264,10 @@ def main():
     ap.add_argument("--spans", choices=span_plan.SPELLINGS, default=None,
                     help="Mask-span inference: masked = process only the frame runs that have a mask (with some context), the other frames stay "
                          "the original ones; cuts = process every frame but split the clip at hard cuts found in the video; masked-cuts = both.")
+    ap.add_argument("--mask-clean", type=_mask_clean_arg, default=None, metavar="on|area=64,bridge=2,grow=1",
+                    help="Mask clean-up before anything reads the masks: drop components of the dilated mask that hold fewer than `area` mask pixels "
+                         "(on: four cells of a 256 x 256 grid at the clip's size), fill dropouts of at most `bridge` frames (on: 2), hold the mask "
+                         "`grow` frames longer at both ends (on: 0).  Prints one line with what it changed.")
     ap.add_argument("--cuts", type=span_plan.parse_cuts, default=None, metavar="120,431",
                     help="Frame indices (relative to --start_frame) where a new shot begins: used instead of the detector.")
     args = ap.parse_args()
@@ -236,7 +287,12 @@ def main():
     kw = {"roi": args.roi} if args.roi is not None else {}      # pass roi= / spans= / cuts= only when asked for: a default call stays the reference's call
     if args.spans is not None: kw["spans"] = args.spans
     if args.cuts is not None: kw["cuts"] = args.cuts
+    if args.mask_clean is not None: kw["mask_clean"] = args.mask_clean
     out_frames = run_infill_on_frames(frames, mask_frames, propainer_frames=prior_frames, **kw)
+    if args.mask_clean is not None and last_mask_clean is not None:
+        r = last_mask_clean
+        print(f"mask clean-up: {int(r.removed.sum())} components ({int(r.cleared.sum())} px) cleared in {int((r.removed > 0).sum())} frames, "
+              f"{int(r.bridged.sum())} px bridged in {int((r.bridged > 0).sum())} frames, {int(r.grown.sum())} px grown in {int((r.grown > 0).sum())} frames")
     tools.write_video_frames_to_path(out_video, out_frames, fps, H0, W0)
 
 

@@ -1,13 +1,13 @@
-"""The orchestration of one diffuerase.run_infill_on_frames call after the dilation: the temporal plan (span_plan, run_spans), and for each
-clip the windows (region_plans, run_clip), ONE crop -> prior -> model sequence (run_windows) and ONE closing step (finish).  The full frame is
+"""The orchestration of one diffuerase.run_infill_on_frames call after the dilation: the mask clean-up (clean_masks), the temporal plan
+(span_plan, run_spans), and for each clip the windows (region_plans, run_clip), ONE crop -> prior -> model sequence (run_windows) and ONE closing step (finish).  The full frame is
 no window, roi= "static" / "follow" one, the "-regions" spellings several.  The stages (weights, prior, model) come from the caller as a Stages
-record; nothing here is module state.  Rules and reasons: DESIGN.md §10, §11."""
+record; nothing here is module state.  Rules and reasons: DESIGN.md §10, §11, §12."""
 from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
 
-from . import hip, spans_hip
+from . import hip, mask_hip, spans_hip
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -34,20 +34,58 @@ def _share(prog, what, k, n, lo, hi):
     return cb
 
 
+# ---- masks: what the planners and the model see -----------------------------------------------------------------------------------------------
+class MaskCleanReport(NamedTuple):
+    """What clean_masks changed, per frame (int64 [T] each), and the cuts its temporal steps respected."""
+    removed: np.ndarray     # components cleared by the despeckle
+    cleared: np.ndarray     # pixels of the dilated mask cleared with them
+    bridged: np.ndarray     # pixels set by the bridge
+    grown: np.ndarray       # pixels set by the grow
+    cuts: tuple
+
+
+def clean_masks(m, dil_t, ccfg, cuts=None):
+    """The mask clean-up (maskclean.py) on the device: m = the raw masks [T,H,W,ch] u8, dil_t = their dilation [T,H,W] u8, ccfg = a
+    MaskCleanConfig, cuts = frame indices, None (one segment) or a callable that finds them on the despeckled masks (the detector must not see the
+    speckles).  Despeckle, then bridge and grow inside every segment of spans.segments.  Returns (the masks that replace dil_t, MaskCleanReport).
+    Depends on nothing but its arguments: every rank gets the same masks.  A step that is switched off launches nothing."""
+    T, H, W = dil_t.shape
+    counts = np.zeros((T, 4), np.int64)
+    area = ccfg.area_for(H, W)
+    if area > 1:
+        dil_t, c = mask_hip.despeckle(dil_t, m, area)
+        counts[:, :2] = c.cpu().numpy()
+    cuts = tuple(int(c) for c in ((cuts(dil_t) if callable(cuts) else cuts) or ()))
+    if ccfg.bridge or ccfg.grow:
+        out = torch.empty_like(dil_t)
+        c = torch.empty((T, 2), dtype=torch.int64, device=dil_t.device)
+        for s, e in span_planner.segments(T, cuts):
+            mask_hip.time_bridge_grow(dil_t[s:e], ccfg.bridge, ccfg.grow, out=out[s:e], counts=c[s:e])
+        dil_t = out
+        counts[:, 2:] = c.cpu().numpy()
+    return dil_t, MaskCleanReport(*(counts[:, k].copy() for k in range(4)), cuts)
+
+
 # ---- spans: the clip in time --------------------------------------------------------------------------------------------------------------
+def clip_cuts(frames_rgb, dil_t, scfg):
+    """The cuts a span setting asks for: its explicit frame indices, with cuts="auto" those spans.find_cuts reads from the device's pair
+    statistics (every frame crosses to the device once for that), else None."""
+    if isinstance(scfg.cuts, tuple):
+        return list(scfg.cuts)
+    if scfg.cuts != "auto":
+        return None
+    if len(frames_rgb) < 2:
+        return []
+    H0, W0 = frames_rgb[0].shape[:2]
+    sad, n, hist = spans_hip.frame_pair_stats(frames_rgb, dil_t)
+    return span_planner.find_cuts(sad, n, hist, scfg, npix=H0 * W0)
+
+
 def span_plan(frames_rgb, dil_t, scfg):
-    """spans.plan_spans for the dilated masks: the per-frame masked flags from mask_bbox (an empty box = unmasked) and, with cuts="auto", the cuts
-    spans.find_cuts reads from the device's pair statistics (every frame crosses to the device once for that)."""
+    """spans.plan_spans for the dilated masks: the per-frame masked flags from mask_bbox (an empty box = unmasked) and the cuts of clip_cuts."""
     bb = hip.mask_bbox(dil_t).cpu().numpy()
     masked = (bb[:, 2] > bb[:, 0]) & (bb[:, 3] > bb[:, 1])
-    cuts = None
-    if scfg.cuts == "auto":
-        cuts = []
-        if len(frames_rgb) >= 2:
-            H0, W0 = frames_rgb[0].shape[:2]
-            sad, n, hist = spans_hip.frame_pair_stats(frames_rgb, dil_t)
-            cuts = span_planner.find_cuts(sad, n, hist, scfg, npix=H0 * W0)
-    return span_planner.plan_spans(masked, cuts, scfg)
+    return span_planner.plan_spans(masked, clip_cuts(frames_rgb, dil_t, scfg), scfg)
 
 
 def _span_progress(prog, n):
