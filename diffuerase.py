@@ -6,7 +6,9 @@ Extra keyword-only knobs (old callers are unaffected): num_inference_steps, sche
 compat_reference_early_return, roi (mask-region inference: videovanish_amd/roi.py; also configure(roi=...) and $VV_ROI), spans / cuts (mask-span
 inference: only the runs of masked frames are processed, and nothing crosses a hard cut: videovanish_amd/spans.py; also configure(spans=...) and
 $VV_SPANS), mask_clean (mask clean-up between the dilation and the planners: speckles dropped, dropouts bridged, the mask grown in time:
-videovanish_amd/maskclean.py; also configure(mask_clean=...) and $VV_MASK_CLEAN).  There is no CPU fallback: without the HIP extension / a GPU this raises.
+videovanish_amd/maskclean.py; also configure(mask_clean=...) and $VV_MASK_CLEAN), tone_match (seam tone matching: the model's pixels are fitted to
+the ring of unmasked pixels round the mask before the composite: videovanish_amd/tonematch.py; also configure(tone_match=...) and $VV_TONE_MATCH).
+There is no CPU fallback: without the HIP extension / a GPU this raises.
 
 This file is the boundary: the reference's names and module state, the settings, and the stages (weights, prior, model) that read that state.
 What a call does with them -- spans, windows, crop -> prior -> model, resize / paste / composite -- is videovanish_amd/infill.py.
@@ -18,7 +20,7 @@ import numpy as np
 import torch
 
 from videovanish_amd import hip, infill
-from videovanish_amd import maskclean
+from videovanish_amd import maskclean, tonematch
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
 from videovanish_amd.config import RunConfig
@@ -40,10 +42,12 @@ _roi = None             # configure(roi=...): mask-region inference for calls th
 _spans = None           # configure(spans=...): mask-span inference for calls that do not pass spans= themselves
 _mask_clean = None      # configure(mask_clean=...): mask clean-up for calls that do not pass mask_clean= themselves
 last_mask_clean = None  # the infill.MaskCleanReport of the last run_infill_on_frames call; None when the stage did not run
+_tone_match = None      # configure(tone_match=...): seam tone matching for calls that do not pass tone_match= themselves
+last_tone_match = None  # the infill.ToneMatchReport of the last run_infill_on_frames call; None when the stage did not run
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
-              mask_clean=None):
+              mask_clean=None, tone_match=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -61,8 +65,11 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     roi= (run_infill_on_frames).
     spans = None / "masked" / "cuts" / "masked-cuts" / a spans.SpanConfig: mask-span inference for calls that do not pass spans=.
     mask_clean = None / "on" / "area=64,bridge=2,grow=1" (any subset) / a maskclean.MaskCleanConfig: mask clean-up for calls that do not pass
-    mask_clean=."""
-    global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi, _spans, _mask_clean
+    mask_clean=.
+    tone_match = None / "on" / "affine" / "offset" / "mode=offset,ring=8,smooth=0" (any subset) / a tonematch.ToneMatchConfig: seam tone matching
+    for calls that do not pass tone_match=."""
+    global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi, _spans, _mask_clean, _tone_match
+    tonematch.as_config(tone_match)
     maskclean.as_config(mask_clean)
     span_plan.as_config(spans)
     roi_plan.as_config(roi)                 # validated now, kept as given: configure(roi="off") means the full frame whatever $VV_ROI says
@@ -76,6 +83,7 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     _roi = roi
     _spans = spans
     _mask_clean = mask_clean
+    _tone_match = tone_match
 
 
 def _resolve_weights(ckpt):
@@ -134,10 +142,21 @@ def mask_clean_config(mask_clean=None):
     return maskclean.as_config(os.environ.get("VV_MASK_CLEAN"))
 
 
+def tone_match_config(tone_match=None):
+    """The seam tone matching setting a call runs with: its own tone_match= argument, else configure(tone_match=...), else $VV_TONE_MATCH (on |
+    affine | offset | off | mode=..,ring=N,..).  None = no tone matching.  tone_match="off" (or False) asks for none whatever configure() or the
+    environment say."""
+    if tone_match is not None:
+        return tonematch.as_config(tone_match)
+    if _tone_match is not None:
+        return tonematch.as_config(_tone_match)
+    return tonematch.as_config(os.environ.get("VV_TONE_MATCH"))
+
+
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
-                         mask_clean=None):
+                         mask_clean=None, tone_match=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -153,18 +172,26 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     of at most `bridge` frames are filled per pixel, the mask is held `grow` frames longer at both ends; the temporal steps stay inside the
     segments between the cuts of spans= / cuts= (found on the despeckled masks when they are "auto").  The result replaces the dilated masks
     for the span and window planners, the prior, the model and the composite; what it changed is kept in last_mask_clean.  Masks that need
-    nothing give the bytes of the call without it."""
-    global last_mask_clean
+    nothing give the bytes of the call without it.
+    tone_match (seam tone matching, opt-in): "on" / "affine" / "offset" / "mode=offset,ring=8,smooth=0" / a videovanish_amd.tonematch.ToneMatchConfig
+    fits, per frame and channel, the model's pixels to the original ones over the ring of unmasked pixels round the mask (a gain and an offset,
+    pooled over neighbouring frames, clamped) and sends every pasted pixel through the resulting table before the feathered composite
+    (infill.finish), for the full frame and for every roi window, inside each span.  What it applied is kept in last_tone_match.  A model frame
+    that equals the original on the ring gives the bytes of the call without it."""
+    global last_mask_clean, last_tone_match
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
     ccfg = mask_clean_config(mask_clean)
-    last_mask_clean = None
+    tcfg = tone_match_config(tone_match)
+    last_mask_clean = last_tone_match = None
     if rcfg is not None and compat_reference_early_return:
         raise ValueError("roi= (mask-region inference) cannot be combined with compat_reference_early_return=True")
     if scfg is not None and compat_reference_early_return:
         raise ValueError("spans= (mask-span inference) cannot be combined with compat_reference_early_return=True")
     if ccfg is not None and compat_reference_early_return:
         raise ValueError("mask_clean= (mask clean-up) cannot be combined with compat_reference_early_return=True")
+    if tcfg is not None and compat_reference_early_return:
+        raise ValueError("tone_match= (seam tone matching) cannot be combined with compat_reference_early_return=True")
 
     if prog is not None: prog(5, "dilating frames")
     dev = get_device()
@@ -180,12 +207,22 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     stages = infill.Stages(lambda: _load_model(dev, ckpt), _load_prior, _run_prior,
                            lambda f, d, prior, p: _run_model(f, d, prior, max_img_size, p, num_inference_steps, scheduler))
 
-    def body(frames, dil, prior, p):
-        return infill.run_clip(frames, dil, prior, rcfg, stages, p, dev, feather_px, keep_unmasked_original, compat_reference_early_return)
+    tone_parts = None if tcfg is None else []       # one report per clip call, in the order of the spans
 
+    def body(frames, dil, prior, p):
+        return infill.run_clip(frames, dil, prior, rcfg, stages, p, dev, feather_px, keep_unmasked_original, compat_reference_early_return,
+                               tone=tcfg, tone_out=tone_parts)
+
+    T = len(frames_rgb)
     if scfg is None:
-        return body(frames_rgb, dil_t, propainer_frames, prog)
-    return infill.run_spans(frames_rgb, dil_t, propainer_frames, infill.span_plan(frames_rgb, dil_t, scfg), body, prog, load=stages.load_model)
+        plan = [(0, T)]
+        out = body(frames_rgb, dil_t, propainer_frames, prog)
+    else:
+        plan = infill.span_plan(frames_rgb, dil_t, scfg)
+        out = infill.run_spans(frames_rgb, dil_t, propainer_frames, plan, body, prog, load=stages.load_model)
+    if tcfg is not None:
+        last_tone_match = infill.tone_report(tone_parts, plan, T)
+    return out
 
 
 def _load_model(dev, ckpt):
@@ -235,6 +272,16 @@ def _frame_io():
     return frameio
 
 
+def _tone_match_arg(text):
+    """--tone-match's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --mask-clean)."""
+    try:
+        if tonematch.as_config(text) is None:
+            raise ValueError("not a setting")
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return text
+
+
 def _mask_clean_arg(text):
     """--mask-clean's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --roi / --spans)."""
     try:
@@ -268,6 +315,10 @@ def main():
                     help="Mask clean-up before anything reads the masks: drop components of the dilated mask that hold fewer than `area` mask pixels "
                          "(on: four cells of a 256 x 256 grid at the clip's size), fill dropouts of at most `bridge` frames (on: 2), hold the mask "
                          "`grow` frames longer at both ends (on: 0).  Prints one line with what it changed.")
+    ap.add_argument("--tone-match", type=_tone_match_arg, default=None, metavar="on|affine|offset|mode=offset,ring=8,smooth=0",
+                    help="Seam tone matching before the composite: per frame and channel, fit the model's pixels to the original ones over the ring of "
+                         "unmasked pixels within `ring` px of the mask (on: a gain and an offset, ring 12, pooled over 2 frames either side; offset: "
+                         "an offset only) and correct every pasted pixel with it.  Prints one line with what it applied.")
     ap.add_argument("--cuts", type=span_plan.parse_cuts, default=None, metavar="120,431",
                     help="Frame indices (relative to --start_frame) where a new shot begins: used instead of the detector.")
     args = ap.parse_args()
@@ -288,11 +339,17 @@ def main():
     if args.spans is not None: kw["spans"] = args.spans
     if args.cuts is not None: kw["cuts"] = args.cuts
     if args.mask_clean is not None: kw["mask_clean"] = args.mask_clean
+    if args.tone_match is not None: kw["tone_match"] = args.tone_match
     out_frames = run_infill_on_frames(frames, mask_frames, propainer_frames=prior_frames, **kw)
     if args.mask_clean is not None and last_mask_clean is not None:
         r = last_mask_clean
         print(f"mask clean-up: {int(r.removed.sum())} components ({int(r.cleared.sum())} px) cleared in {int((r.removed > 0).sum())} frames, "
               f"{int(r.bridged.sum())} px bridged in {int((r.bridged > 0).sum())} frames, {int(r.grown.sum())} px grown in {int((r.grown > 0).sum())} frames")
+    if args.tone_match is not None and last_tone_match is not None:
+        r = last_tone_match
+        changed = (r.gain != 1.0).any(axis=(0, 2)) | (r.offset != 0.0).any(axis=(0, 2))
+        print(f"tone match: {int(changed.sum())} of {changed.size} frames corrected, largest |gain - 1| {float(np.abs(r.gain - 1.0).max()):.4f}, "
+              f"largest |offset| {float(np.abs(r.offset).max()):.2f}")
     tools.write_video_frames_to_path(out_video, out_frames, fps, H0, W0)
 
 

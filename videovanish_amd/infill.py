@@ -1,13 +1,14 @@
 """The orchestration of one diffuerase.run_infill_on_frames call after the dilation: the mask clean-up (clean_masks), the temporal plan
 (span_plan, run_spans), and for each clip the windows (region_plans, run_clip), ONE crop -> prior -> model sequence (run_windows) and ONE closing step (finish).  The full frame is
-no window, roi= "static" / "follow" one, the "-regions" spellings several.  The stages (weights, prior, model) come from the caller as a Stages
-record; nothing here is module state.  Rules and reasons: DESIGN.md §10, §11, §12."""
+no window, roi= "static" / "follow" one, the "-regions" spellings several.  With tone matching the closing step fits each window's pixels to the
+ring round the mask first (finish, tone_report).  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is
+module state.  Rules and reasons: DESIGN.md §10, §11, §12, §13."""
 from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
 
-from . import hip, mask_hip, spans_hip
+from . import hip, mask_hip, spans_hip, tone_hip, tonematch
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -162,9 +163,9 @@ def region_plans(dil_t, H0, W0, feather_px, cfg):
 
 
 def run_clip(frames_rgb, dil_t, propainer_frames, rcfg, stages, prog, dev, feather_px=3, keep_unmasked_original=True,
-             compat_reference_early_return=False):
+             compat_reference_early_return=False, tone=None, tone_out=None):
     """One clip after the dilation: the windows rcfg asks for (none without it, or where the planner falls back to the full frame), run_windows,
-    finish.  The whole call without spans=, and each span's call with it."""
+    finish.  The whole call without spans=, and each span's call with it.  tone / tone_out: finish's."""
     H0, W0 = frames_rgb[0].shape[:2]
     if rcfg is None:
         plans = []
@@ -174,7 +175,7 @@ def run_clip(frames_rgb, dil_t, propainer_frames, rcfg, stages, prog, dev, feath
         plan = roi_plan.plan_roi(hip.mask_bbox(dil_t).cpu().numpy(), H0, W0, feather_px, rcfg)
         plans = [] if plan is None else [plan]
     outs = run_windows(frames_rgb, list(dil_t.cpu().numpy()), propainer_frames, plans, stages, prog)
-    return finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return)
+    return finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return, tone, tone_out)
 
 
 def run_windows(frames_rgb, dil, propainer_frames, plans, stages, prog):
@@ -210,14 +211,41 @@ def _on_device(res, n, dev, fn):
     return res
 
 
-def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return=False):
+class ToneMatchReport(NamedTuple):
+    """What seam tone matching applied, per window k and frame t (K = 1 for the full frame): the pixels of the frame's own ring, the gain and offset
+    per channel, and the RMS of original - model and of original - (gain model + offset) over that ring (tonematch.ToneFit, stacked).  Frames
+    outside every span, frames this rank does not hold and windows a span does not have are identity rows with n = 0."""
+    n: np.ndarray               # [K,T] int64
+    gain: np.ndarray            # [K,T,3] float64
+    offset: np.ndarray          # [K,T,3] float64
+    rms_before: np.ndarray      # [K,T,3] float64
+    rms_after: np.ndarray       # [K,T,3] float64
+
+
+def tone_report(parts, spans, T, K=1):
+    """The report of a call over T frames from its clips' reports: parts[i] (finish's tone_out) covers the frames spans[i] = (a, b); at least K
+    windows."""
+    K = max([len(p.n) for p in parts] + [K])
+    rep = ToneMatchReport(np.zeros((K, T), np.int64), np.ones((K, T, 3)), np.zeros((K, T, 3)), np.zeros((K, T, 3)), np.zeros((K, T, 3)))
+    for part, (a, b) in zip(parts, spans):
+        for whole, piece in zip(rep, part):
+            whole[:len(piece), a:b] = piece
+    return rep
+
+
+def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return=False, tone=None, tone_out=None):
     """The model's frames into frames of the original size.  No plan (reference :69-112): resize when the model ran at another size, feathered
     composite with the originals when keep_unmasked_original, in place in outs[0].  The reference returns from inside its loop (:114) so only
     frame 0 is post-processed; the evident intent (all frames) is the default here, compat_reference_early_return=True reproduces the quirk.
     With plans: each window's frames into the originals (resize to the window, paste, feathered composite: roi_paste_composite once per window,
     the output of window k the original of window k + 1: two buffers, one upload, one download).  Exact because the windows are disjoint: inside
-    window k the mask holds only region k's pixels and no other window has touched the bytes.  keep_unmasked_original=False: the plain paste."""
+    window k the mask holds only region k's pixels and no other window has touched the bytes.  keep_unmasked_original=False: the plain paste.
+    tone (a tonematch.ToneMatchConfig): per window -- the full frame is the window (0, 0, H0, W0) -- ring_stats of the model's
+    pixels against the running buffer (inside window k still the original bytes), the [T,16] sums to the host, tonematch.fit and tables, the
+    [T,3,256] tables to the device, paste_lut_composite in place of the paste; with keep_unmasked_original=False every pasted pixel goes through
+    the table.  The clip's ToneMatchReport is appended to tone_out.  Without tone nothing here changes."""
     H0, W0 = frames_rgb[0].shape[:2]
+    T = len(outs[0])
 
     def full_frame(idx, up):
         out = up(outs[0])
@@ -237,6 +265,31 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
                                     out=bufs[(k + 1) % 2])
         return bufs[len(plans) % 2]
 
+    def toned(idx, up):
+        wins = [(p.offsets, p.size) for p in plans] or [(np.zeros((T, 2), np.int32), (H0, W0))]
+        bufs = [up(frames_rgb).contiguous()]
+        bufs.append(torch.empty_like(bufs[0]))
+        mask = dil_t[idx].contiguous()
+        fits = []
+        for k, ((offsets, (h, w)), o) in enumerate(zip(wins, outs)):
+            offs = torch.from_numpy(np.ascontiguousarray(offsets[idx], np.int32)).to(dev)
+            patch = up(o).contiguous()
+            sums = np.zeros((T, tonematch.NSUM), np.int64)
+            sums[idx] = tone_hip.ring_stats(patch, bufs[k % 2], mask, offs, h, w, tone.ring).cpu().numpy()
+            fits.append(tonematch.fit(sums, tone))
+            lut = torch.from_numpy(tonematch.tables(fits[-1].gain[idx], fits[-1].offset[idx])).to(dev)
+            tone_hip.paste_lut_composite(patch, bufs[k % 2], mask, offs, lut, h, w, float(feather_px if keep_unmasked_original else -1.0),
+                                         out=bufs[(k + 1) % 2])
+        if tone_out is not None:
+            tone_out.append(ToneMatchReport(*(np.stack(f) for f in zip(*fits))))
+        return bufs[len(wins) % 2]
+
+    if tone is not None:
+        done = len(tone_out) if tone_out is not None else 0
+        res = _on_device(outs[0] if not plans else list(outs[0]), T, dev, toned)
+        if tone_out is not None and len(tone_out) == done:        # this rank holds no frame of the clip: identity rows
+            tone_out.append(tone_report([], [], T, K=max(len(plans), 1)))
+        return res
     if not plans:
         return _on_device(outs[0], 1 if compat_reference_early_return else len(outs[0]), dev, full_frame)
     return _on_device(list(outs[0]), len(outs[0]), dev, windows)
