@@ -7,7 +7,8 @@ compat_reference_early_return, roi (mask-region inference: videovanish_amd/roi.p
 inference: only the runs of masked frames are processed, and nothing crosses a hard cut: videovanish_amd/spans.py; also configure(spans=...) and
 $VV_SPANS), mask_clean (mask clean-up between the dilation and the planners: speckles dropped, dropouts bridged, the mask grown in time:
 videovanish_amd/maskclean.py; also configure(mask_clean=...) and $VV_MASK_CLEAN), tone_match (seam tone matching: the model's pixels are fitted to
-the ring of unmasked pixels round the mask before the composite: videovanish_amd/tonematch.py; also configure(tone_match=...) and $VV_TONE_MATCH).
+the ring of unmasked pixels round the mask before the composite: videovanish_amd/tonematch.py; also configure(tone_match=...) and $VV_TONE_MATCH), grain_match (seam grain matching: the pasted pixels get the grain
+the original pixels of that ring have and the model's lack: videovanish_amd/grainmatch.py; also configure(grain_match=...) and $VV_GRAIN_MATCH).
 There is no CPU fallback: without the HIP extension / a GPU this raises.
 
 This file is the boundary: the reference's names and module state, the settings, and the stages (weights, prior, model) that read that state.
@@ -20,7 +21,7 @@ import numpy as np
 import torch
 
 from videovanish_amd import hip, infill
-from videovanish_amd import maskclean, tonematch
+from videovanish_amd import grainmatch, maskclean, tonematch
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
 from videovanish_amd.config import RunConfig
@@ -44,10 +45,12 @@ _mask_clean = None      # configure(mask_clean=...): mask clean-up for calls tha
 last_mask_clean = None  # the infill.MaskCleanReport of the last run_infill_on_frames call; None when the stage did not run
 _tone_match = None      # configure(tone_match=...): seam tone matching for calls that do not pass tone_match= themselves
 last_tone_match = None  # the infill.ToneMatchReport of the last run_infill_on_frames call; None when the stage did not run
+_grain_match = None     # configure(grain_match=...): seam grain matching for calls that do not pass grain_match= themselves
+last_grain_match = None # the infill.GrainMatchReport of the last run_infill_on_frames call; None when the stage did not run
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
-              mask_clean=None, tone_match=None):
+              mask_clean=None, tone_match=None, grain_match=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -67,8 +70,11 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     mask_clean = None / "on" / "area=64,bridge=2,grow=1" (any subset) / a maskclean.MaskCleanConfig: mask clean-up for calls that do not pass
     mask_clean=.
     tone_match = None / "on" / "affine" / "offset" / "mode=offset,ring=8,smooth=0" (any subset) / a tonematch.ToneMatchConfig: seam tone matching
-    for calls that do not pass tone_match=."""
-    global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi, _spans, _mask_clean, _tone_match
+    for calls that do not pass tone_match=.
+    grain_match = None / "on" / "luma" / "rgb" / "mode=rgb,ring=8,strength=0.8,seed=3" (any subset) / a grainmatch.GrainMatchConfig: seam grain
+    matching for calls that do not pass grain_match=."""
+    global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi, _spans, _mask_clean, _tone_match, _grain_match
+    grainmatch.as_config(grain_match)
     tonematch.as_config(tone_match)
     maskclean.as_config(mask_clean)
     span_plan.as_config(spans)
@@ -84,6 +90,7 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     _spans = spans
     _mask_clean = mask_clean
     _tone_match = tone_match
+    _grain_match = grain_match
 
 
 def _resolve_weights(ckpt):
@@ -153,10 +160,21 @@ def tone_match_config(tone_match=None):
     return tonematch.as_config(os.environ.get("VV_TONE_MATCH"))
 
 
+def grain_match_config(grain_match=None):
+    """The seam grain matching setting a call runs with: its own grain_match= argument, else configure(grain_match=...), else $VV_GRAIN_MATCH (on |
+    luma | rgb | off | mode=..,ring=N,..).  None = no grain matching.  grain_match="off" (or False) asks for none whatever configure() or the
+    environment say."""
+    if grain_match is not None:
+        return grainmatch.as_config(grain_match)
+    if _grain_match is not None:
+        return grainmatch.as_config(_grain_match)
+    return grainmatch.as_config(os.environ.get("VV_GRAIN_MATCH"))
+
+
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
-                         mask_clean=None, tone_match=None):
+                         mask_clean=None, tone_match=None, grain_match=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -177,13 +195,21 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     fits, per frame and channel, the model's pixels to the original ones over the ring of unmasked pixels round the mask (a gain and an offset,
     pooled over neighbouring frames, clamped) and sends every pasted pixel through the resulting table before the feathered composite
     (infill.finish), for the full frame and for every roi window, inside each span.  What it applied is kept in last_tone_match.  A model frame
-    that equals the original on the ring gives the bytes of the call without it."""
-    global last_mask_clean, last_tone_match
+    that equals the original on the ring gives the bytes of the call without it.
+    grain_match (seam grain matching, opt-in): "on" / "luma" / "rgb" / "mode=rgb,ring=8,strength=0.8,seed=3" / a
+    videovanish_amd.grainmatch.GrainMatchConfig measures, per frame, channel and brightness band, the grain the original pixels have and the
+    model's pixels lack over the flat part of that ring (after tone matching's table, when both are on; pooled over neighbouring frames,
+    capped) and adds stateless white noise of that level to every pasted pixel before the feathered composite (infill.finish), for the full
+    frame and for every roi window, inside each span; the noise of a pixel depends on the seed, the frame's index in this call and the
+    pixel's position in the frame only.  What it measured and added is kept in last_grain_match.  A model frame that equals the original on
+    the ring gives the bytes of the call without it."""
+    global last_mask_clean, last_tone_match, last_grain_match
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
     ccfg = mask_clean_config(mask_clean)
     tcfg = tone_match_config(tone_match)
-    last_mask_clean = last_tone_match = None
+    gcfg = grain_match_config(grain_match)
+    last_mask_clean = last_tone_match = last_grain_match = None
     if rcfg is not None and compat_reference_early_return:
         raise ValueError("roi= (mask-region inference) cannot be combined with compat_reference_early_return=True")
     if scfg is not None and compat_reference_early_return:
@@ -192,6 +218,8 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         raise ValueError("mask_clean= (mask clean-up) cannot be combined with compat_reference_early_return=True")
     if tcfg is not None and compat_reference_early_return:
         raise ValueError("tone_match= (seam tone matching) cannot be combined with compat_reference_early_return=True")
+    if gcfg is not None and compat_reference_early_return:
+        raise ValueError("grain_match= (seam grain matching) cannot be combined with compat_reference_early_return=True")
 
     if prog is not None: prog(5, "dilating frames")
     dev = get_device()
@@ -208,10 +236,12 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
                            lambda f, d, prior, p: _run_model(f, d, prior, max_img_size, p, num_inference_steps, scheduler))
 
     tone_parts = None if tcfg is None else []       # one report per clip call, in the order of the spans
+    grain_parts = None if gcfg is None else []
 
-    def body(frames, dil, prior, p):
+    def body(frames, dil, prior, p, frame0=0):
+        more = {} if gcfg is None else dict(grain=gcfg, grain_out=grain_parts, frame0=frame0)     # passed only when grain matching is on
         return infill.run_clip(frames, dil, prior, rcfg, stages, p, dev, feather_px, keep_unmasked_original, compat_reference_early_return,
-                               tone=tcfg, tone_out=tone_parts)
+                               tone=tcfg, tone_out=tone_parts, **more)
 
     T = len(frames_rgb)
     if scfg is None:
@@ -219,9 +249,12 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         out = body(frames_rgb, dil_t, propainer_frames, prog)
     else:
         plan = infill.span_plan(frames_rgb, dil_t, scfg)
-        out = infill.run_spans(frames_rgb, dil_t, propainer_frames, plan, body, prog, load=stages.load_model)
+        more = {} if gcfg is None else dict(frame0=True)        # each span's clip call learns where it starts
+        out = infill.run_spans(frames_rgb, dil_t, propainer_frames, plan, body, prog, load=stages.load_model, **more)
     if tcfg is not None:
         last_tone_match = infill.tone_report(tone_parts, plan, T)
+    if gcfg is not None:
+        last_grain_match = infill.grain_report(grain_parts, plan, T)
     return out
 
 
@@ -282,6 +315,16 @@ def _tone_match_arg(text):
     return text
 
 
+def _grain_match_arg(text):
+    """--grain-match's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --tone-match)."""
+    try:
+        if grainmatch.as_config(text) is None:
+            raise ValueError("not a setting")
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return text
+
+
 def _mask_clean_arg(text):
     """--mask-clean's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --roi / --spans)."""
     try:
@@ -319,6 +362,10 @@ def main():
                     help="Seam tone matching before the composite: per frame and channel, fit the model's pixels to the original ones over the ring of "
                          "unmasked pixels within `ring` px of the mask (on: a gain and an offset, ring 12, pooled over 2 frames either side; offset: "
                          "an offset only) and correct every pasted pixel with it.  Prints one line with what it applied.")
+    ap.add_argument("--grain-match", type=_grain_match_arg, default=None, metavar="on|luma|rgb|mode=rgb,ring=8,strength=0.8,seed=3",
+                    help="Seam grain matching before the composite: measure, over the flat part of the ring of unmasked pixels within `ring` px of the "
+                         "mask, the grain the original pixels have and the model's lack, and add white noise of that level to every pasted pixel (on / "
+                         "luma: one noise value per pixel; rgb: one per channel).  Prints one line with what it added.")
     ap.add_argument("--cuts", type=span_plan.parse_cuts, default=None, metavar="120,431",
                     help="Frame indices (relative to --start_frame) where a new shot begins: used instead of the detector.")
     args = ap.parse_args()
@@ -340,6 +387,7 @@ def main():
     if args.cuts is not None: kw["cuts"] = args.cuts
     if args.mask_clean is not None: kw["mask_clean"] = args.mask_clean
     if args.tone_match is not None: kw["tone_match"] = args.tone_match
+    if args.grain_match is not None: kw["grain_match"] = args.grain_match
     out_frames = run_infill_on_frames(frames, mask_frames, propainer_frames=prior_frames, **kw)
     if args.mask_clean is not None and last_mask_clean is not None:
         r = last_mask_clean
@@ -350,6 +398,10 @@ def main():
         changed = (r.gain != 1.0).any(axis=(0, 2)) | (r.offset != 0.0).any(axis=(0, 2))
         print(f"tone match: {int(changed.sum())} of {changed.size} frames corrected, largest |gain - 1| {float(np.abs(r.gain - 1.0).max()):.4f}, "
               f"largest |offset| {float(np.abs(r.offset).max()):.2f}")
+    if args.grain_match is not None and last_grain_match is not None:
+        r = last_grain_match
+        touched = (r.sigma_added > 0.0).any(axis=(0, 2, 3))
+        print(f"grain match: grain added in {int(touched.sum())} of {touched.size} frames, largest sigma {float(r.sigma_added.max()):.2f}")
     tools.write_video_frames_to_path(out_video, out_frames, fps, H0, W0)
 
 

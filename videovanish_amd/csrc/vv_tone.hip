@@ -2,31 +2,25 @@
 //   vvt_ring_stats            16 integer sums per frame over the ring: the unmasked pixels of the window within `ring` pixels (a box) of a mask
 //                             pixel, where both the model's pixel x and the original pixel y exist
 //   vvt_paste_lut_composite   vv_roi_paste_composite with the window's bytes sent through a per-frame, per-channel table first
-// The ring test is a separable box dilation on bits.  A block owns a TW x TH tile of the window and reads the mask of the tile plus a halo of
-// `ring` pixels, one row per wave step: two ballots turn the row into 128 bits, a log-step shift-OR ORs every run of 2 ring + 1 bits (the row
-// pass: seven 128-bit shift-ORs whatever the ring), and TH threads OR the 2 ring + 1 row words above and below their row (the column pass:
-// 2 ring + 1 LDS reads per tile ROW, not per pixel).  Nothing is searched per pixel; a tile without a ring pixel ends after the mask reads.
+// The ring test is a separable box dilation on bits (vv_ring_bits.h, shared with vv_grain.hip): two ballots per halo row, a log-step shift-OR,
+// a column OR per tile row.  Nothing is searched per pixel; a tile without a ring pixel ends after the mask reads.
 // The sums go registers -> wave reduction -> 64-bit LDS atomics -> one set of 64-bit global integer atomics per block (as vv_spans.hip's pair
 // statistics): integer adds, so the result does not depend on the order.  The per-pixel arithmetic (resize, feather) is vv_image_px.h, the
 // statement vv_roi.hip uses, so an identity table gives vv_roi_paste_composite's bytes.
 #include "vv_image_px.h"
+#include "vv_ring_bits.h"
 #include "../../include/vvtone.h"
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int TB = 256;                          // threads per block: 4 waves
-constexpr int TW = 64, TH = 32;                  // the tile: one lane per column, TH * TW / TB = 8 rows per thread
-constexpr int HALO_ROWS = TH + 2 * VVT_MAX_RING;
+using vvring::TB;                                // threads per block: 4 waves
+using vvring::TW;                                // the tile: one lane per column, TH * TW / TB = 8 rows per thread
+using vvring::TH;
+using vvring::u64;
 constexpr int NSUM = 16;
-static_assert(TW + 2 * VVT_MAX_RING <= 128, "a halo row is two ballots");
-typedef unsigned long long u64;
+static_assert(VVT_MAX_RING == vvring::MAX_RING, "the ring of vv_ring_bits.h");
 
-// (hi:lo) >> k, 0 < k < 64
-__device__ __forceinline__ void shr128(u64& hi, u64& lo, int k) {
-    lo = (lo >> k) | (hi << (64 - k));
-    hi >>= k;
-}
 __device__ __forceinline__ u64 wave_sum64(u64 v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -52,7 +46,7 @@ __device__ __forceinline__ void window_px(const uint8_t* src, int Hm, int Wm, in
 __global__ __launch_bounds__(TB) void ring_stats_kernel(const uint8_t* __restrict__ patch, int Hm, int Wm, const uint8_t* __restrict__ orig,
                                                         const uint8_t* __restrict__ mask, const int* __restrict__ offsets, int H, int W, int h, int w,
                                                         int r, int tiles_x, int tiles_y, u64* __restrict__ sums) {
-    __shared__ u64 rowbits[HALO_ROWS];           // halo row j: bit px = some mask pixel in the row within r columns of tile column px
+    __shared__ u64 rowbits[vvring::HALO_ROWS];   // scratch of the row pass
     __shared__ u64 own[TH];                      // tile row y: bit px = the pixel's own mask
     __shared__ u64 ringbits[TH];                 // tile row y: bit px = the pixel belongs to the ring
     __shared__ u64 tot[NSUM];
@@ -60,53 +54,8 @@ __global__ __launch_bounds__(TB) void ring_stats_kernel(const uint8_t* __restric
     const int tx0 = (tile % tiles_x) * TW, ty0 = (tile / tiles_x) * TH;        // the tile's origin in the window
     const int oy = offsets[t * 2 + 0], ox = offsets[t * 2 + 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint8_t* m = mask + (int64_t)t * H * W;
     if (threadIdx.x < NSUM) tot[threadIdx.x] = 0;
-
-    // row pass.  Halo row j is frame row oy + ty0 + j - r, halo column i is frame column ox + tx0 + i - r; outside the frame: no mask
-    const int rows = TH + 2 * r, n = 2 * r + 1;
-    for (int j = wave; j < rows; j += TB / 64) {                               // wave-uniform
-        const int Y = oy + ty0 + j - r;
-        const int X0 = ox + tx0 + lane - r, X1 = X0 + 64;
-        const bool rowin = Y >= 0 && Y < H;
-        const bool b0 = rowin && X0 >= 0 && X0 < W && m[(int64_t)Y * W + X0] != 0;
-        const bool b1 = rowin && lane < 2 * r && X1 >= 0 && X1 < W && m[(int64_t)Y * W + X1] != 0;
-        u64 lo = __ballot(b0), hi = __ballot(b1);
-        if (j >= r && j < r + TH) {
-            u64 a = hi, b = lo;
-            shr128(a, b, r);
-            if (lane == 0) own[j - r] = b;
-        }
-        // OR of the n bits from each position on: doubling steps while they fit, one last step for the rest
-        int cover = 1;
-        for (; cover * 2 <= n; cover *= 2) {
-            u64 a = hi, b = lo;
-            shr128(a, b, cover);
-            hi |= a; lo |= b;
-        }
-        if (n > cover) {
-            u64 a = hi, b = lo;
-            shr128(a, b, n - cover);
-            hi |= a; lo |= b;
-        }
-        if (lane == 0) rowbits[j] = lo;
-    }
-    __syncthreads();
-
-    // column pass: tile row y is halo row y + r and sees halo rows y .. y + 2 r; then the window and the frame clip the tile
-    if (threadIdx.x < TH) {
-        const int y = threadIdx.x;
-        u64 v = 0;
-        for (int k = 0; k < n; ++k) v |= rowbits[y + k];
-        const int yy = ty0 + y, Y = oy + yy;
-        u64 cols = 0;
-        if (yy < h && Y >= 0 && Y < H) {
-            int lo_x = max(0, -(ox + tx0)), hi_x = min(TW, min(w - tx0, W - (ox + tx0)));          // tile columns [lo_x, hi_x) exist
-            if (hi_x > lo_x) cols = (hi_x - lo_x >= 64 ? ~0ull : ((1ull << (hi_x - lo_x)) - 1ull)) << lo_x;
-        }
-        ringbits[y] = v & ~own[y] & cols;
-    }
-    __syncthreads();
+    vvring::ring_bits<false>(mask + (int64_t)t * H * W, H, W, oy, ox, tx0, ty0, h, w, r, rowbits, own, ringbits, nullptr);
 
     u64 acc[NSUM];
 #pragma unroll

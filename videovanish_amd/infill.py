@@ -1,14 +1,15 @@
 """The orchestration of one diffuerase.run_infill_on_frames call after the dilation: the mask clean-up (clean_masks), the temporal plan
 (span_plan, run_spans), and for each clip the windows (region_plans, run_clip), ONE crop -> prior -> model sequence (run_windows) and ONE closing step (finish).  The full frame is
 no window, roi= "static" / "follow" one, the "-regions" spellings several.  With tone matching the closing step fits each window's pixels to the
-ring round the mask first (finish, tone_report).  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is
-module state.  Rules and reasons: DESIGN.md §10, §11, §12, §13."""
+ring round the mask first (finish, tone_report); with grain matching it gives them the grain the ring's originals have and the model's pixels lack
+(finish, grain_report).  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is
+module state.  Rules and reasons: DESIGN.md §10, §11, §12, §13, §14."""
 from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
 
-from . import hip, mask_hip, spans_hip, tone_hip, tonematch
+from . import grain_hip, grainmatch, hip, mask_hip, spans_hip, tone_hip, tonematch
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -122,14 +123,16 @@ def _span_progress(prog, n):
     return span, seen
 
 
-def run_spans(frames_rgb, dil, propainer_frames, plan, body, prog, load=None):
+def run_spans(frames_rgb, dil, propainer_frames, plan, body, prog, load=None, frame0=False):
     """The temporal plan carried out: body(frames[a:b], dil[a:b], prior[a:b] | None, progress) per span (a, b), in order; every other frame is the
     original array.  One span that is the whole clip: body on the clip as it is, with the caller's progress.  No span: the original frames, no
     model (load is not called), the milestones 5 / 10 / 20 / 50 / 90 still delivered.  body is the per-clip computation (run_infill_on_frames
-    passes run_clip); load loads the weights once, before the first span."""
+    passes run_clip); load loads the weights once, before the first span.  frame0=True: body also gets frame0=a, the index of its clip's first
+    frame in the call (grain matching keys its noise on it: a frame gets the same field however the clip was split)."""
     T = len(frames_rgb)
+    at = (lambda a: {"frame0": a}) if frame0 else (lambda a: {})
     if list(plan) == [(0, T)]:
-        return body(frames_rgb, dil, propainer_frames, prog)
+        return body(frames_rgb, dil, propainer_frames, prog, **at(0))
     out = list(frames_rgb)
     if not plan:
         if prog is not None:
@@ -142,7 +145,7 @@ def run_spans(frames_rgb, dil, propainer_frames, plan, body, prog, load=None):
         load()
     span, seen = _span_progress(prog, len(plan))
     for k, (a, b) in enumerate(plan):
-        out[a:b] = body(frames_rgb[a:b], dil[a:b], None if propainer_frames is None else propainer_frames[a:b], span(k))
+        out[a:b] = body(frames_rgb[a:b], dil[a:b], None if propainer_frames is None else propainer_frames[a:b], span(k), **at(a))
     if prog is not None:
         if 50 not in seen: prog(50, "running DiffuEraser")
         prog(90, "resizing and merging finished frames")
@@ -163,9 +166,9 @@ def region_plans(dil_t, H0, W0, feather_px, cfg):
 
 
 def run_clip(frames_rgb, dil_t, propainer_frames, rcfg, stages, prog, dev, feather_px=3, keep_unmasked_original=True,
-             compat_reference_early_return=False, tone=None, tone_out=None):
+             compat_reference_early_return=False, tone=None, tone_out=None, grain=None, grain_out=None, frame0=0):
     """One clip after the dilation: the windows rcfg asks for (none without it, or where the planner falls back to the full frame), run_windows,
-    finish.  The whole call without spans=, and each span's call with it.  tone / tone_out: finish's."""
+    finish.  The whole call without spans=, and each span's call with it.  tone / tone_out / grain / grain_out / frame0: finish's."""
     H0, W0 = frames_rgb[0].shape[:2]
     if rcfg is None:
         plans = []
@@ -175,7 +178,8 @@ def run_clip(frames_rgb, dil_t, propainer_frames, rcfg, stages, prog, dev, feath
         plan = roi_plan.plan_roi(hip.mask_bbox(dil_t).cpu().numpy(), H0, W0, feather_px, rcfg)
         plans = [] if plan is None else [plan]
     outs = run_windows(frames_rgb, list(dil_t.cpu().numpy()), propainer_frames, plans, stages, prog)
-    return finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return, tone, tone_out)
+    more = {} if grain is None else dict(grain=grain, grain_out=grain_out, frame0=frame0)       # passed only when grain matching is on
+    return finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return, tone, tone_out, **more)
 
 
 def run_windows(frames_rgb, dil, propainer_frames, plans, stages, prog):
@@ -233,7 +237,31 @@ def tone_report(parts, spans, T, K=1):
     return rep
 
 
-def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return=False, tone=None, tone_out=None):
+class GrainMatchReport(NamedTuple):
+    """What seam grain matching measured and added, per window k, frame t, channel and brightness band (K = 1 for the full frame): the counted
+    pixels of the frame's own ring, the grain (sigma, 8-bit levels) of the original and of the model's rendering over the pooled ring, and the
+    sigma of the noise added (grainmatch.GrainFit, stacked).  Frames outside every span, frames this rank does not hold and windows a span does
+    not have are zero rows."""
+    n: np.ndarray               # [K,T,3,4] int64
+    sigma_orig: np.ndarray      # [K,T,3,4] float64
+    sigma_model: np.ndarray     # [K,T,3,4] float64
+    sigma_added: np.ndarray     # [K,T,3,4] float64
+
+
+def grain_report(parts, spans, T, K=1):
+    """The report of a call over T frames from its clips' reports: parts[i] (finish's grain_out) covers the frames spans[i] = (a, b); at least K
+    windows."""
+    K = max([len(p.n) for p in parts] + [K])
+    shape = (K, T, 3, grainmatch.BANDS)
+    rep = GrainMatchReport(np.zeros(shape, np.int64), np.zeros(shape), np.zeros(shape), np.zeros(shape))
+    for part, (a, b) in zip(parts, spans):
+        for whole, piece in zip(rep, part):
+            whole[:len(piece), a:b] = piece
+    return rep
+
+
+def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return=False, tone=None, tone_out=None,
+           grain=None, grain_out=None, frame0=0):
     """The model's frames into frames of the original size.  No plan (reference :69-112): resize when the model ran at another size, feathered
     composite with the originals when keep_unmasked_original, in place in outs[0].  The reference returns from inside its loop (:114) so only
     frame 0 is post-processed; the evident intent (all frames) is the default here, compat_reference_early_return=True reproduces the quirk.
@@ -243,7 +271,12 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
     tone (a tonematch.ToneMatchConfig): per window -- the full frame is the window (0, 0, H0, W0) -- ring_stats of the model's
     pixels against the running buffer (inside window k still the original bytes), the [T,16] sums to the host, tonematch.fit and tables, the
     [T,3,256] tables to the device, paste_lut_composite in place of the paste; with keep_unmasked_original=False every pasted pixel goes through
-    the table.  The clip's ToneMatchReport is appended to tone_out.  Without tone nothing here changes."""
+    the table.  The clip's ToneMatchReport is appended to tone_out.  Without tone nothing here changes.
+    grain (a grainmatch.GrainMatchConfig): per window, after tone's table (the identity table without tone): ring_grain_stats of
+    the looked-up pixels against the running buffer, the [T,36] sums to the host, grainmatch.fit and tables, the [T,3,256] amplitudes to the
+    device, paste_grain_composite in place of the paste, its noise keyed on the frame's index in the call, frame0 + its index in this clip;
+    with keep_unmasked_original=False every pasted pixel gets grain.  The clip's GrainMatchReport is appended to grain_out.  Without grain
+    nothing here changes, and the tone-only path still calls paste_lut_composite."""
     H0, W0 = frames_rgb[0].shape[:2]
     T = len(outs[0])
 
@@ -284,11 +317,43 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
             tone_out.append(ToneMatchReport(*(np.stack(f) for f in zip(*fits))))
         return bufs[len(wins) % 2]
 
-    if tone is not None:
-        done = len(tone_out) if tone_out is not None else 0
-        res = _on_device(outs[0] if not plans else list(outs[0]), T, dev, toned)
-        if tone_out is not None and len(tone_out) == done:        # this rank holds no frame of the clip: identity rows
+    def grained(idx, up):
+        wins = [(p.offsets, p.size) for p in plans] or [(np.zeros((T, 2), np.int32), (H0, W0))]
+        bufs = [up(frames_rgb).contiguous()]
+        bufs.append(torch.empty_like(bufs[0]))
+        mask = dil_t[idx].contiguous()
+        ids = torch.from_numpy(np.asarray(idx, np.int32) + np.int32(frame0)).to(dev)
+        ident = np.broadcast_to(np.arange(256, dtype=np.uint8), (len(idx), 3, 256))
+        tfits, gfits = [], []
+        for k, ((offsets, (h, w)), o) in enumerate(zip(wins, outs)):
+            offs = torch.from_numpy(np.ascontiguousarray(offsets[idx], np.int32)).to(dev)
+            patch = up(o).contiguous()
+            lut = ident
+            if tone is not None:
+                sums = np.zeros((T, tonematch.NSUM), np.int64)
+                sums[idx] = tone_hip.ring_stats(patch, bufs[k % 2], mask, offs, h, w, tone.ring).cpu().numpy()
+                tfits.append(tonematch.fit(sums, tone))
+                lut = tonematch.tables(tfits[-1].gain[idx], tfits[-1].offset[idx])
+            lut = torch.from_numpy(np.ascontiguousarray(lut)).to(dev)
+            sums = np.zeros((T, grainmatch.NSUM), np.int64)
+            sums[idx] = grain_hip.ring_grain_stats(patch, bufs[k % 2], mask, offs, lut, h, w, grain.ring, grain.flat).cpu().numpy()
+            gfits.append(grainmatch.fit(sums, grain))
+            amp = torch.from_numpy(grainmatch.tables(gfits[-1].sigma_added[idx])).to(dev)
+            grain_hip.paste_grain_composite(patch, bufs[k % 2], mask, offs, lut, amp, ids, grain.seed, grainmatch.MODES.index(grain.mode), h, w,
+                                            float(feather_px if keep_unmasked_original else -1.0), out=bufs[(k + 1) % 2])
+        if tone is not None and tone_out is not None:
+            tone_out.append(ToneMatchReport(*(np.stack(f) for f in zip(*tfits))))
+        if grain_out is not None:
+            grain_out.append(GrainMatchReport(*(np.stack(f) for f in zip(*gfits))))
+        return bufs[len(wins) % 2]
+
+    if tone is not None or grain is not None:
+        done = [len(o) if o is not None else 0 for o in (tone_out, grain_out)]
+        res = _on_device(outs[0] if not plans else list(outs[0]), T, dev, toned if grain is None else grained)
+        if tone is not None and tone_out is not None and len(tone_out) == done[0]:        # this rank holds no frame of the clip: identity rows
             tone_out.append(tone_report([], [], T, K=max(len(plans), 1)))
+        if grain is not None and grain_out is not None and len(grain_out) == done[1]:     # likewise: zero rows
+            grain_out.append(grain_report([], [], T, K=max(len(plans), 1)))
         return res
     if not plans:
         return _on_device(outs[0], 1 if compat_reference_early_return else len(outs[0]), dev, full_frame)
