@@ -264,7 +264,7 @@ typedef struct {
     const void* q; const void* k; const void* v; void* o;   /* h16 */
     int64_t q_bs, k_bs, v_bs, o_bs;   /* batch strides (elements) */
     int64_t q_rs, k_rs, v_rs, o_rs;   /* row strides (elements) */
-    int32_t B, heads, Nq, Nkv, D;     /* D in {32,40,64,80,160,512} */
+    int32_t B, heads, Nq, Nkv, D;     /* D in {32,40,64,80,128,160,256,512} */
     float scale;                      /* softmax scale (D^-1/2) */
     int64_t q_hs, k_hs, v_hs;         /* head strides (elements) of q / k / v; 0 = D (heads side by side inside a row).  The
                                          head-major QKV layout written by vv_conv_gemm's split_heads store uses
@@ -276,7 +276,8 @@ typedef struct {
     float* lse;                       /* optional (ABI 8) [B][heads][Nq] fp32: log2 of sum_k 2^(scale log2e q.k) over THIS call's keys.  With it a
                                          long key sequence is split over the batch index (q_bs = 0, k_bs = v_bs = chunk * row stride) and the
                                          partial outputs are merged by vv_attention_merge: more blocks for one long head (SAM 2 memory attention:
-                                         4096 queries x 28736 keys, one head of 256).  Generic kernel only (not the d = 40 spatial form). */
+                                         4096 queries x 28736 keys, one head of 256).  Refused (VV_E_UNSUPPORTED) at D = 40; written by the generic (16x16x32) kernels and
+                                         by VV_ATTN_ROUTE_MFMA32_D80 (vv_attention_route). */
     int64_t o_hs;                     /* ABI 10: head stride (elements) of o; 0 = D (heads side by side inside a row of o_rs elements: o[b*o_bs + i*o_rs + h*D + c]).
                                          HEAD-MAJOR output o[b][head][token][D] (o_hs = Nq*D, o_rs = D, o_bs = heads*Nq*D): every wave stores whole
                                          contiguous 2*D-byte records, 64 tokens = 64 * 2*D contiguous bytes -- in the row layout a head's 80-byte (D = 40)
@@ -284,6 +285,28 @@ typedef struct {
                                          level-0 spatial blocks use it: vv_spatial_chain_c320 reads that layout with vv_chain_params.o_hw > 0. */
 } vv_attn_params;
 int vv_attention(const vv_attn_params* host_p, int dtype, void* stream);
+/* The kernel vv_attention would launch for these parameters, as a VV_ATTN_ROUTE_* code (> 0), or the negative VV_E_* code it would refuse the launch
+   with (vv_last_error has the reason).  Host only: pointers are read as null / non-null flags, no device is touched; vv_attention launches the route this
+   function returns.  One code per kernel body; "cross" = Nkv < 128 && Nq != Nkv (the 77 text tokens), "short" = Nq <= 32 && Nkv <= 32 (temporal attention).
+   route = form | flags: VV_ATTN_ROUTE_CROSS on DMA64 / REG80 (the cross-attention instantiation of the same body, named apart for profilers),
+   VV_ATTN_ROUTE_RAGGED on MFMA32_* (Nkv % 64 != 0: the instantiation that masks the last key tile). */
+enum { VV_ATTN_ROUTE_CROSS = 1, VV_ATTN_ROUTE_RAGGED = 2 };
+enum {
+    /* 16x16x32 flash kernels (vv_attn.hip); W waves x Q queries each, K-key tiles */
+    VV_ATTN_ROUTE_SHORT         = 0x10,   /* short, D < 512 (D >= 128: Nq <= 16 only): 1 wave, 32 queries, 32-key tile */
+    VV_ATTN_ROUTE_SHORT_2W      = 0x20,   /* short, D in {128,160,256}, Nq > 16: 2 waves x 16 queries, 32-key tile */
+    VV_ATTN_ROUTE_DMA64         = 0x30,   /* D <= 64 (D = 40: what MFMA32_D40* leaves): 4 x 32 queries, 64-key tiles by LDS-DMA, double buffered (| CROSS) */
+    VV_ATTN_ROUTE_REG80         = 0x40,   /* D = 80 (what MFMA32_D80 leaves): 4 x 32 queries, 64-key tiles staged through registers (| CROSS) */
+    VV_ATTN_ROUTE_W4x32         = 0x50,   /* D in {128,160,256}: 4 x 32 queries, 64-key tiles (D = 160: Nq < 256; D = 256: more than 128 blocks of 128 queries) */
+    VV_ATTN_ROUTE_W8x16         = 0x60,   /* D = 160 with Nq >= 256, D = 256 with B * heads * ceil(Nq / 128) <= 128: 8 x 16 queries, 64-key tiles */
+    VV_ATTN_ROUTE_D512_W4       = 0x70,   /* D = 512, Nq < 256: 4 x 16 queries, 32-key tiles */
+    VV_ATTN_ROUTE_D512_W8       = 0x80,   /* D = 512, Nq >= 256: 8 x 16 queries, 32-key tiles */
+    /* 32x32x16 kernels with an optimistic softmax reference (vv_attn32.hip): not short, not cross, Nkv >= 64 (| RAGGED) */
+    VV_ATTN_ROUTE_MFMA32_D40    = 0x90,   /* D = 40, Nq < 1024: 4 x 32 queries */
+    VV_ATTN_ROUTE_MFMA32_D40_Q2 = 0xa0,   /* D = 40, Nq >= 1024: 4 x 64 queries */
+    VV_ATTN_ROUTE_MFMA32_D80    = 0xb0    /* D = 80, Nq >= 512: 4 x 64 queries; writes lse */
+};
+int vv_attention_route(const vv_attn_params* host_p, int dtype);
 /* out[q][h*D + c] = sum_s w_s o_parts[s][q][h*D + c] / sum_s w_s, w_s = 2^(lse[s][h][q] - max_s lse): merges S partial attention results
  * (o_parts: h16 [S][Nq][ld], lse: [S][heads][Nq]) into out (h16 [Nq][ld]) */
 int vv_attention_merge(const void* o_parts, const float* lse, int S, int heads, int Nq, int D, int ld, void* out, int dtype, void* stream);

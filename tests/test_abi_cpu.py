@@ -54,7 +54,7 @@ def test_binding_lists_match_header(lib):
     or float parameter passed without its declaration would be truncated / passed as garbage silently."""
     from videovanish_amd import hip
     protos = _prototypes()
-    assert sorted(protos) == _declared() and len(protos) == 87
+    assert sorted(protos) == _declared() and len(protos) == 88
     assert sorted(hip.EXPORTS) == _declared()
     assert sorted(hip.SIGNATURES) == sorted(protos)
     loaded = hip.lib()

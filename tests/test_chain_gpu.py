@@ -103,15 +103,17 @@ def test_head_major_attention_output_is_bit_identical(gpu):
     cfg = UNetConfig()
     g = torch.Generator().manual_seed(9)
     ctx = vnn.Ctx("cuda:0", "fp16", 0)
-    for (B, heads, N, D) in ((2, 8, 1000, 40), (1, 8, 4096, 40), (2, 8, 1115, 40), (3, 4, 200, 64), (2, 8, 900, 80)):
+    for (B, heads, N, D, route) in ((2, 8, 1000, 40, "mfma32-d40 ragged"), (1, 8, 4096, 40, "mfma32-d40-q2 whole"), (2, 8, 1115, 40, "mfma32-d40-q2 ragged"),
+                                    (3, 4, 200, 64, "dma64 self"), (2, 8, 900, 80, "mfma32-d80 ragged")):
         C = heads * D
         qkv = (torch.randn(B, 3, heads, N, D, generator=g) * 0.5).to(gpu).to(ctx.h16)
         outs = []
         for hm in (False, True):
             o = torch.zeros((B, heads, N, D) if hm else (B * N, C), dtype=ctx.h16, device=gpu)
-            hip.attention(ctx.dt, qkv, qkv, qkv, o, B=B, heads=heads, Nq=N, Nkv=N, D=D, q_bs=N * 3 * C, k_bs=N * 3 * C, v_bs=N * 3 * C, o_bs=N * C,
-                          q_rs=D, k_rs=D, v_rs=D, o_rs=D if hm else C, k_off=N * C, v_off=2 * N * C, q_hs=N * D, k_hs=N * D, v_hs=N * D,
-                          o_hs=N * D if hm else 0)
+            kw = dict(B=B, heads=heads, Nq=N, Nkv=N, D=D, q_bs=N * 3 * C, k_bs=N * 3 * C, v_bs=N * 3 * C, o_bs=N * C, q_rs=D, k_rs=D, v_rs=D, o_rs=D if hm else C,
+                      k_off=N * C, v_off=2 * N * C, q_hs=N * D, k_hs=N * D, v_hs=N * D, o_hs=N * D if hm else 0)
+            assert hip.attn_route_name(hip.attention_route(ctx.dt, qkv, qkv, qkv, o, **kw)) == route
+            hip.attention(ctx.dt, qkv, qkv, qkv, o, **kw)
             outs.append(o.permute(0, 2, 1, 3).reshape(B * N, C) if hm else o)
         assert torch.isfinite(outs[0].float()).all() and torch.equal(outs[0], outs[1]), (B, heads, N, D)
     text = ctx.dev(torch.randn(77, 768, generator=g), ctx.h16)

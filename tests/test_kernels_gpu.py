@@ -208,6 +208,9 @@ def test_attention_spatial(gpu, dname, td, ulp, B, heads, Nq, Nkv, D):
     """fused-QKV layout for self attention; separate K/V with batch stride 0 for cross attention (Nq != Nkv)."""
     from videovanish_amd import hip
     dt = hip.dtype_id(dname)
+    taken = hip.attention_route(dt, (1,), (1,), (1,), (1,), B=B, heads=heads, Nq=Nq, Nkv=Nkv, D=D, q_bs=8, k_bs=8, v_bs=8, o_bs=8, q_rs=8, k_rs=8, v_rs=8, o_rs=8)
+    assert hip.attn_route_name(taken) == {(200, 40): "mfma32-d40 ragged", (130, 80): "reg80 self", (70, 160): "w4x32", (150, 512): "d512-w4", (100, 32): "dma64 cross",
+                                          (64, 40): "dma64 cross", (129, 64): "dma64 self"}[(Nq, D)]        # (strides do not enter the route)
     g = torch.Generator().manual_seed(5)
     C = heads * D
     q = _r(torch.randn(B, Nq, heads, D, generator=g), td)
@@ -381,6 +384,8 @@ def test_attention_temporal(gpu, dname, td, ulp, Fr, HW, heads, D):
     """b = pixel, i = frame: rows of the [F*HW, 3C] QKV matrix are gathered with stride HW*3C."""
     from videovanish_amd import hip
     dt = hip.dtype_id(dname)
+    taken = hip.attention_route(dt, (1,), (1,), (1,), (1,), B=HW, heads=heads, Nq=Fr, Nkv=Fr, D=D, q_bs=8, k_bs=8, v_bs=8, o_bs=8, q_rs=8, k_rs=8, v_rs=8, o_rs=8)
+    assert hip.attn_route_name(taken) == {40: "short", 80: "short", 160: "short-2w", 32: "short"}[D]
     g = torch.Generator().manual_seed(6)
     C = heads * D
     qkv = _r(torch.randn(Fr, HW, 3, heads, D, generator=g), td)

@@ -133,6 +133,10 @@ def test_attention_split_kv(hipmod, D, Nq, Nk):
     k = k * 1.5
     o_split, o_one = torch.empty(Nq, I, dtype=torch.float16, device=_dev()), torch.empty(Nq, I, dtype=torch.float16, device=_dev())
     kw = dict(heads=heads, Nq=Nq, Nkv=Nk, D=D, q_rs=I, k_rs=I, v_rs=I, o_rs=I, q_hs=D, k_hs=D, v_hs=D)
+    # the routes of the chunk launch (4 batches of Nk / 4 keys, with lse) and of the unsplit launch
+    taken = (hip.attention_route(hip.F16, q, k, v, o_split, B=4, q_bs=0, k_bs=Nk // 4 * I, v_bs=Nk // 4 * I, o_bs=Nq * I, lse=(1,), **dict(kw, Nkv=Nk // 4)),
+             hip.attention_route(hip.F16, q, k, v, o_one, B=1, q_bs=0, k_bs=0, v_bs=0, o_bs=0, **kw))
+    assert tuple(hip.attn_route_name(r) for r in taken) == {256: ("w8x16", "w8x16"), 64: ("dma64 cross", "dma64 self"), 80: ("reg80 self", "reg80 self")}[D]
     hip.attention_split_kv(hip.F16, q, k, v, o_split, S=4, **kw)
     hip.attention(hip.F16, q, k, v, o_one, B=1, q_bs=0, k_bs=0, v_bs=0, o_bs=0, **kw)
     sep = lambda t: t.float().cpu().reshape(t.shape[0], heads, D).transpose(0, 1)[None]

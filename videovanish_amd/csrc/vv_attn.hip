@@ -318,8 +318,7 @@ int attn_launch(const vv_attn_params& p, hipStream_t st) {
     constexpr int BQ = NW * QT * 16;
     const size_t lds = DMA ? 0 : (size_t)KVT * (PK + PV);
     const int nqt = (p.Nq + BQ - 1) / BQ;
-    const int64_t nblk = (int64_t)p.B * p.heads * nqt;
-    if (nblk > 0x7fffffff) VV_FAIL(VV_E_ARG, "vv_attention: grid too large");
+    const int64_t nblk = (int64_t)p.B * p.heads * nqt;      // fits a grid: attn_route (vv_attn_common.h) refuses the launch otherwise, with BQ from attn_route_block_queries
     auto kern = attn_kernel<T, D, QT, KVT, NW, PREFETCH, OCC, DMA, KIND>;
     static bool attr_done = false;
     if (!attr_done && lds > 48 * 1024) {
@@ -332,54 +331,60 @@ int attn_launch(const vv_attn_params& p, hipStream_t st) {
     return VV_OK;
 }
 
+// launches a route of attn_route_generic (vv_attn_common.h: the rules; here: why the thresholds are where they are)
 template <typename T, int D>
-int attn_dispatch(const vv_attn_params& p, hipStream_t st) {
+int attn_dispatch(const int route, const vv_attn_params& p, hipStream_t st) {
+    const int form = route & ~15;
     if constexpr (D >= 512) {
         // (round 6: eight waves of 16 queries instead of four -- the waves share the block's 32-key K / V tiles: the VAE mid attention, 4 frames x 14400 tokens, 4.32 -> 3.58 ms;
         //  profiles/r6_attn160_ab.txt)
-        if (p.Nq >= 256) return attn_launch<T, D, 1, 32, 8, false>(p, st);
-        return attn_launch<T, D, 1, 32, 4, false>(p, st);
+        if (form == VV_ATTN_ROUTE_D512_W8) return attn_launch<T, D, 1, 32, 8, false>(p, st);
+        if (form == VV_ATTN_ROUTE_D512_W4) return attn_launch<T, D, 1, 32, 4, false>(p, st);
     } else {
         // short sequences (temporal attention over <=32 frames, tiny test shapes): one wave per block, 32-key tiles
         // (round 6: at d = 160 two waves of 16 queries share the one 32-key tile of a temporal attention: 0.0865 -> 0.072 ms at 32 frames x 920 pixels; d = 80: +2 %, unchanged;
         //  profiles/r6_attn160_ab.txt)
-        if (D >= 128 && p.Nq <= 32 && p.Nkv <= 32 && p.Nq > 16) return attn_launch<T, D, 1, 32, 2, true>(p, st);
-        if (p.Nq <= 32 && p.Nkv <= 32) return attn_launch<T, D, 2, 32, 1, true>(p, st);
+        if constexpr (D >= 128) {
+            if (form == VV_ATTN_ROUTE_SHORT_2W) return attn_launch<T, D, 1, 32, 2, true>(p, st);
+        }
+        if (form == VV_ATTN_ROUTE_SHORT) return attn_launch<T, D, 2, 32, 1, true>(p, st);
         if constexpr (D <= 80) {
             // default for d <= 64: K/V by LDS-DMA, double buffered, 3 waves/SIMD (d = 80 would spill: stays register staged)
-            const bool cross = p.Nkv < 128 && p.Nq != p.Nkv;
-            if (D <= 64) return cross ? attn_launch<T, D, 2, 64, 4, false, 3, true, 1>(p, st) : attn_launch<T, D, 2, 64, 4, false, 3, true, 0>(p, st);
-            return cross ? attn_launch<T, D, 2, 64, 4, true, 1, false, 1>(p, st) : attn_launch<T, D, 2, 64, 4, true, 1, false, 0>(p, st);
+            const bool cross = (route & VV_ATTN_ROUTE_CROSS) != 0;
+            if constexpr (D <= 64) {
+                if (form == VV_ATTN_ROUTE_DMA64) return cross ? attn_launch<T, D, 2, 64, 4, false, 3, true, 1>(p, st) : attn_launch<T, D, 2, 64, 4, false, 3, true, 0>(p, st);
+            } else {
+                if (form == VV_ATTN_ROUTE_REG80) return cross ? attn_launch<T, D, 2, 64, 4, true, 1, false, 1>(p, st) : attn_launch<T, D, 2, 64, 4, true, 1, false, 0>(p, st);
+            }
+        } else {
+            // one long head (SAM 2 memory attention: d = 256, 4096 queries x up to 28736 keys) is 32 blocks whatever the block shape below 8 waves:
+            // eight waves of 16 queries keep the block's K/V tile loads covered (1.80 -> 1.05 ms; blocks of fewer than four waves are 7x slower:
+            // the register-staged loader wants 256 threads), profiles/r3_sam2_attn256_ab.txt
+            // d = 160 spatial self-attention (level 2: 32 frames x 8 heads x 920 tokens at 720p): eight waves of 16 queries share a block's K / V tile loads --
+            // 0.372 -> 0.325 ms (+14.5 %) against four waves of 32 queries; four waves of 16: 0.329; 32-key tiles: 0.509 (round 6, profiles/r6_attn160_ab.txt)
+            // (... and the level-2 cross attention to the 77 text tokens: 0.089 -> 0.076 ms; d = 80 cross attention: no gain, unchanged)
+            if constexpr (D == 256 || D == 160) {
+                if (form == VV_ATTN_ROUTE_W8x16) return attn_launch<T, D, 1, 64, 8, true>(p, st);
+            }
+            if (form == VV_ATTN_ROUTE_W4x32) return attn_launch<T, D, 2, 64, 4, true>(p, st);
         }
-        // one long head (SAM 2 memory attention: d = 256, 4096 queries x up to 28736 keys) is 32 blocks whatever the block shape below 8 waves:
-        // eight waves of 16 queries keep the block's K/V tile loads covered (1.80 -> 1.05 ms; blocks of fewer than four waves are 7x slower:
-        // the register-staged loader wants 256 threads), profiles/r3_sam2_attn256_ab.txt
-        if constexpr (D == 256) {
-            if ((int64_t)p.B * p.heads * ((p.Nq + 127) / 128) <= 128) return attn_launch<T, D, 1, 64, 8, true>(p, st);
-        }
-        // d = 160 spatial self-attention (level 2: 32 frames x 8 heads x 920 tokens at 720p): eight waves of 16 queries share a block's K / V tile loads --
-        // 0.372 -> 0.325 ms (+14.5 %) against four waves of 32 queries; four waves of 16: 0.329; 32-key tiles: 0.509 (round 6, profiles/r6_attn160_ab.txt)
-        // (... and the level-2 cross attention to the 77 text tokens: 0.089 -> 0.076 ms; d = 80 cross attention: no gain, unchanged)
-        if constexpr (D == 160) {
-            if (p.Nq >= 256) return attn_launch<T, D, 1, 64, 8, true>(p, st);
-        }
-        return attn_launch<T, D, 2, 64, 4, true>(p, st);
     }
+    VV_FAIL(VV_E_UNSUPPORTED, "vv_attention: route 0x%x is not built at head dim %d", route, D);
 }
 
 template <typename T>
-int attn_by_d(const vv_attn_params& p, hipStream_t st) {
+int attn_by_d(const int route, const vv_attn_params& p, hipStream_t st) {
     switch (p.D) {
 #if VV_ATTN_PART == 0      // small head dims: built with -mllvm -amdgpu-mfma-vgpr-form (accumulators in arch VGPRs)
-        case 32: return attn_dispatch<T, 32>(p, st);
-        case 40: return attn_dispatch<T, 40>(p, st);
-        case 64: return attn_dispatch<T, 64>(p, st);
-        case 80: return attn_dispatch<T, 80>(p, st);
+        case 32: return attn_dispatch<T, 32>(route, p, st);
+        case 40: return attn_dispatch<T, 40>(route, p, st);
+        case 64: return attn_dispatch<T, 64>(route, p, st);
+        case 80: return attn_dispatch<T, 80>(route, p, st);
 #else                      // large head dims need the AGPR half of the register file for O^T
-        case 128: return attn_dispatch<T, 128>(p, st);
-        case 160: return attn_dispatch<T, 160>(p, st);
-        case 256: return attn_dispatch<T, 256>(p, st);
-        case 512: return attn_dispatch<T, 512>(p, st);
+        case 128: return attn_dispatch<T, 128>(route, p, st);
+        case 160: return attn_dispatch<T, 160>(route, p, st);
+        case 256: return attn_dispatch<T, 256>(route, p, st);
+        case 512: return attn_dispatch<T, 512>(route, p, st);
 #endif
         default: VV_FAIL(VV_E_UNSUPPORTED, "vv_attention: head dim %d not built (32,40,64,80,128,160,256,512)", p.D);
     }
@@ -423,29 +428,22 @@ extern "C" int vv_attention_merge(const void* o_parts, const float* lse, int S, 
     return VV_OK;
 }
 
-extern "C" int vv_attention_large_d(const vv_attn_params* pp, int dtype, void* stream);
-extern "C" int vv_attention_mfma32(const vv_attn_params* pp, int dtype, void* stream);
+extern "C" int vv_attention_large_d(const vv_attn_params* pp, int dtype, int route, void* stream);
+extern "C" int vv_attention_mfma32(const vv_attn_params* pp, int dtype, int route, void* stream);
+
+extern "C" int vv_attention_route(const vv_attn_params* pp, int dtype) { return attn_route(pp, dtype); }
 
 extern "C" int vv_attention(const vv_attn_params* pp, int dtype, void* stream) {
-    if (!pp) VV_FAIL(VV_E_ARG, "vv_attention: null params");
+    const int route = attn_route(pp, dtype);
+    if (route < 0) return route;
     const vv_attn_params& p = *pp;
-    if (!p.q || !p.k || !p.v || !p.o) VV_FAIL(VV_E_ARG, "vv_attention: null pointer");
-    if (p.B <= 0 || p.heads <= 0 || p.Nq <= 0 || p.Nkv <= 0) VV_FAIL(VV_E_ARG, "vv_attention: empty problem");
-    if ((p.q_rs | p.k_rs | p.v_rs | p.o_rs | p.q_bs | p.k_bs | p.v_bs | p.o_bs) & 3) VV_FAIL(VV_E_ARG, "vv_attention: strides must be multiples of 4 elements (q/k/v: 8)");
-    if ((p.q_rs | p.k_rs | p.v_rs | p.q_bs | p.k_bs | p.v_bs | p.q_hs | p.k_hs | p.v_hs) & 7) VV_FAIL(VV_E_ARG, "vv_attention: q/k/v strides must be multiples of 8 elements");
-    if (p.o_hs & 3) VV_FAIL(VV_E_ARG, "vv_attention: o_hs must be a multiple of 4 elements");
-    if (dtype != VV_BF16 && dtype != VV_F16) VV_FAIL(VV_E_ARG, "vv_attention: bad dtype");
-    if (p.lse && p.D == 40) VV_FAIL(VV_E_UNSUPPORTED, "vv_attention: lse output is not available at D = 40");
-    if (p.D == 40 || p.D == 80) {      // vv_attn32.hip: the 32x32x16 kernels with an optimistic softmax reference take the spatial self-attention shapes
-        const int r = vv_attention_mfma32(pp, dtype, stream);
-        if (r != -1000) return r;
-    }
-    if (p.D > 80) return vv_attention_large_d(pp, dtype, stream);
-    return dtype == VV_BF16 ? attn_by_d<BF16>(p, (hipStream_t)stream) : attn_by_d<F16>(p, (hipStream_t)stream);
+    if ((route & ~15) >= VV_ATTN_ROUTE_MFMA32_D40) return vv_attention_mfma32(pp, dtype, route, stream);      // vv_attn32.hip: the 32x32x16 kernels with an optimistic softmax reference
+    if (p.D > 80) return vv_attention_large_d(pp, dtype, route, stream);
+    return dtype == VV_BF16 ? attn_by_d<BF16>(route, p, (hipStream_t)stream) : attn_by_d<F16>(route, p, (hipStream_t)stream);
 }
 #else
-extern "C" int vv_attention_large_d(const vv_attn_params* pp, int dtype, void* stream) {
+extern "C" int vv_attention_large_d(const vv_attn_params* pp, int dtype, int route, void* stream) {
     const vv_attn_params& p = *pp;
-    return dtype == VV_BF16 ? attn_by_d<BF16>(p, (hipStream_t)stream) : attn_by_d<F16>(p, (hipStream_t)stream);
+    return dtype == VV_BF16 ? attn_by_d<BF16>(route, p, (hipStream_t)stream) : attn_by_d<F16>(route, p, (hipStream_t)stream);
 }
 #endif

@@ -1,6 +1,6 @@
 // Spatial self-attention on the FULL-SIZE matrix instruction (v_mfma_f32_32x32x16) with an optimistic softmax reference: head dims 40 (UNet level 0: the
 // dominant kernel of the denoise step) and 80 (level 1; SAM 2's 72 -> 80 padded heads).  Split off vv_attn.hip (which keeps the 16x16x32 flash kernels
-// of every other shape and calls vv_attention_mfma32 first for D = 40 / 80); built with -mllvm -amdgpu-mfma-vgpr-form like the small-head part there.
+// of every other shape and calls vv_attention_mfma32 only for a VV_ATTN_ROUTE_MFMA32_* route of attn_route, vv_attn_common.h); built with -mllvm -amdgpu-mfma-vgpr-form like the small-head part there.
 #include <type_traits>
 #include "vv_attn_common.h"
 
@@ -154,11 +154,10 @@ __device__ __forceinline__ uint4 a32_scale_q(const uint4 f, const float scale) {
 // one launcher: `ragged` / `whole` = the kernel's instantiations for a last key tile of fewer than 64 keys / whole tiles, BQ = queries per block
 typedef void (*a32_kernel_t)(const vv_attn_params, const int);
 template <int NW, int BQ>
-int a32_launch(const a32_kernel_t ragged, const a32_kernel_t whole, const vv_attn_params& p, hipStream_t st, const char* what) {
+int a32_launch(const a32_kernel_t ragged, const a32_kernel_t whole, const int route, const vv_attn_params& p, hipStream_t st, const char* what) {
     const int nqt = (p.Nq + BQ - 1) / BQ;
-    const int64_t nblk = (int64_t)p.B * p.heads * nqt;
-    if (nblk > 0x7fffffff) VV_FAIL(VV_E_ARG, "vv_attention: grid too large");
-    hipLaunchKernelGGL(p.Nkv % 64 ? ragged : whole, dim3((unsigned)nblk), dim3(NW * 64), 0, st, p, nqt);
+    const int64_t nblk = (int64_t)p.B * p.heads * nqt;      // fits a grid: attn_route (vv_attn_common.h) refuses the launch otherwise
+    hipLaunchKernelGGL((route & VV_ATTN_ROUTE_RAGGED) ? ragged : whole, dim3((unsigned)nblk), dim3(NW * 64), 0, st, p, nqt);
     VV_CHECK_LAUNCH(what);
     return VV_OK;
 }
@@ -896,26 +895,22 @@ __global__ __launch_bounds__(NW * 64, OCC) void attn80_kernel(const vv_attn_para
 
 // four waves per block; d = 40: 64 queries per wave at 2 waves per SIMD on long sequences, 32 queries at 3 waves per SIMD below 1024
 template <typename T>
-int attn40_launch(const vv_attn_params& p, hipStream_t st) {
-    if (p.Nq >= 1024) return a32_launch<4, 256>(attn40q2_kernel<T, 4, 2, true>, attn40q2_kernel<T, 4, 2, false>, p, st, "vv_attention(d40, 64 queries per wave)");
-    return a32_launch<4, 128>(attn40_kernel<T, 4, 3, true>, attn40_kernel<T, 4, 3, false>, p, st, "vv_attention(d40, 32x32x16)");
+int attn40_launch(const int route, const vv_attn_params& p, hipStream_t st) {
+    if ((route & ~15) == VV_ATTN_ROUTE_MFMA32_D40_Q2)
+        return a32_launch<4, 256>(attn40q2_kernel<T, 4, 2, true>, attn40q2_kernel<T, 4, 2, false>, route, p, st, "vv_attention(d40, 64 queries per wave)");
+    return a32_launch<4, 128>(attn40_kernel<T, 4, 3, true>, attn40_kernel<T, 4, 3, false>, route, p, st, "vv_attention(d40, 32x32x16)");
 }
 template <typename T>
-int attn80_launch(const vv_attn_params& p, hipStream_t st) {
-    return a32_launch<4, 256>(attn80_kernel<T, 4, 2, true>, attn80_kernel<T, 4, 2, false>, p, st, "vv_attention(d80, 64 queries per wave)");
+int attn80_launch(const int route, const vv_attn_params& p, hipStream_t st) {
+    return a32_launch<4, 256>(attn80_kernel<T, 4, 2, true>, attn80_kernel<T, 4, 2, false>, route, p, st, "vv_attention(d80, 64 queries per wave)");
 }
 
 }  // namespace
 
-// the shapes these kernels take (anything else: -1000, the caller falls back to the 16x16x32 kernels): self-attention (or any Nq / Nkv that is not the
-// 77-key cross-attention shape) over at least 64 keys, more than 32 queries; d = 40: 64 queries per wave (2 waves/SIMD) on long sequences, 32 (3 waves/SIMD)
-// below 1024; d = 80: from 512 queries
-extern "C" int vv_attention_mfma32(const vv_attn_params* pp, int dtype, void* stream) {
+// launches a VV_ATTN_ROUTE_MFMA32_* route (attn_route_mfma32 in vv_attn_common.h holds the shapes these kernels take)
+extern "C" int vv_attention_mfma32(const vv_attn_params* pp, int dtype, int route, void* stream) {
     const vv_attn_params& p = *pp;
     hipStream_t st = (hipStream_t)stream;
-    const bool cross = p.Nkv < 128 && p.Nq != p.Nkv;
-    if ((p.Nq <= 32 && p.Nkv <= 32) || cross || p.Nkv < 64) return -1000;
-    if (p.D == 40) return dtype == VV_BF16 ? attn40_launch<BF16>(p, st) : attn40_launch<F16>(p, st);
-    if (p.D == 80 && p.Nq >= 512) return dtype == VV_BF16 ? attn80_launch<BF16>(p, st) : attn80_launch<F16>(p, st);
-    return -1000;
+    if ((route & ~15) == VV_ATTN_ROUTE_MFMA32_D80) return dtype == VV_BF16 ? attn80_launch<BF16>(route, p, st) : attn80_launch<F16>(route, p, st);
+    return dtype == VV_BF16 ? attn40_launch<BF16>(route, p, st) : attn40_launch<F16>(route, p, st);
 }

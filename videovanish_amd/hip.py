@@ -129,6 +129,7 @@ SIGNATURES = {
     "vv_gn_affine_frames": (I, (P, P, P, I, I, I, P, P)),
     "vv_layernorm": (I, (P, I, I, P, P, P, I, P, I, P)),
     "vv_attention": (I, (P, I, P)),
+    "vv_attention_route": (I, (P, I)),
     "vv_attention_merge": (I, (P, P, I, I, I, I, I, P, I, P)),
     "vv_axpby_f32": (I, (P, P, Fl, Fl, P, L, P)),
     "vv_sched_step": (I, (P, P, P, Fl, Fl, Fl, Fl, Fl, P, L, P)),
@@ -463,21 +464,61 @@ def attention_q_scale(D):
     return float(D) ** -0.5 * 1.4426950408889634
 
 
+# vv_attention_route codes (vvhip.h VV_ATTN_ROUTE_*): route = form | flags
+ATTN_ROUTE_CROSS, ATTN_ROUTE_RAGGED = 1, 2
+ATTN_ROUTE_SHORT, ATTN_ROUTE_SHORT_2W, ATTN_ROUTE_DMA64, ATTN_ROUTE_REG80, ATTN_ROUTE_W4x32, ATTN_ROUTE_W8x16 = 0x10, 0x20, 0x30, 0x40, 0x50, 0x60
+ATTN_ROUTE_D512_W4, ATTN_ROUTE_D512_W8, ATTN_ROUTE_MFMA32_D40, ATTN_ROUTE_MFMA32_D40_Q2, ATTN_ROUTE_MFMA32_D80 = 0x70, 0x80, 0x90, 0xa0, 0xb0
+_ATTN_ROUTES = {ATTN_ROUTE_SHORT: "short", ATTN_ROUTE_SHORT_2W: "short-2w", ATTN_ROUTE_DMA64: "dma64", ATTN_ROUTE_REG80: "reg80", ATTN_ROUTE_W4x32: "w4x32",
+                ATTN_ROUTE_W8x16: "w8x16", ATTN_ROUTE_D512_W4: "d512-w4", ATTN_ROUTE_D512_W8: "d512-w8", ATTN_ROUTE_MFMA32_D40: "mfma32-d40",
+                ATTN_ROUTE_MFMA32_D40_Q2: "mfma32-d40-q2", ATTN_ROUTE_MFMA32_D80: "mfma32-d80"}
+_ATTN_ROUTE_FLAGS = {ATTN_ROUTE_DMA64: {0: " self", ATTN_ROUTE_CROSS: " cross"}, ATTN_ROUTE_REG80: {0: " self", ATTN_ROUTE_CROSS: " cross"},
+                     ATTN_ROUTE_MFMA32_D40: {0: " whole", ATTN_ROUTE_RAGGED: " ragged"}, ATTN_ROUTE_MFMA32_D40_Q2: {0: " whole", ATTN_ROUTE_RAGGED: " ragged"},
+                     ATTN_ROUTE_MFMA32_D80: {0: " whole", ATTN_ROUTE_RAGGED: " ragged"}}
+
+
+def attn_route_name(code):
+    """Readable name of a vv_attention route: "short", "dma64 cross", "mfma32-d40 ragged", ..."""
+    form, flags = code & ~15, code & 15
+    if form not in _ATTN_ROUTES or flags not in _ATTN_ROUTE_FLAGS.get(form, {0: ""}):
+        raise ValueError(f"not a vv_attention route: {code}")
+    return _ATTN_ROUTES[form] + _ATTN_ROUTE_FLAGS.get(form, {0: ""})[flags]
+
+
+def attention_label(Nq, Nkv):
+    """The kind in the profile key attention[kind,dD] (bench.py's kernel_times_s reads these keys): temporal = the short shapes, cross = the 77 text tokens"""
+    return "temporal" if (Nq <= 32 and Nkv <= 32) else ("cross" if Nkv < 128 and Nq != Nkv else "spatial")
+
+
 def attention(dtype, q, k, v, out, *, B, heads, Nq, Nkv, D, q_bs, k_bs, v_bs, o_bs, q_rs, k_rs, v_rs, o_rs, q_off=0, k_off=0, v_off=0,
-              q_hs=0, k_hs=0, v_hs=0, q_prescaled=False, scale=None, lse=None, o_hs=0):
+              q_hs=0, k_hs=0, v_hs=0, q_prescaled=False, scale=None, lse=None, o_hs=0, _route=False):
     """q/k/v/out: h16 tensors (any shape); element offsets *_off select a column block inside a fused QKV buffer.
     q_prescaled: q already carries D**-0.5 * log2(e) (attention_q_scale(D) folded into the query projection)."""
-    _need_cuda(q, k, v, out)
-    es = 2
-    p = AttnParams(q=q.data_ptr() + q_off * es, k=k.data_ptr() + k_off * es, v=v.data_ptr() + v_off * es, o=_p(out),
-                   q_bs=q_bs, k_bs=k_bs, v_bs=v_bs, o_bs=o_bs, q_rs=q_rs, k_rs=k_rs, v_rs=v_rs, o_rs=o_rs, B=B, heads=heads, Nq=Nq,
-                   Nkv=Nkv, D=D, scale=float(D) ** -0.5 if scale is None else float(scale), q_hs=q_hs, k_hs=k_hs, v_hs=v_hs, q_prescaled=1 if q_prescaled else 0, lse=_p(lse), o_hs=o_hs)
-    kind = "temporal" if (Nq <= 32 and Nkv <= 32) else ("cross" if Nkv < 128 and Nq != Nkv else "spatial")
+    if _route:      # attention_route: nothing is launched, pointers are passed as null / non-null flags
+        flag = lambda t: 0 if t is None else 1
+        p = AttnParams(q=flag(q), k=flag(k), v=flag(v), o=flag(out), lse=flag(lse))
+    else:
+        _need_cuda(q, k, v, out)
+        es = 2
+        p = AttnParams(q=q.data_ptr() + q_off * es, k=k.data_ptr() + k_off * es, v=v.data_ptr() + v_off * es, o=_p(out), lse=_p(lse))
+    p.q_bs, p.k_bs, p.v_bs, p.o_bs, p.q_rs, p.k_rs, p.v_rs, p.o_rs = q_bs, k_bs, v_bs, o_bs, q_rs, k_rs, v_rs, o_rs
+    p.B, p.heads, p.Nq, p.Nkv, p.D = B, heads, Nq, Nkv, D
+    p.scale = float(D) ** -0.5 if scale is None else float(scale)
+    p.q_hs, p.k_hs, p.v_hs, p.o_hs, p.q_prescaled = q_hs, k_hs, v_hs, o_hs, 1 if q_prescaled else 0
+    if _route:
+        return lib().vv_attention_route(C.byref(p), dtype)
+    kind = attention_label(Nq, Nkv)
     if PROFILE_SHAPES:
         kind = f"B{B},N{Nq}|" + kind
     with _Prof(f"attention[{kind},d{D}]", 4.0 * B * heads * Nq * Nkv * D, 2 * B * heads * D * (2 * Nq + 2 * Nkv)):
         _check(lib().vv_attention(C.byref(p), dtype, _stream()), "vv_attention")
     return out
+
+
+def attention_route(dtype, q, k, v, out, **kw):
+    """The kernel vv_attention would launch for attention(dtype, q, k, v, out, **kw) (same keywords), as an ATTN_ROUTE_* code (attn_route_name), or the negative
+    VV_E_* code the launch would be refused with.  Needs no GPU: q / k / v / out / lse may be tensors on any device or bare shapes (None = a null pointer);
+    only the keywords decide."""
+    return attention(dtype, q, k, v, out, _route=True, **kw)
 
 
 def deform_im2col(dtype, x, *, B, H, W, kh=3, kw=3, stride=1, pad=1, dil=1, deform_groups=1, offset=None, mask=None, raw=None, flow=None,
