@@ -8,7 +8,9 @@ inference: only the runs of masked frames are processed, and nothing crosses a h
 $VV_SPANS), mask_clean (mask clean-up between the dilation and the planners: speckles dropped, dropouts bridged, the mask grown in time:
 videovanish_amd/maskclean.py; also configure(mask_clean=...) and $VV_MASK_CLEAN), tone_match (seam tone matching: the model's pixels are fitted to
 the ring of unmasked pixels round the mask before the composite: videovanish_amd/tonematch.py; also configure(tone_match=...) and $VV_TONE_MATCH), grain_match (seam grain matching: the pasted pixels get the grain
-the original pixels of that ring have and the model's lack: videovanish_amd/grainmatch.py; also configure(grain_match=...) and $VV_GRAIN_MATCH).
+the original pixels of that ring have and the model's lack: videovanish_amd/grainmatch.py; also configure(grain_match=...) and $VV_GRAIN_MATCH), seam_blend (seam membrane blending: the
+difference original - model on that ring, interpolated harmonically into the hole and added to the pasted pixels: videovanish_amd/seamblend.py;
+also configure(seam_blend=...) and $VV_SEAM_BLEND).
 There is no CPU fallback: without the HIP extension / a GPU this raises.
 
 This file is the boundary: the reference's names and module state, the settings, and the stages (weights, prior, model) that read that state.
@@ -21,7 +23,7 @@ import numpy as np
 import torch
 
 from videovanish_amd import hip, infill
-from videovanish_amd import grainmatch, maskclean, tonematch
+from videovanish_amd import grainmatch, maskclean, seamblend, tonematch
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
 from videovanish_amd.config import RunConfig
@@ -47,10 +49,12 @@ _tone_match = None      # configure(tone_match=...): seam tone matching for call
 last_tone_match = None  # the infill.ToneMatchReport of the last run_infill_on_frames call; None when the stage did not run
 _grain_match = None     # configure(grain_match=...): seam grain matching for calls that do not pass grain_match= themselves
 last_grain_match = None # the infill.GrainMatchReport of the last run_infill_on_frames call; None when the stage did not run
+_seam_blend = None      # configure(seam_blend=...): seam membrane blending for calls that do not pass seam_blend= themselves
+last_seam_blend = None  # the infill.SeamBlendReport of the last run_infill_on_frames call; None when the stage did not run
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
-              mask_clean=None, tone_match=None, grain_match=None):
+              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -72,8 +76,12 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     tone_match = None / "on" / "affine" / "offset" / "mode=offset,ring=8,smooth=0" (any subset) / a tonematch.ToneMatchConfig: seam tone matching
     for calls that do not pass tone_match=.
     grain_match = None / "on" / "luma" / "rgb" / "mode=rgb,ring=8,strength=0.8,seed=3" (any subset) / a grainmatch.GrainMatchConfig: seam grain
-    matching for calls that do not pass grain_match=."""
+    matching for calls that do not pass grain_match=.
+    seam_blend = None / "on" / "ring=12,presmooth=2,sweeps=8,max_shift=32,strength=1.0" (any subset) / a seamblend.SeamBlendConfig: seam membrane
+    blending for calls that do not pass seam_blend=."""
     global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi, _spans, _mask_clean, _tone_match, _grain_match
+    global _seam_blend
+    seamblend.as_config(seam_blend)
     grainmatch.as_config(grain_match)
     tonematch.as_config(tone_match)
     maskclean.as_config(mask_clean)
@@ -91,6 +99,7 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     _mask_clean = mask_clean
     _tone_match = tone_match
     _grain_match = grain_match
+    _seam_blend = seam_blend
 
 
 def _resolve_weights(ckpt):
@@ -171,10 +180,21 @@ def grain_match_config(grain_match=None):
     return grainmatch.as_config(os.environ.get("VV_GRAIN_MATCH"))
 
 
+def seam_blend_config(seam_blend=None, feather_px=None):
+    """The seam membrane blending setting a call runs with: its own seam_blend= argument, else configure(seam_blend=...), else $VV_SEAM_BLEND (on |
+    off | ring=N,presmooth=N,sweeps=N,max_shift=N,strength=X).  None = no blending.  seam_blend="off" (or False) asks for none whatever
+    configure() or the environment say.  feather_px: the call's feather, which the ring has to be wider than."""
+    if seam_blend is not None:
+        return seamblend.as_config(seam_blend, feather_px)
+    if _seam_blend is not None:
+        return seamblend.as_config(_seam_blend, feather_px)
+    return seamblend.as_config(os.environ.get("VV_SEAM_BLEND"), feather_px)
+
+
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
-                         mask_clean=None, tone_match=None, grain_match=None):
+                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -202,14 +222,21 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     capped) and adds stateless white noise of that level to every pasted pixel before the feathered composite (infill.finish), for the full
     frame and for every roi window, inside each span; the noise of a pixel depends on the seed, the frame's index in this call and the
     pixel's position in the frame only.  What it measured and added is kept in last_grain_match.  A model frame that equals the original on
-    the ring gives the bytes of the call without it."""
-    global last_mask_clean, last_tone_match, last_grain_match
+    the ring gives the bytes of the call without it.
+    seam_blend (seam membrane blending, opt-in): "on" / "ring=12,presmooth=2,sweeps=8,max_shift=32,strength=1.0" / a
+    videovanish_amd.seamblend.SeamBlendConfig interpolates, per frame and channel, the difference original - model from that ring harmonically
+    into the hole (after tone matching's table, when both are on) and adds this membrane to every pasted pixel before the grain and the
+    feathered composite (infill.finish), for the full frame and for every roi window, inside each span: a correction that varies across the
+    hole, which one gain and offset cannot give; in front of it tone matching fits its offset alone (gain 1), whatever its mode.  The ring must be wider than ceil(feather_px).  What it measured and added is kept in
+    last_seam_blend.  A model frame that equals the original on the ring gives the bytes of the call without it."""
+    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
     ccfg = mask_clean_config(mask_clean)
     tcfg = tone_match_config(tone_match)
     gcfg = grain_match_config(grain_match)
-    last_mask_clean = last_tone_match = last_grain_match = None
+    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = None
+    bcfg = seam_blend_config(seam_blend, feather_px if keep_unmasked_original else None)
     if rcfg is not None and compat_reference_early_return:
         raise ValueError("roi= (mask-region inference) cannot be combined with compat_reference_early_return=True")
     if scfg is not None and compat_reference_early_return:
@@ -220,6 +247,8 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         raise ValueError("tone_match= (seam tone matching) cannot be combined with compat_reference_early_return=True")
     if gcfg is not None and compat_reference_early_return:
         raise ValueError("grain_match= (seam grain matching) cannot be combined with compat_reference_early_return=True")
+    if bcfg is not None and compat_reference_early_return:
+        raise ValueError("seam_blend= (seam membrane blending) cannot be combined with compat_reference_early_return=True")
 
     if prog is not None: prog(5, "dilating frames")
     dev = get_device()
@@ -237,9 +266,12 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
 
     tone_parts = None if tcfg is None else []       # one report per clip call, in the order of the spans
     grain_parts = None if gcfg is None else []
+    blend_parts = None if bcfg is None else []
 
     def body(frames, dil, prior, p, frame0=0):
         more = {} if gcfg is None else dict(grain=gcfg, grain_out=grain_parts, frame0=frame0)     # passed only when grain matching is on
+        if bcfg is not None:                                                                       # likewise
+            more.update(blend=bcfg, blend_out=blend_parts)
         return infill.run_clip(frames, dil, prior, rcfg, stages, p, dev, feather_px, keep_unmasked_original, compat_reference_early_return,
                                tone=tcfg, tone_out=tone_parts, **more)
 
@@ -255,6 +287,8 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         last_tone_match = infill.tone_report(tone_parts, plan, T)
     if gcfg is not None:
         last_grain_match = infill.grain_report(grain_parts, plan, T)
+    if bcfg is not None:
+        last_seam_blend = infill.seam_blend_report(blend_parts, plan, T)
     return out
 
 
@@ -325,6 +359,16 @@ def _grain_match_arg(text):
     return text
 
 
+def _seam_blend_arg(text):
+    """--seam-blend's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --grain-match)."""
+    try:
+        if seamblend.as_config(text) is None:
+            raise ValueError("not a setting")
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return text
+
+
 def _mask_clean_arg(text):
     """--mask-clean's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --roi / --spans)."""
     try:
@@ -366,6 +410,10 @@ def main():
                     help="Seam grain matching before the composite: measure, over the flat part of the ring of unmasked pixels within `ring` px of the "
                          "mask, the grain the original pixels have and the model's lack, and add white noise of that level to every pasted pixel (on / "
                          "luma: one noise value per pixel; rgb: one per channel).  Prints one line with what it added.")
+    ap.add_argument("--seam-blend", type=_seam_blend_arg, default=None, metavar="on|ring=12,presmooth=2,sweeps=8,max_shift=32,strength=1.0",
+                    help="Seam membrane blending before the composite: interpolate the difference original - model from the ring of unmasked pixels "
+                         "within `ring` px of the mask harmonically into the hole and add it to every pasted pixel, so that the patch meets the "
+                         "original along the whole outline (a correction that varies across the hole).  Prints one line with what it added.")
     ap.add_argument("--cuts", type=span_plan.parse_cuts, default=None, metavar="120,431",
                     help="Frame indices (relative to --start_frame) where a new shot begins: used instead of the detector.")
     args = ap.parse_args()
@@ -388,6 +436,7 @@ def main():
     if args.mask_clean is not None: kw["mask_clean"] = args.mask_clean
     if args.tone_match is not None: kw["tone_match"] = args.tone_match
     if args.grain_match is not None: kw["grain_match"] = args.grain_match
+    if args.seam_blend is not None: kw["seam_blend"] = args.seam_blend
     out_frames = run_infill_on_frames(frames, mask_frames, propainer_frames=prior_frames, **kw)
     if args.mask_clean is not None and last_mask_clean is not None:
         r = last_mask_clean
@@ -402,6 +451,11 @@ def main():
         r = last_grain_match
         touched = (r.sigma_added > 0.0).any(axis=(0, 2, 3))
         print(f"grain match: grain added in {int(touched.sum())} of {touched.size} frames, largest sigma {float(r.sigma_added.max()):.2f}")
+    if args.seam_blend is not None and last_seam_blend is not None:
+        r = last_seam_blend
+        touched = (r.max_shift > 0.0).any(axis=(0, 2))
+        print(f"seam blend: membrane added in {int(touched.sum())} of {touched.size} frames, largest |shift| {float(r.max_shift.max()):.2f}, "
+              f"largest ring RMS {float(r.rms_diff.max()):.2f}")
     tools.write_video_frames_to_path(out_video, out_frames, fps, H0, W0)
 
 

@@ -1,0 +1,477 @@
+// Seam membrane blending (videovanish_amd/seamblend.py): the difference y - x on the ring round the mask, interpolated
+// harmonically into the hole and added to the pasted pixels.  The rules are include/vvblend.h's; all arithmetic is integer.
+//   vvb_ring_diff               level 0: classes (vv_ring_bits.h's ring, the statement vv_tone.hip and vv_grain.hip use) and the presmoothed
+//                               Q6 differences of the ring pixels; two launches on the tiles of ring_stats_kernel
+//   vvb_pull                    one level up: a coarse cell is the rounded mean of its known children
+//   vvb_relax                   the hot path: all sweeps of a level in ONE launch, a block's tile and a halo of `sweeps` cells in LDS
+//   vvb_solve                   the three in order over the caller's scratch
+//   vvb_paste_blend_composite   vvg_paste_grain_composite with the field added after the table
+// The sums go registers -> wave reduction -> 64-bit LDS atomics -> one set of 64-bit global integer atomics per block, as in vv_tone.hip.
+#include "vv_paste_px.h"
+#include "vv_ring_bits.h"
+#include "../../include/vvblend.h"
+#pragma clang fp contract(off)
+
+namespace {
+
+using vvring::TB;
+using vvring::TW;
+using vvring::TH;
+using vvring::u64;
+using vvpaste::window_px;
+constexpr int NSUM = VVB_NSUM;
+constexpr int PS = VVB_MAX_PRESMOOTH, MS = VVB_MAX_SWEEPS;
+constexpr int DW = TW + 2 * PS, DH = TH + 2 * PS;           // the staged differences: the tile and a halo of the largest presmooth
+static_assert(VVB_MAX_RING == vvring::MAX_RING, "the ring of vv_ring_bits.h");
+// |d| <= 255: a thread adds TH / 4 squares, a wave 64 threads; |m| <= 64 * 255: likewise
+static_assert(64ull * (TH / 4) * 255ull * 255ull < (1ull << 32) && 64ull * (TH / 4) * 64ull * VVB_MAX_SHIFT < (1ull << 32), "32-bit sums up to the wave");
+static_assert(64 * VVB_MAX_SHIFT <= 32767, "the field is int16");
+
+__device__ __forceinline__ unsigned wave_sum32(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned wave_max32(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor(v, o, 64));
+    return v;
+}
+// (2 s + n) // (2 n), the floor division, n > 0
+__device__ __forceinline__ int round_div(int s, int n) {
+    const int num = 2 * s + n, den = 2 * n;
+    int q = num / den;
+    if (num < 0 && q * den != num) --q;
+    return q;
+}
+
+// grid: tiles_x * tiles_y * T blocks, as ring_stats_kernel of vv_tone.hip.  Writes the classes of the tile's cells inside the window; reads the
+// mask only (bounds-checked against the frame, whatever the offsets hold).
+__global__ __launch_bounds__(TB) void classify_kernel(const uint8_t* __restrict__ mask, const int* __restrict__ offsets, int H, int W, int h, int w, int r,
+                                                      int tiles_x, int tiles_y, uint8_t* __restrict__ cls) {
+    __shared__ u64 rowbits[vvring::HALO_ROWS];
+    __shared__ u64 own[TH];
+    __shared__ u64 ringbits[TH];
+    const int tile = (int)blockIdx.x % (tiles_x * tiles_y), t = (int)blockIdx.x / (tiles_x * tiles_y);
+    const int tx0 = (tile % tiles_x) * TW, ty0 = (tile / tiles_x) * TH;
+    const int oy = offsets[t * 2 + 0], ox = offsets[t * 2 + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    vvring::ring_bits<false>(mask + (int64_t)t * H * W, H, W, oy, ox, tx0, ty0, h, w, r, rowbits, own, ringbits, nullptr);
+    const int xx = tx0 + lane;
+    if (xx >= w) return;                                                       // after the last barrier
+    for (int y = wave; y < TH; y += TB / 64) {
+        const int yy = ty0 + y;
+        if (yy >= h) break;
+        const int c = ((ringbits[y] >> lane) & 1ull) ? VVB_KNOWN : (((own[y] >> lane) & 1ull) ? VVB_UNKNOWN : VVB_INACTIVE);      // own: a mask byte of the frame
+        cls[((int64_t)t * h + yy) * w + xx] = (uint8_t)c;
+    }
+}
+
+// grid as classify_kernel, after it.  Stages the classes of the tile and a halo of ps cells, then d = y - x of the known cells among them, and
+// writes the tile's values: the presmoothed Q6 mean on known cells, 0 on the others.  Every read of cls / val lies inside the window, a known
+// cell lies inside the frame (the ring's definition), so every read of orig and patch is in bounds.
+__global__ __launch_bounds__(TB) void ring_diff_kernel(const uint8_t* __restrict__ patch, int Hm, int Wm, const uint8_t* __restrict__ orig,
+                                                       const int* __restrict__ offsets, const uint8_t* __restrict__ lut, int H, int W, int h, int w, int ps,
+                                                       int lim, int tiles_x, int tiles_y, const uint8_t* __restrict__ cls, int16_t* __restrict__ val,
+                                                       u64* __restrict__ sums) {
+    __shared__ int16_t ds[3][DH][DW];            // staged cell (i, j) = window pixel (tx0 + i - ps, ty0 + j - ps)
+    __shared__ uint8_t ks[DH][DW];               // 1: a known cell
+    __shared__ u64 tot[4];
+    const int tile = (int)blockIdx.x % (tiles_x * tiles_y), t = (int)blockIdx.x / (tiles_x * tiles_y);
+    const int tx0 = (tile % tiles_x) * TW, ty0 = (tile / tiles_x) * TH;
+    const int oy = offsets[t * 2 + 0], ox = offsets[t * 2 + 1];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sw = TW + 2 * ps, sh = TH + 2 * ps;
+    if (threadIdx.x < 4) tot[threadIdx.x] = 0;
+    const uint8_t* cl = cls + (int64_t)t * h * w;
+    int mine = 0;                                                              // a known cell of the tile itself
+    for (int k = threadIdx.x; k < sw * sh; k += TB) {
+        const int j = k / sw, i = k - j * sw;
+        const int xx = tx0 + i - ps, yy = ty0 + j - ps;
+        const bool known = xx >= 0 && xx < w && yy >= 0 && yy < h && cl[(int64_t)yy * w + xx] == VVB_KNOWN;
+        ks[j][i] = known ? 1 : 0;
+        mine |= known && i >= ps && i < ps + TW && j >= ps && j < ps + TH;
+    }
+    int16_t* vt = val + (int64_t)t * h * w * 3;
+    if (!__syncthreads_or(mine)) {                                             // no ring pixel: zeros, no image byte read
+        const int xx = tx0 + lane;
+        for (int y = wave; y < TH; y += TB / 64) {
+            const int yy = ty0 + y;
+            if (xx < w && yy < h) { int16_t* v = vt + ((int64_t)yy * w + xx) * 3; v[0] = 0; v[1] = 0; v[2] = 0; }
+        }
+        return;
+    }
+    const uint8_t* src = patch + (int64_t)t * Hm * Wm * 3;
+    const uint8_t* tab = lut + (int64_t)t * 3 * 256;
+    for (int k = threadIdx.x; k < sw * sh; k += TB) {
+        const int j = k / sw, i = k - j * sw;
+        int d[3] = {0, 0, 0};
+        if (ks[j][i]) {
+            const int xx = tx0 + i - ps, yy = ty0 + j - ps;
+            uint8_t p[3];
+            window_px(src, Hm, Wm, xx, yy, h, w, p);
+            const uint8_t* o = orig + (((int64_t)t * H + (oy + yy)) * W + (ox + xx)) * 3;
+            d[0] = (int)o[0] - (int)tab[p[0]]; d[1] = (int)o[1] - (int)tab[256 + p[1]]; d[2] = (int)o[2] - (int)tab[512 + p[2]];
+        }
+        ds[0][j][i] = (int16_t)d[0]; ds[1][j][i] = (int16_t)d[1]; ds[2][j][i] = (int16_t)d[2];
+    }
+    __syncthreads();
+
+    unsigned acc[4] = {0, 0, 0, 0};
+    const int xx = tx0 + lane;
+    for (int y = wave; y < TH; y += TB / 64) {
+        const int yy = ty0 + y;
+        if (xx >= w || yy >= h) continue;
+        int v[3] = {0, 0, 0};
+        if (ks[y + ps][lane + ps]) {
+            int n = 0, s[3] = {0, 0, 0};
+            for (int dy = 0; dy <= 2 * ps; ++dy)
+                for (int dx = 0; dx <= 2 * ps; ++dx) {                         // unknown and inactive cells hold d = 0, k = 0
+                    n += ks[y + dy][lane + dx];
+                    s[0] += ds[0][y + dy][lane + dx]; s[1] += ds[1][y + dy][lane + dx]; s[2] += ds[2][y + dy][lane + dx];
+                }
+            acc[0] += 1;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int d = ds[c][y + ps][lane + ps];
+                acc[1 + c] += (unsigned)(d * d);
+                v[c] = min(max(round_div(64 * s[c], n), -lim), lim);           // |64 s| <= 64 * 81 * 255
+            }
+        }
+        int16_t* o = vt + ((int64_t)yy * w + xx) * 3;
+        o[0] = (int16_t)v[0]; o[1] = (int16_t)v[1]; o[2] = (int16_t)v[2];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const unsigned s = wave_sum32(acc[i]);
+        if (lane == 0 && s) atomicAdd(&tot[i], (u64)s);
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && tot[threadIdx.x]) atomicAdd(&sums[(int64_t)t * NSUM + threadIdx.x], tot[threadIdx.x]);
+}
+
+// one thread per cell of the level above
+__global__ __launch_bounds__(TB) void pull_kernel(const uint8_t* __restrict__ cls, const int16_t* __restrict__ val, int T, int hl, int wl, int hu, int wu,
+                                                  uint8_t* __restrict__ cls_up, int16_t* __restrict__ val_up) {
+    const int64_t n = (int64_t)T * hu * wu;
+    const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const int X = (int)(i % wu), Y = (int)((i / wu) % hu), t = (int)(i / ((int64_t)wu * hu));
+    int cnt = 0, unk = 0, s[3] = {0, 0, 0};
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int y = 2 * Y + a, x = 2 * X + b;
+            if (y >= hl || x >= wl) continue;
+            const int64_t k = ((int64_t)t * hl + y) * wl + x;
+            const int c = cls[k];
+            unk |= c == VVB_UNKNOWN;
+            if (c == VVB_KNOWN) { ++cnt; s[0] += val[k * 3]; s[1] += val[k * 3 + 1]; s[2] += val[k * 3 + 2]; }
+        }
+    cls_up[i] = (uint8_t)(cnt ? VVB_KNOWN : (unk ? VVB_UNKNOWN : VVB_INACTIVE));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) val_up[i * 3 + c] = (int16_t)(cnt ? round_div(s[c], cnt) : 0);
+}
+
+// grid: tiles_x * tiles_y * T blocks over the hl x wl level.  Dynamic LDS, for sw = TW + 2 s columns and sh = TH + 2 s rows: two planar int16
+// fields [3][sh][sw], the classes and the neighbour flags [sh][sw] u8 each: 14 sw sh bytes (86016 at s = 16, 53760 at s = 8).  Staged cell
+// (i, j) is level cell (tx0 + i - s, ty0 + j - s); a cell outside the grid is staged inactive.  Sweep k = 1 .. s updates the staged cells at
+// least k cells from the staged border: a cell d cells outside the tile holds the value of the global sweep up to sweep s - d, so the tile
+// after sweep s is the tile after s global sweeps.  The replicate rule reads the classes, which are stated on the level's grid, not the tile.
+// val and out may be the same buffer when START is set: unknown cells of val are then never read, and only unknown cells are written.
+__global__ __launch_bounds__(TB) void relax_kernel(const uint8_t* __restrict__ cls, const int16_t* val, const int16_t* __restrict__ parent, int16_t* out,
+                                                   int hl, int wl, int s, int start, int tiles_x, int tiles_y, u64* __restrict__ sums) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ u64 tot[7];
+    const int sw = TW + 2 * s, sh = TH + 2 * s, plane = sw * sh;
+    int16_t* buf0 = (int16_t*)smem;
+    int16_t* buf1 = buf0 + 3 * plane;
+    uint8_t* cs = (uint8_t*)(buf1 + 3 * plane);
+    uint8_t* fs = cs + plane;
+    const int tile = (int)blockIdx.x % (tiles_x * tiles_y), t = (int)blockIdx.x / (tiles_x * tiles_y);
+    const int tx0 = (tile % tiles_x) * TW, ty0 = (tile / tiles_x) * TH;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int hu = (hl + 1) >> 1, wu = (wl + 1) >> 1;
+    const uint8_t* cl = cls + (int64_t)t * hl * wl;
+    const int16_t* in = val + (int64_t)t * hl * wl * 3;
+    int16_t* ot = out + (int64_t)t * hl * wl * 3;
+    const int16_t* par = parent ? parent + (int64_t)t * hu * wu * 3 : nullptr;
+    if (threadIdx.x < 7) tot[threadIdx.x] = 0;
+
+    int mine = 0;                                                              // an unknown cell of the tile itself
+    for (int k = threadIdx.x; k < plane; k += TB) {
+        const int j = k / sw, i = k - j * sw;
+        const int x = tx0 + i - s, y = ty0 + j - s;
+        int c = VVB_INACTIVE, v[3] = {0, 0, 0};
+        if (x >= 0 && x < wl && y >= 0 && y < hl) {
+            const int64_t g = (int64_t)y * wl + x;
+            c = cl[g];
+            const int16_t* p = nullptr;
+            if (c == VVB_KNOWN || (c == VVB_UNKNOWN && !start)) p = in + g * 3;
+            else if (c == VVB_UNKNOWN && par) p = par + ((int64_t)(y >> 1) * wu + (x >> 1)) * 3;
+            if (p) { v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; }
+        }
+        cs[k] = (uint8_t)c;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) { buf0[ch * plane + k] = (int16_t)v[ch]; buf1[ch * plane + k] = (int16_t)v[ch]; }
+        mine |= c == VVB_UNKNOWN && i >= s && i < s + TW && j >= s && j < s + TH;
+    }
+    const int x = tx0 + lane;
+    if (!__syncthreads_or(mine)) {                                             // nothing to solve: the tile as it is
+        if (ot != in && x < wl)
+            for (int yt = wave; yt < TH && ty0 + yt < hl; yt += TB / 64) {
+                const int k = (yt + s) * sw + lane + s;
+                int16_t* o = ot + ((int64_t)(ty0 + yt) * wl + x) * 3;
+                o[0] = buf0[k]; o[1] = buf0[plane + k]; o[2] = buf0[2 * plane + k];
+            }
+        return;
+    }
+    // bit 0: the cell is unknown; bits 1 .. 4: the neighbour above / below / left / right is staged and not inactive
+    for (int k = threadIdx.x; k < plane; k += TB) {
+        const int j = k / sw, i = k - j * sw;
+        int f = cs[k] == VVB_UNKNOWN ? 1 : 0;
+        if (j > 0 && cs[k - sw] != VVB_INACTIVE) f |= 2;
+        if (j + 1 < sh && cs[k + sw] != VVB_INACTIVE) f |= 4;
+        if (i > 0 && cs[k - 1] != VVB_INACTIVE) f |= 8;
+        if (i + 1 < sw && cs[k + 1] != VVB_INACTIVE) f |= 16;
+        fs[k] = (uint8_t)f;
+    }
+    __syncthreads();
+    int16_t* a = buf0;
+    int16_t* b = buf1;
+    for (int sweep = 1; sweep <= s; ++sweep) {
+        const int rw = sw - 2 * sweep, rh = sh - 2 * sweep;                    // rows and columns sweep .. size - sweep - 1: every neighbour is staged
+        for (int q = threadIdx.x; q < rw * rh; q += TB) {
+            const int j = q / rw, i = q - j * rw;
+            const int k = (j + sweep) * sw + i + sweep;
+            const int f = fs[k];
+            if (!(f & 1)) continue;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const int16_t* p = a + ch * plane + k;
+                const int self = p[0];
+                const int sum = ((f & 2) ? p[-sw] : self) + ((f & 4) ? p[sw] : self) + ((f & 8) ? p[-1] : self) + ((f & 16) ? p[1] : self);
+                b[ch * plane + k] = (int16_t)((sum + 2) >> 2);
+            }
+        }
+        __syncthreads();
+        int16_t* tmp = a; a = b; b = tmp;
+    }
+    // a holds sweep s on the tile
+    unsigned cnt = 0, sa[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
+    if (x < wl)
+        for (int yt = wave; yt < TH && ty0 + yt < hl; yt += TB / 64) {
+            const int k = (yt + s) * sw + lane + s;
+            const bool unk = fs[k] & 1;
+            if (!unk && ot == in) continue;
+            int16_t* o = ot + ((int64_t)(ty0 + yt) * wl + x) * 3;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const int v = a[ch * plane + k];
+                o[ch] = (int16_t)v;
+                if (unk) { const unsigned m = (unsigned)(v < 0 ? -v : v); sa[ch] += m; mx[ch] = max(mx[ch], m); }
+            }
+            cnt += unk;
+        }
+    if (!sums) return;                                                         // block-uniform
+    {
+        const unsigned c = wave_sum32(cnt);
+        if (lane == 0 && c) atomicAdd(&tot[0], (u64)c);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const unsigned sm = wave_sum32(sa[ch]), m = wave_max32(mx[ch]);
+            if (lane == 0 && sm) { atomicAdd(&tot[1 + ch], (u64)sm); atomicMax(&tot[4 + ch], (u64)m); }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && tot[threadIdx.x]) atomicAdd(&sums[(int64_t)t * NSUM + 4 + threadIdx.x], tot[threadIdx.x]);
+    else if (threadIdx.x >= 4 && threadIdx.x < 7 && tot[threadIdx.x]) atomicMax(&sums[(int64_t)t * NSUM + 4 + threadIdx.x], tot[threadIdx.x]);
+}
+
+// pixel (x, y) of frame t, as paste_grain_kernel of vv_grain.hip; inside the window the looked-up bytes get the membrane, then their grain
+__global__ __launch_bounds__(TB) void paste_blend_kernel(const uint8_t* __restrict__ patch, int Hm, int Wm, const uint8_t* __restrict__ orig,
+                                                         const uint8_t* __restrict__ mask, const int* __restrict__ offsets, const uint8_t* __restrict__ lut,
+                                                         const int16_t* __restrict__ field, int strength, const uint8_t* __restrict__ amp,
+                                                         const int* __restrict__ frame_ids, int seed, int mode, int T, int H, int W, int h, int w, float feather,
+                                                         int R, uint8_t* __restrict__ out) {
+    const int64_t n = (int64_t)T * H * W;
+    const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= n) return;
+    const int x = (int)(i % W); const int y = (int)((i / W) % H); const int t = (int)(i / ((int64_t)W * H));
+    const int yy = y - offsets[t * 2 + 0], xx = x - offsets[t * 2 + 1];
+    const uint8_t* o = orig + i * 3;
+    uint8_t* d = out + i * 3;
+    if (yy < 0 || yy >= h || xx < 0 || xx >= w) {
+        d[0] = o[0]; d[1] = o[1]; d[2] = o[2];
+        return;
+    }
+    uint8_t p[3];
+    window_px(patch + (int64_t)t * Hm * Wm * 3, Hm, Wm, xx, yy, h, w, p);
+    const uint8_t* tab = lut + (int64_t)t * 3 * 256;
+    p[0] = tab[p[0]]; p[1] = tab[256 + p[1]]; p[2] = tab[512 + p[2]];
+    const uint8_t* a = amp + (int64_t)t * 3 * 256;
+    const int av[3] = {a[p[0]], a[256 + p[1]], a[512 + p[2]]};                 // the amplitude of the tabled value, as the grain statistic saw it
+    const int16_t* m = field + (((int64_t)t * h + yy) * w + xx) * 3;
+    int g[3];
+    vvpaste::grain_px(vvpaste::noise_key(seed, frame_ids[t], H, W, x, y), mode, av, g);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int v = min(max((int)p[c] + (((int)m[c] * strength + (1 << 13)) >> 14), 0), 255);
+        p[c] = (uint8_t)min(max(v + g[c], 0), 255);
+    }
+    if (feather < 0.f) {
+        d[0] = p[0]; d[1] = p[1]; d[2] = p[2];
+        return;
+    }
+    const float alpha = vvpx::feather_alpha(mask + (int64_t)t * H * W, H, W, x, y, feather, R);
+    vvpx::feather_blend(alpha, p, o, d);
+}
+
+bool bad_sizes(int Hm, int Wm, int T, int H0, int W0, int h, int w) {
+    return T <= 0 || H0 <= 0 || W0 <= 0 || Hm <= 0 || Wm <= 0 || h <= 0 || w <= 0 || h > H0 || w > W0;
+}
+int64_t level_bytes(int T, int hl, int wl) { return ((int64_t)7 * T * hl * wl + 15) & ~(int64_t)15; }
+// tiles of a level, 0 when one launch does not hold them
+int64_t tiles(int T, int hl, int wl, int& tiles_x, int& tiles_y) {
+    tiles_x = (wl + TW - 1) / TW; tiles_y = (hl + TH - 1) / TH;
+    const int64_t blocks = (int64_t)tiles_x * tiles_y * T;
+    return blocks > 0x7fffffff ? 0 : blocks;
+}
+
+// the checks of vvb_ring_diff / vvb_relax / vvb_pull, under the caller's name
+int check_diff(const char* who, int ring, int presmooth, int max_shift) {
+    if (ring < 1 || ring > VVB_MAX_RING) VV_FAIL(VV_E_UNSUPPORTED, "%s: ring 1 .. %d is supported, not %d", who, VVB_MAX_RING, ring);
+    if (presmooth < 0 || presmooth > PS) VV_FAIL(VV_E_UNSUPPORTED, "%s: presmooth 0 .. %d is supported, not %d", who, PS, presmooth);
+    if (max_shift < 1 || max_shift > VVB_MAX_SHIFT) VV_FAIL(VV_E_UNSUPPORTED, "%s: max_shift 1 .. %d is supported, not %d", who, VVB_MAX_SHIFT, max_shift);
+    return VV_OK;
+}
+int check_sweeps(const char* who, int sweeps) {
+    if (sweeps < 1 || sweeps > MS) VV_FAIL(VV_E_UNSUPPORTED, "%s: sweeps 1 .. %d is supported, not %d", who, MS, sweeps);
+    return VV_OK;
+}
+
+int launch_diff(const char* who, const uint8_t* patch, int Hm, int Wm, const uint8_t* orig, const uint8_t* mask2d, const int* offsets, const uint8_t* lut,
+                int T, int H0, int W0, int h, int w, int ring, int presmooth, int max_shift, uint8_t* cls, int16_t* val, int64_t* sums, hipStream_t st) {
+    int tiles_x, tiles_y;
+    const int64_t blocks = tiles(T, h, w, tiles_x, tiles_y);
+    if (!blocks) VV_FAIL(VV_E_UNSUPPORTED, "%s: more tiles than one launch holds", who);
+    if (hipMemsetAsync(sums, 0, (size_t)T * NSUM * sizeof(int64_t), st) != hipSuccess) VV_FAIL(VV_E_LAUNCH, "%s: memset failed", who);
+    hipLaunchKernelGGL(classify_kernel, dim3((unsigned)blocks), dim3(TB), 0, st, mask2d, offsets, H0, W0, h, w, ring, tiles_x, tiles_y, cls);
+    hipLaunchKernelGGL(ring_diff_kernel, dim3((unsigned)blocks), dim3(TB), 0, st, patch, Hm, Wm, orig, offsets, lut, H0, W0, h, w, presmooth, 64 * max_shift,
+                       tiles_x, tiles_y, cls, val, (u64*)sums);
+    VV_CHECK_LAUNCH(who);
+    return VV_OK;
+}
+
+int launch_pull(const char* who, const uint8_t* cls, const int16_t* val, int T, int hl, int wl, uint8_t* cls_up, int16_t* val_up, hipStream_t st) {
+    const int hu = (hl + 1) / 2, wu = (wl + 1) / 2;
+    const int64_t n = (int64_t)T * hu * wu;
+    if ((n + TB - 1) / TB > 0x7fffffff) VV_FAIL(VV_E_UNSUPPORTED, "%s: more cells than one launch holds", who);
+    hipLaunchKernelGGL(pull_kernel, dim3((unsigned)((n + TB - 1) / TB)), dim3(TB), 0, st, cls, val, T, hl, wl, hu, wu, cls_up, val_up);
+    VV_CHECK_LAUNCH(who);
+    return VV_OK;
+}
+
+int launch_relax(const char* who, const uint8_t* cls, const int16_t* val, const int16_t* parent, int16_t* out, int T, int hl, int wl, int sweeps, int start,
+                 int64_t* sums, hipStream_t st) {
+    int tiles_x, tiles_y;
+    const int64_t blocks = tiles(T, hl, wl, tiles_x, tiles_y);
+    if (!blocks) VV_FAIL(VV_E_UNSUPPORTED, "%s: more tiles than one launch holds", who);
+    const size_t lds = (size_t)14 * (TW + 2 * sweeps) * (TH + 2 * sweeps);
+    // beyond the default limit of dynamic LDS the function needs the attribute; set whenever it is needed (a cheap host call), so a second device
+    // or a second host thread is covered as well
+    if (lds > 48 * 1024 &&
+        hipFuncSetAttribute((const void*)relax_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 14 * (TW + 2 * MS) * (TH + 2 * MS)) != hipSuccess)
+        VV_FAIL(VV_E_LAUNCH, "%s: %zu bytes of LDS refused", who, lds);
+    hipLaunchKernelGGL(relax_kernel, dim3((unsigned)blocks), dim3(TB), lds, st, cls, val, parent, out, hl, wl, sweeps, start, tiles_x, tiles_y, (u64*)sums);
+    VV_CHECK_LAUNCH(who);
+    return VV_OK;
+}
+
+}  // namespace
+
+extern "C" int vvb_abi_version(void) { return VVB_ABI_VERSION; }
+extern "C" const char* vvb_last_error(void) { return vv_last_error(); }
+
+extern "C" int vvb_levels(int h, int w) {
+    if (h <= 0 || w <= 0) return -1;
+    int n = 1;
+    for (; (h > w ? h : w) > 2; ++n) { h = (h + 1) / 2; w = (w + 1) / 2; }
+    return n;
+}
+
+extern "C" int64_t vvb_scratch_bytes(int T, int h, int w) {
+    if (T <= 0 || h <= 0 || w <= 0) return -1;
+    int64_t bytes = level_bytes(T, h, w);
+    while ((h > w ? h : w) > 2) { h = (h + 1) / 2; w = (w + 1) / 2; bytes += level_bytes(T, h, w); }
+    return bytes;
+}
+
+extern "C" int vvb_ring_diff(const uint8_t* patch, int Hm, int Wm, const uint8_t* orig, const uint8_t* mask2d, const int* offsets, const uint8_t* lut, int T,
+                             int H0, int W0, int h, int w, int ring, int presmooth, int max_shift, uint8_t* cls, int16_t* val, int64_t* sums, void* stream) {
+    if (!patch || !orig || !mask2d || !offsets || !lut || !cls || !val || !sums || bad_sizes(Hm, Wm, T, H0, W0, h, w))
+        VV_FAIL(VV_E_ARG, "vvb_ring_diff: bad args (no null pointer, sizes > 0, h <= H0, w <= W0)");
+    if (int rc = check_diff("vvb_ring_diff", ring, presmooth, max_shift)) return rc;
+    return launch_diff("vvb_ring_diff", patch, Hm, Wm, orig, mask2d, offsets, lut, T, H0, W0, h, w, ring, presmooth, max_shift, cls, val, sums,
+                       (hipStream_t)stream);
+}
+
+extern "C" int vvb_pull(const uint8_t* cls, const int16_t* val, int T, int hl, int wl, uint8_t* cls_up, int16_t* val_up, void* stream) {
+    if (!cls || !val || !cls_up || !val_up || T <= 0 || hl <= 0 || wl <= 0) VV_FAIL(VV_E_ARG, "vvb_pull: bad args (no null pointer, sizes > 0)");
+    return launch_pull("vvb_pull", cls, val, T, hl, wl, cls_up, val_up, (hipStream_t)stream);
+}
+
+extern "C" int vvb_relax(const uint8_t* cls, const int16_t* val, const int16_t* parent, int16_t* out, int T, int hl, int wl, int sweeps, int start,
+                         int64_t* sums, void* stream) {
+    if (!cls || !val || !out || T <= 0 || hl <= 0 || wl <= 0 || start < 0 || start > 1 || (!start && out == val))
+        VV_FAIL(VV_E_ARG, "vvb_relax: bad args (no null cls / val / out, sizes > 0, start 0 or 1, start 0 needs out != val)");
+    if (int rc = check_sweeps("vvb_relax", sweeps)) return rc;
+    return launch_relax("vvb_relax", cls, val, parent, out, T, hl, wl, sweeps, start, sums, (hipStream_t)stream);
+}
+
+extern "C" int vvb_solve(const uint8_t* patch, int Hm, int Wm, const uint8_t* orig, const uint8_t* mask2d, const int* offsets, const uint8_t* lut, int T,
+                         int H0, int W0, int h, int w, int ring, int presmooth, int sweeps, int max_shift, void* scratch, int64_t scratch_bytes,
+                         int64_t* sums, void* stream) {
+    if (!patch || !orig || !mask2d || !offsets || !lut || !scratch || !sums || bad_sizes(Hm, Wm, T, H0, W0, h, w))
+        VV_FAIL(VV_E_ARG, "vvb_solve: bad args (no null pointer, sizes > 0, h <= H0, w <= W0)");
+    if (scratch_bytes < vvb_scratch_bytes(T, h, w))
+        VV_FAIL(VV_E_ARG, "vvb_solve: %lld bytes of scratch, vvb_scratch_bytes asks for %lld", (long long)scratch_bytes, (long long)vvb_scratch_bytes(T, h, w));
+    if (int rc = check_diff("vvb_solve", ring, presmooth, max_shift)) return rc;
+    if (int rc = check_sweeps("vvb_solve", sweeps)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    constexpr int MAXL = 32;
+    int16_t* val[MAXL]; uint8_t* cls[MAXL]; int hs[MAXL], ws[MAXL];
+    const int L = vvb_levels(h, w);
+    unsigned char* at = (unsigned char*)scratch;
+    for (int l = 0, hl = h, wl = w; l < L; ++l, hl = (hl + 1) / 2, wl = (wl + 1) / 2) {
+        hs[l] = hl; ws[l] = wl;
+        val[l] = (int16_t*)at; cls[l] = at + (int64_t)6 * T * hl * wl;
+        at += level_bytes(T, hl, wl);
+    }
+    if (int rc = launch_diff("vvb_solve", patch, Hm, Wm, orig, mask2d, offsets, lut, T, H0, W0, h, w, ring, presmooth, max_shift, cls[0], val[0], sums, st)) return rc;
+    for (int l = 0; l + 1 < L; ++l)
+        if (int rc = launch_pull("vvb_solve", cls[l], val[l], T, hs[l], ws[l], cls[l + 1], val[l + 1], st)) return rc;
+    for (int l = L - 1; l >= 0; --l)
+        if (int rc = launch_relax("vvb_solve", cls[l], val[l], l + 1 < L ? val[l + 1] : nullptr, val[l], T, hs[l], ws[l], sweeps, 1, l == 0 ? sums : nullptr, st))
+            return rc;
+    return VV_OK;
+}
+
+extern "C" int vvb_paste_blend_composite(const uint8_t* patch, int Hm, int Wm, const uint8_t* orig, const uint8_t* mask2d, const int* offsets,
+                                         const uint8_t* lut, const int16_t* field, int strength_q8, const uint8_t* amp, const int* frame_ids, int seed,
+                                         int mode, int T, int H0, int W0, int h, int w, float feather_px, uint8_t* out, void* stream) {
+    if (!patch || !orig || !offsets || !lut || !field || !amp || !frame_ids || !out || bad_sizes(Hm, Wm, T, H0, W0, h, w))
+        VV_FAIL(VV_E_ARG, "vvb_paste_blend_composite: bad args (no null pointer, sizes > 0, h <= H0, w <= W0)");
+    if (seed < 0 || mode < 0 || mode > 1) VV_FAIL(VV_E_ARG, "vvb_paste_blend_composite: seed >= 0 and mode 0 (luma) or 1 (rgb), not seed %d, mode %d", seed, mode);
+    if (feather_px >= 0.f && !mask2d) VV_FAIL(VV_E_ARG, "vvb_paste_blend_composite: the feathered composite needs mask2d");
+    if (feather_px > 64.f) VV_FAIL(VV_E_UNSUPPORTED, "vvb_paste_blend_composite: feather_px %.1f > 64", feather_px);
+    if (strength_q8 < 0 || strength_q8 > VVB_MAX_STRENGTH_Q8)
+        VV_FAIL(VV_E_UNSUPPORTED, "vvb_paste_blend_composite: strength_q8 0 .. %d is supported, not %d", VVB_MAX_STRENGTH_Q8, strength_q8);
+    const int R = feather_px > 0.f ? (int)ceilf(feather_px) : 0;
+    const int64_t n = (int64_t)T * H0 * W0;
+    hipLaunchKernelGGL(paste_blend_kernel, dim3((unsigned)((n + TB - 1) / TB)), dim3(TB), 0, (hipStream_t)stream, patch, Hm, Wm, orig, mask2d, offsets, lut,
+                       field, strength_q8, amp, frame_ids, seed, mode, T, H0, W0, h, w, feather_px, R, out);
+    VV_CHECK_LAUNCH("vvb_paste_blend_composite");
+    return VV_OK;
+}

@@ -8,8 +8,8 @@
 // so each byte is resized, looked up and read from memory once and the nine taps are LDS reads.  The sums go 32-bit registers -> 32-bit wave
 // reduction -> 64-bit LDS atomics -> one set of 64-bit global integer atomics per block: integer adds, so the result does not depend on the
 // order.  The band is selected by unrolled compares, every accumulator index is a constant.  The per-pixel arithmetic (resize, feather) is
-// vv_image_px.h, so a zero amplitude gives vvt_paste_lut_composite's bytes.
-#include "vv_image_px.h"
+// vv_image_px.h, the window's pixel and the noise vv_paste_px.h (shared with vv_blend.hip), so a zero amplitude gives vvt_paste_lut_composite's bytes.
+#include "vv_paste_px.h"
 #include "vv_ring_bits.h"
 #include "../../include/vvgrain.h"
 #pragma clang fp contract(off)
@@ -20,6 +20,7 @@ using vvring::TB;
 using vvring::TW;
 using vvring::TH;
 using vvring::u64;
+using vvpaste::window_px;
 constexpr int NSUM = VVG_NSUM, BANDS = VVG_BANDS;
 constexpr int SW = TW + 2, SH = TH + 2;          // the staged tile: a one-pixel halo
 constexpr int SP = 68;                           // its row pitch in bytes
@@ -34,16 +35,6 @@ __device__ __forceinline__ unsigned wave_sum32(unsigned v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
-}
-
-// the window's pixel (xx, yy) of frame t's Hm x Wm image `src`, as vv_roi_paste_composite reads it
-__device__ __forceinline__ void window_px(const uint8_t* src, int Hm, int Wm, int xx, int yy, int h, int w, uint8_t* p) {
-    if (Hm == h && Wm == w) {
-        const uint8_t* s = src + ((int64_t)yy * w + xx) * 3;
-        p[0] = s[0]; p[1] = s[1]; p[2] = s[2];
-    } else {
-        vvpx::bilinear_px(src, Hm, Wm, 3, xx, yy, h, w, p);
-    }
 }
 
 // Immerkaer's operator, and max - min, on the 3 x 3 bytes round s (pitch SP)
@@ -143,18 +134,6 @@ __global__ __launch_bounds__(TB) void ring_grain_stats_kernel(const uint8_t* __r
     if (threadIdx.x < NSUM && tot[threadIdx.x]) atomicAdd(&sums[(int64_t)t * NSUM + threadIdx.x], tot[threadIdx.x]);
 }
 
-// the noise of one key (include/vvgrain.h): splitmix64's finaliser, the sum of its eight bytes centred
-__device__ __forceinline__ int noise_sum(u64 key) {
-    u64 z = key + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    // byte sums in parallel: pairs, then quads, then all eight
-    z = (z & 0x00FF00FF00FF00FFull) + ((z >> 8) & 0x00FF00FF00FF00FFull);
-    z = (z & 0x0000FFFF0000FFFFull) + ((z >> 16) & 0x0000FFFF0000FFFFull);
-    return (int)((unsigned)z + (unsigned)(z >> 32)) - 1020;
-}
-
 // pixel (x, y) of frame t, as paste_lut_kernel of vv_tone.hip; inside the window the looked-up bytes get their grain before the feather
 __global__ __launch_bounds__(TB) void paste_grain_kernel(const uint8_t* __restrict__ patch, int Hm, int Wm, const uint8_t* __restrict__ orig,
                                                          const uint8_t* __restrict__ mask, const int* __restrict__ offsets, const uint8_t* __restrict__ lut,
@@ -176,14 +155,11 @@ __global__ __launch_bounds__(TB) void paste_grain_kernel(const uint8_t* __restri
     const uint8_t* tab = lut + (int64_t)t * 3 * 256;
     p[0] = tab[p[0]]; p[1] = tab[256 + p[1]]; p[2] = tab[512 + p[2]];
     const uint8_t* a = amp + (int64_t)t * 3 * 256;
-    const u64 key = ((u64)(unsigned)seed << 32) ^ (((u64)(int64_t)frame_ids[t] * (u64)H + (u64)y) * (u64)W + (u64)x);
-    const int s0 = noise_sum(mode ? key * 3ull : key);
+    const int av[3] = {a[p[0]], a[256 + p[1]], a[512 + p[2]]};
+    int g[3];
+    vvpaste::grain_px(vvpaste::noise_key(seed, frame_ids[t], H, W, x, y), mode, av, g);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int s = (mode && c) ? noise_sum(key * 3ull + (u64)c) : s0;
-        const int v = (int)p[c] + (((int)a[c * 256 + p[c]] * s * 5017 + (1 << 23)) >> 24);
-        p[c] = (uint8_t)min(max(v, 0), 255);
-    }
+    for (int c = 0; c < 3; ++c) p[c] = (uint8_t)min(max((int)p[c] + g[c], 0), 255);
     if (feather < 0.f) {
         d[0] = p[0]; d[1] = p[1]; d[2] = p[2];
         return;

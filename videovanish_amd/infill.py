@@ -2,14 +2,16 @@
 (span_plan, run_spans), and for each clip the windows (region_plans, run_clip), ONE crop -> prior -> model sequence (run_windows) and ONE closing step (finish).  The full frame is
 no window, roi= "static" / "follow" one, the "-regions" spellings several.  With tone matching the closing step fits each window's pixels to the
 ring round the mask first (finish, tone_report); with grain matching it gives them the grain the ring's originals have and the model's pixels lack
-(finish, grain_report).  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is
-module state.  Rules and reasons: DESIGN.md §10, §11, §12, §13, §14."""
+(finish, grain_report); with seam blending it adds the membrane that carries the ring's difference original - model into the hole (finish,
+seam_blend_report).  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is
+module state.  Rules and reasons: DESIGN.md §10, §11, §12, §13, §14, §15."""
+import dataclasses
 from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
 
-from . import grain_hip, grainmatch, hip, mask_hip, spans_hip, tone_hip, tonematch
+from . import blend_hip, grain_hip, grainmatch, hip, mask_hip, seamblend, spans_hip, tone_hip, tonematch
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -166,9 +168,9 @@ def region_plans(dil_t, H0, W0, feather_px, cfg):
 
 
 def run_clip(frames_rgb, dil_t, propainer_frames, rcfg, stages, prog, dev, feather_px=3, keep_unmasked_original=True,
-             compat_reference_early_return=False, tone=None, tone_out=None, grain=None, grain_out=None, frame0=0):
+             compat_reference_early_return=False, tone=None, tone_out=None, grain=None, grain_out=None, frame0=0, blend=None, blend_out=None):
     """One clip after the dilation: the windows rcfg asks for (none without it, or where the planner falls back to the full frame), run_windows,
-    finish.  The whole call without spans=, and each span's call with it.  tone / tone_out / grain / grain_out / frame0: finish's."""
+    finish.  The whole call without spans=, and each span's call with it.  tone / tone_out / grain / grain_out / frame0 / blend / blend_out: finish's."""
     H0, W0 = frames_rgb[0].shape[:2]
     if rcfg is None:
         plans = []
@@ -179,6 +181,8 @@ def run_clip(frames_rgb, dil_t, propainer_frames, rcfg, stages, prog, dev, feath
         plans = [] if plan is None else [plan]
     outs = run_windows(frames_rgb, list(dil_t.cpu().numpy()), propainer_frames, plans, stages, prog)
     more = {} if grain is None else dict(grain=grain, grain_out=grain_out, frame0=frame0)       # passed only when grain matching is on
+    if blend is not None:                                                                        # likewise
+        more.update(blend=blend, blend_out=blend_out)
     return finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return, tone, tone_out, **more)
 
 
@@ -260,8 +264,31 @@ def grain_report(parts, spans, T, K=1):
     return rep
 
 
+class SeamBlendReport(NamedTuple):
+    """What seam membrane blending measured and added, per window k and frame t (K = 1 for the full frame): the ring pixels that gave data, the
+    RMS of original - model on them per channel (after tone matching's table), the pixels of the hole, and the largest and the mean |membrane|
+    inside the hole per channel, in 8-bit levels before `strength` (seamblend.SeamBlendFit, stacked: closed forms of exact integer sums).
+    Frames outside every span, frames this rank does not hold and windows a span does not have are zero rows."""
+    n: np.ndarray               # [K,T] int64
+    rms_diff: np.ndarray        # [K,T,3] float64
+    n_hole: np.ndarray          # [K,T] int64
+    max_shift: np.ndarray       # [K,T,3] float64
+    mean_shift: np.ndarray      # [K,T,3] float64
+
+
+def seam_blend_report(parts, spans, T, K=1):
+    """The report of a call over T frames from its clips' reports: parts[i] (finish's blend_out) covers the frames spans[i] = (a, b); at least K
+    windows."""
+    K = max([len(p.n) for p in parts] + [K])
+    rep = SeamBlendReport(np.zeros((K, T), np.int64), np.zeros((K, T, 3)), np.zeros((K, T), np.int64), np.zeros((K, T, 3)), np.zeros((K, T, 3)))
+    for part, (a, b) in zip(parts, spans):
+        for whole, piece in zip(rep, part):
+            whole[:len(piece), a:b] = piece
+    return rep
+
+
 def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return=False, tone=None, tone_out=None,
-           grain=None, grain_out=None, frame0=0):
+           grain=None, grain_out=None, frame0=0, blend=None, blend_out=None):
     """The model's frames into frames of the original size.  No plan (reference :69-112): resize when the model ran at another size, feathered
     composite with the originals when keep_unmasked_original, in place in outs[0].  The reference returns from inside its loop (:114) so only
     frame 0 is post-processed; the evident intent (all frames) is the default here, compat_reference_early_return=True reproduces the quirk.
@@ -276,7 +303,13 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
     the looked-up pixels against the running buffer, the [T,36] sums to the host, grainmatch.fit and tables, the [T,3,256] amplitudes to the
     device, paste_grain_composite in place of the paste, its noise keyed on the frame's index in the call, frame0 + its index in this clip;
     with keep_unmasked_original=False every pasted pixel gets grain.  The clip's GrainMatchReport is appended to grain_out.  Without grain
-    nothing here changes, and the tone-only path still calls paste_lut_composite."""
+    nothing here changes, and the tone-only path still calls paste_lut_composite.
+    blend (a seamblend.SeamBlendConfig): per window, after tone's table (the identity table without tone; with blend the tone
+    stage fits the offset alone, gain 1, whatever tone.mode says: a shift that varies round the ring misleads a gain): blend_hip.solve of the
+    looked-up pixels against the running buffer gives the membrane, over groups of frames (seamblend.groups) that share one scratch buffer;
+    paste_blend_composite in place of the paste adds it after the table and before the grain (zero amplitudes without grain, whose statistic
+    stays on the tabled pixel without the membrane).  The clip's SeamBlendReport is appended to blend_out.  Without blend nothing here
+    changes and no vvb_ symbol is resolved."""
     H0, W0 = frames_rgb[0].shape[:2]
     T = len(outs[0])
 
@@ -347,9 +380,60 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
             grain_out.append(GrainMatchReport(*(np.stack(f) for f in zip(*gfits))))
         return bufs[len(wins) % 2]
 
-    if tone is not None or grain is not None:
-        done = [len(o) if o is not None else 0 for o in (tone_out, grain_out)]
-        res = _on_device(outs[0] if not plans else list(outs[0]), T, dev, toned if grain is None else grained)
+    def blended(idx, up):
+        wins = [(p.offsets, p.size) for p in plans] or [(np.zeros((T, 2), np.int32), (H0, W0))]
+        bufs = [up(frames_rgb).contiguous()]
+        bufs.append(torch.empty_like(bufs[0]))
+        mask = dil_t[idx].contiguous()
+        n = len(idx)
+        ids = torch.from_numpy(np.asarray(idx, np.int32) + np.int32(frame0)).to(dev)
+        ident = np.broadcast_to(np.arange(256, dtype=np.uint8), (n, 3, 256))
+        amp = torch.zeros((n, 3, 256), dtype=torch.uint8, device=dev)
+        seed, mode = (0, 0) if grain is None else (grain.seed, grainmatch.MODES.index(grain.mode))
+        feather = float(feather_px if keep_unmasked_original else -1.0)
+        tfits, gfits, bfits = [], [], []
+        # a shift that varies round the ring is correlated with the picture there and misleads a fitted gain; what varies is the membrane's to
+        # take, so in front of it the tone stage fits the offset alone
+        tone_cfg = None if tone is None else dataclasses.replace(tone, mode="offset")
+        for k, ((offsets, (h, w)), o) in enumerate(zip(wins, outs)):
+            offs = torch.from_numpy(np.ascontiguousarray(offsets[idx], np.int32)).to(dev)
+            patch = up(o).contiguous()
+            lut = ident
+            if tone is not None:
+                sums = np.zeros((T, tonematch.NSUM), np.int64)
+                sums[idx] = tone_hip.ring_stats(patch, bufs[k % 2], mask, offs, h, w, tone.ring).cpu().numpy()
+                tfits.append(tonematch.fit(sums, tone_cfg))
+                lut = tonematch.tables(tfits[-1].gain[idx], tfits[-1].offset[idx])
+            lut = torch.from_numpy(np.ascontiguousarray(lut)).to(dev)
+            if grain is not None:
+                sums = np.zeros((T, grainmatch.NSUM), np.int64)
+                sums[idx] = grain_hip.ring_grain_stats(patch, bufs[k % 2], mask, offs, lut, h, w, grain.ring, grain.flat).cpu().numpy()
+                gfits.append(grainmatch.fit(sums, grain))
+                amp = torch.from_numpy(grainmatch.tables(gfits[-1].sigma_added[idx])).to(dev)
+            sums = np.zeros((T, seamblend.NSUM), np.int64)
+            scratch = None
+            for a, b in seamblend.groups(n, h, w):
+                if scratch is None:
+                    scratch = torch.empty((seamblend.scratch_bytes(b - a, h, w),), dtype=torch.uint8, device=dev)
+                field, _, part = blend_hip.solve(patch[a:b], bufs[k % 2][a:b], mask[a:b], offs[a:b], lut[a:b], h, w, blend.ring, blend.presmooth,
+                                                 blend.sweeps, blend.max_shift, scratch=scratch)
+                sums[idx[a:b]] = part.cpu().numpy()
+                blend_hip.paste_blend_composite(patch[a:b], bufs[k % 2][a:b], mask[a:b], offs[a:b], lut[a:b], field, blend.strength_q8, amp[a:b],
+                                                ids[a:b], seed, mode, h, w, feather, out=bufs[(k + 1) % 2][a:b])
+            bfits.append(seamblend.fit(sums))
+        if tone is not None and tone_out is not None:
+            tone_out.append(ToneMatchReport(*(np.stack(f) for f in zip(*tfits))))
+        if grain is not None and grain_out is not None:
+            grain_out.append(GrainMatchReport(*(np.stack(f) for f in zip(*gfits))))
+        if blend_out is not None:
+            blend_out.append(SeamBlendReport(*(np.stack(f) for f in zip(*bfits))))
+        return bufs[len(wins) % 2]
+
+    if tone is not None or grain is not None or blend is not None:
+        done = [len(o) if o is not None else 0 for o in (tone_out, grain_out, blend_out)]
+        res = _on_device(outs[0] if not plans else list(outs[0]), T, dev, blended if blend is not None else toned if grain is None else grained)
+        if blend is not None and blend_out is not None and len(blend_out) == done[2]:     # this rank holds no frame of the clip: zero rows
+            blend_out.append(seam_blend_report([], [], T, K=max(len(plans), 1)))
         if tone is not None and tone_out is not None and len(tone_out) == done[0]:        # this rank holds no frame of the clip: identity rows
             tone_out.append(tone_report([], [], T, K=max(len(plans), 1)))
         if grain is not None and grain_out is not None and len(grain_out) == done[1]:     # likewise: zero rows
