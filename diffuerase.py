@@ -10,7 +10,9 @@ videovanish_amd/maskclean.py; also configure(mask_clean=...) and $VV_MASK_CLEAN)
 the ring of unmasked pixels round the mask before the composite: videovanish_amd/tonematch.py; also configure(tone_match=...) and $VV_TONE_MATCH), grain_match (seam grain matching: the pasted pixels get the grain
 the original pixels of that ring have and the model's lack: videovanish_amd/grainmatch.py; also configure(grain_match=...) and $VV_GRAIN_MATCH), seam_blend (seam membrane blending: the
 difference original - model on that ring, interpolated harmonically into the hole and added to the pasted pixels: videovanish_amd/seamblend.py;
-also configure(seam_blend=...) and $VV_SEAM_BLEND).
+also configure(seam_blend=...) and $VV_SEAM_BLEND), plate_fill (clean-plate fill: masked pixels whose background other frames of the shot show are
+filled from the nearest such frame and leave the mask before anything plans or runs the model: videovanish_amd/platefill.py; also
+configure(plate_fill=...) and $VV_PLATE_FILL).
 There is no CPU fallback: without the HIP extension / a GPU this raises.
 
 This file is the boundary: the reference's names and module state, the settings, and the stages (weights, prior, model) that read that state.
@@ -23,7 +25,7 @@ import numpy as np
 import torch
 
 from videovanish_amd import hip, infill
-from videovanish_amd import grainmatch, maskclean, seamblend, tonematch
+from videovanish_amd import grainmatch, maskclean, platefill, seamblend, tonematch
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
 from videovanish_amd.config import RunConfig
@@ -51,10 +53,12 @@ _grain_match = None     # configure(grain_match=...): seam grain matching for ca
 last_grain_match = None # the infill.GrainMatchReport of the last run_infill_on_frames call; None when the stage did not run
 _seam_blend = None      # configure(seam_blend=...): seam membrane blending for calls that do not pass seam_blend= themselves
 last_seam_blend = None  # the infill.SeamBlendReport of the last run_infill_on_frames call; None when the stage did not run
+_plate_fill = None      # configure(plate_fill=...): clean-plate fill for calls that do not pass plate_fill= themselves
+last_plate_fill = None  # the infill.PlateFillReport of the last run_infill_on_frames call; None when the stage did not run
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
-              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None):
+              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, plate_fill=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -78,9 +82,12 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     grain_match = None / "on" / "luma" / "rgb" / "mode=rgb,ring=8,strength=0.8,seed=3" (any subset) / a grainmatch.GrainMatchConfig: seam grain
     matching for calls that do not pass grain_match=.
     seam_blend = None / "on" / "ring=12,presmooth=2,sweeps=8,max_shift=32,strength=1.0" (any subset) / a seamblend.SeamBlendConfig: seam membrane
-    blending for calls that do not pass seam_blend=."""
+    blending for calls that do not pass seam_blend=.
+    plate_fill = None / "on" / "guard=1,min_samples=4,tol=6,outlier=3,max_gap=0,margin=2,max_bytes=N" (any subset) / a platefill.PlateFillConfig:
+    clean-plate fill for calls that do not pass plate_fill=."""
     global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi, _spans, _mask_clean, _tone_match, _grain_match
-    global _seam_blend
+    global _seam_blend, _plate_fill
+    platefill.as_config(plate_fill)
     seamblend.as_config(seam_blend)
     grainmatch.as_config(grain_match)
     tonematch.as_config(tone_match)
@@ -100,6 +107,7 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     _tone_match = tone_match
     _grain_match = grain_match
     _seam_blend = seam_blend
+    _plate_fill = plate_fill
 
 
 def _resolve_weights(ckpt):
@@ -191,10 +199,21 @@ def seam_blend_config(seam_blend=None, feather_px=None):
     return seamblend.as_config(os.environ.get("VV_SEAM_BLEND"), feather_px)
 
 
+def plate_fill_config(plate_fill=None):
+    """The clean-plate fill setting a call runs with: its own plate_fill= argument, else configure(plate_fill=...), else $VV_PLATE_FILL (on | off |
+    guard=N,min_samples=N,tol=N,outlier=N,max_gap=N,margin=N,max_bytes=N).  None = no fill.  plate_fill="off" (or False) asks for none whatever
+    configure() or the environment say."""
+    if plate_fill is not None:
+        return platefill.as_config(plate_fill)
+    if _plate_fill is not None:
+        return platefill.as_config(_plate_fill)
+    return platefill.as_config(os.environ.get("VV_PLATE_FILL"))
+
+
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
-                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None):
+                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, plate_fill=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -228,14 +247,22 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     into the hole (after tone matching's table, when both are on) and adds this membrane to every pasted pixel before the grain and the
     feathered composite (infill.finish), for the full frame and for every roi window, inside each span: a correction that varies across the
     hole, which one gain and offset cannot give; in front of it tone matching fits its offset alone (gain 1), whatever its mode.  The ring must be wider than ceil(feather_px).  What it measured and added is kept in
-    last_seam_blend.  A model frame that equals the original on the ring gives the bytes of the call without it."""
-    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend
+    last_seam_blend.  A model frame that equals the original on the ring gives the bytes of the call without it.
+    plate_fill (clean-plate fill, opt-in): "on" / "guard=1,min_samples=4,tol=6,outlier=3,max_gap=0,margin=2,max_bytes=N" / a
+    videovanish_amd.platefill.PlateFillConfig fills, after the dilation and the mask clean-up and before anything plans or runs, every masked
+    pixel whose background the same shot shows steadily in other frames at the same place with the bytes of the nearest such frame
+    (infill.plate_fill; rules: include/vvplate.h) and takes it out of the mask; the segments are those between the cuts of spans= / cuts=.  The
+    filled frames and the smaller masks replace the originals for the span and window planners, the prior, the model and the composite: windows
+    shrink, and with spans="masked" frames that are filled completely drop out of inference.  A supplied propainer_frames is passed on
+    untouched.  What it filled is kept in last_plate_fill.  A clip in which nothing can be filled gives the bytes of the call without it."""
+    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
     ccfg = mask_clean_config(mask_clean)
     tcfg = tone_match_config(tone_match)
     gcfg = grain_match_config(grain_match)
-    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = None
+    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = None
+    pcfg = plate_fill_config(plate_fill)
     bcfg = seam_blend_config(seam_blend, feather_px if keep_unmasked_original else None)
     if rcfg is not None and compat_reference_early_return:
         raise ValueError("roi= (mask-region inference) cannot be combined with compat_reference_early_return=True")
@@ -249,6 +276,8 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         raise ValueError("grain_match= (seam grain matching) cannot be combined with compat_reference_early_return=True")
     if bcfg is not None and compat_reference_early_return:
         raise ValueError("seam_blend= (seam membrane blending) cannot be combined with compat_reference_early_return=True")
+    if pcfg is not None and compat_reference_early_return:
+        raise ValueError("plate_fill= (clean-plate fill) cannot be combined with compat_reference_early_return=True")
 
     if prog is not None: prog(5, "dilating frames")
     dev = get_device()
@@ -260,6 +289,12 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         if scfg is not None and scfg.cuts == "auto":        # the detector has run, on the despeckled masks: the span plan takes its cuts
             import dataclasses
             scfg = dataclasses.replace(scfg, cuts=last_mask_clean.cuts)
+    if pcfg is not None:
+        found = None if scfg is None else infill.clip_cuts(frames_rgb, dil_t, scfg)
+        if scfg is not None and scfg.cuts == "auto":        # the detector has run: the span plan takes its cuts
+            import dataclasses
+            scfg = dataclasses.replace(scfg, cuts=tuple(found))
+        frames_rgb, dil_t, last_plate_fill = infill.plate_fill(frames_rgb, dil_t, pcfg, found)      # downstream these are the originals
 
     stages = infill.Stages(lambda: _load_model(dev, ckpt), _load_prior, _run_prior,
                            lambda f, d, prior, p: _run_model(f, d, prior, max_img_size, p, num_inference_steps, scheduler))
@@ -369,6 +404,16 @@ def _seam_blend_arg(text):
     return text
 
 
+def _plate_fill_arg(text):
+    """--plate-fill's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --seam-blend)."""
+    try:
+        if platefill.as_config(text) is None:
+            raise ValueError("not a setting")
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return text
+
+
 def _mask_clean_arg(text):
     """--mask-clean's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --roi / --spans)."""
     try:
@@ -414,6 +459,11 @@ def main():
                     help="Seam membrane blending before the composite: interpolate the difference original - model from the ring of unmasked pixels "
                          "within `ring` px of the mask harmonically into the hole and add it to every pasted pixel, so that the patch meets the "
                          "original along the whole outline (a correction that varies across the hole).  Prints one line with what it added.")
+    ap.add_argument("--plate-fill", type=_plate_fill_arg, default=None, metavar="on|guard=1,min_samples=4,tol=6,outlier=3,max_gap=0,margin=2",
+                    help="Clean-plate fill before anything plans or runs the model: a masked pixel whose background the same shot shows steadily (a "
+                         "standard deviation of at most `tol` over at least `min_samples` unmasked frames, `guard` frames away from the mask) is filled "
+                         "from the nearest such frame and leaves the mask; what is never revealed stays with the model.  For locked-off shots.  "
+                         "Prints one line with what it filled.")
     ap.add_argument("--cuts", type=span_plan.parse_cuts, default=None, metavar="120,431",
                     help="Frame indices (relative to --start_frame) where a new shot begins: used instead of the detector.")
     args = ap.parse_args()
@@ -437,6 +487,7 @@ def main():
     if args.tone_match is not None: kw["tone_match"] = args.tone_match
     if args.grain_match is not None: kw["grain_match"] = args.grain_match
     if args.seam_blend is not None: kw["seam_blend"] = args.seam_blend
+    if args.plate_fill is not None: kw["plate_fill"] = args.plate_fill
     out_frames = run_infill_on_frames(frames, mask_frames, propainer_frames=prior_frames, **kw)
     if args.mask_clean is not None and last_mask_clean is not None:
         r = last_mask_clean
@@ -456,6 +507,10 @@ def main():
         touched = (r.max_shift > 0.0).any(axis=(0, 2))
         print(f"seam blend: membrane added in {int(touched.sum())} of {touched.size} frames, largest |shift| {float(r.max_shift.max()):.2f}, "
               f"largest ring RMS {float(r.rms_diff.max()):.2f}")
+    if args.plate_fill is not None and last_plate_fill is not None:
+        r = last_plate_fill
+        print(f"plate fill: {int(r.filled.sum())} px filled in {int((r.filled > 0).sum())} frames, {int(r.left.sum())} px left to the model in "
+              f"{int((r.left > 0).sum())} of {r.left.size} frames, {sum(r.skipped)} of {len(r.segments)} segments skipped")
     tools.write_video_frames_to_path(out_video, out_frames, fps, H0, W0)
 
 

@@ -1,0 +1,310 @@
+// Clean-plate fill (videovanish_amd/platefill.py, infill.plate_fill): masked pixels whose background the clip itself shows,
+// steadily, in other frames of the shot are filled from the nearest such frame and leave the mask.  The rules are include/vvplate.h's; all
+// arithmetic is integer.
+//   vvp_stats     per pixel along time: n, S1, S2 over the sample frames, the steady flag
+//   vvp_sources   per pixel along time, forward then backward: the nearest usable sample frame of every masked frame, and R0
+//   vvp_fill      per frame: the gather frames[src] -> frames where the pixel left the mask, dil', the counts
+// A streaming family over [T][H][W][3] u8.  A thread owns P adjacent pixels of one row and walks the frames (VEC: P = 4, one 12-byte image load
+// and one 4-byte mask load per frame, lane after lane contiguous; W % 4 == 0, tile % 4 == 0 and aligned bases, checked by the launcher; else
+// P = 1 with byte loads).  A thread whose pixels lie in a tile without a mask pixel ends before any load: the launcher has set its outputs.
+// A frame in which none of the thread's pixels can contribute costs its mask bytes only.  vvp_sources keeps, forward, the last usable frame seen and
+// leaves it in src (at unmasked frames: the frame's own index where it is usable), so the backward walk reads src and dil only, no image byte.
+// The counts go registers -> wave reduction -> LDS -> one pair of 64-bit global atomics per block, as in vv_tone.hip: integer adds in any order.
+#include "vv_common.h"
+#include "../../include/vvplate.h"
+
+namespace {
+
+constexpr int PB = 256;                     // threads per block
+constexpr unsigned NONE = VVP_NO_SOURCE;
+typedef unsigned long long u64;
+static_assert((u64)VVP_MAX_T * 255 * 255 < (1ull << 32), "S2 in 32 bits");
+
+struct __attribute__((aligned(4))) U3 { unsigned a, b, c; };
+
+// the tile test: unit u's first pixel decides (VEC: the launcher made all P pixels share a row and a tile)
+__device__ __forceinline__ bool occupied(const uint8_t* occ, int64_t i0, int W, int tile, int tw) {
+    if (!occ) return true;
+    const int y = (int)(i0 / W), x = (int)(i0 % W);
+    return occ[(int64_t)(y / tile) * tw + x / tile] != 0;
+}
+// the P mask bytes at m, byte p in bits 8 p ..
+template <bool VEC> __device__ __forceinline__ unsigned load_mask(const uint8_t* m) {
+    if constexpr (VEC) return *reinterpret_cast<const unsigned*>(m);
+    else return *m;
+}
+// the 3 P image bytes at px, as values
+template <bool VEC> __device__ __forceinline__ void load_px(const uint8_t* px, unsigned* v) {
+    if constexpr (VEC) {
+        const U3 q = *reinterpret_cast<const U3*>(px);
+        const unsigned w[3] = {q.a, q.b, q.c};
+#pragma unroll
+        for (int j = 0; j < 12; ++j) v[j] = (w[j >> 2] >> ((j & 3) * 8)) & 255u;
+    } else {
+        v[0] = px[0]; v[1] = px[1]; v[2] = px[2];
+    }
+}
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(PB) void stats_kernel(const uint8_t* __restrict__ frames, const uint8_t* __restrict__ ns, const uint8_t* __restrict__ occ, int T,
+                                                   int64_t N, int64_t units, int W, int tile, int tw, int min_samples, int tol,
+                                                   uint8_t* __restrict__ steady, int* __restrict__ n_out, int* __restrict__ s1_out) {
+    constexpr int P = VEC ? 4 : 1;
+    const int64_t u = (int64_t)blockIdx.x * PB + threadIdx.x;
+    if (u >= units || !occupied(occ, u * P, W, tile, tw)) return;
+    const int64_t i0 = u * P;
+    unsigned n[P], s1[3 * P], s2[3 * P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) n[p] = 0;
+#pragma unroll
+    for (int j = 0; j < 3 * P; ++j) s1[j] = s2[j] = 0;
+    for (int t = 0; t < T; ++t) {
+        const unsigned m = load_mask<VEC>(ns + (int64_t)t * N + i0);
+        unsigned smp[P], any = 0;
+#pragma unroll
+        for (int p = 0; p < P; ++p) { smp[p] = ((m >> (8 * p)) & 255u) == 0; any |= smp[p]; }
+        if (!any) continue;
+        unsigned v[3 * P];
+        load_px<VEC>(frames + ((int64_t)t * N + i0) * 3, v);
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            n[p] += smp[p];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const unsigned x = smp[p] ? v[3 * p + c] : 0u;
+                s1[3 * p + c] += x;
+                s2[3 * p + c] += x * x;
+            }
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        bool st = (int)n[p] >= min_samples;
+        const u64 bound = (u64)tol * tol * n[p] * n[p];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const u64 a = (u64)n[p] * s2[3 * p + c], b = (u64)s1[3 * p + c] * s1[3 * p + c];      // a >= b (Cauchy-Schwarz)
+            st = st && a - b <= bound;
+            s1_out[(i0 + p) * 3 + c] = (int)s1[3 * p + c];
+        }
+        steady[i0 + p] = st ? 1 : 0;
+        n_out[i0 + p] = (int)n[p];
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(PB) void sources_kernel(const uint8_t* __restrict__ frames, const uint8_t* __restrict__ dil, const uint8_t* __restrict__ ns,
+                                                     const uint8_t* __restrict__ occ, const uint8_t* __restrict__ steady, const int* __restrict__ n_in,
+                                                     const int* __restrict__ s1_in, int T, int64_t N, int64_t units, int W, int tile, int tw, int tol,
+                                                     int outlier, int max_gap, uint16_t* src, uint8_t* __restrict__ r0) {
+    constexpr int P = VEC ? 4 : 1;
+    const int64_t u = (int64_t)blockIdx.x * PB + threadIdx.x;
+    if (u >= units || !occupied(occ, u * P, W, tile, tw)) return;
+    const int64_t i0 = u * P;
+    int n[P], s1[3 * P], lim[P];
+    unsigned prev[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        n[p] = steady[i0 + p] ? n_in[i0 + p] : 0;                            // n = 0: not steady, no frame is usable
+        lim[p] = outlier * tol * n[p];                                      // <= 64 * 255 * 65535 < 2^31
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s1[3 * p + c] = s1_in[(i0 + p) * 3 + c];
+        prev[p] = NONE;
+    }
+    // forward: src[t] = the last usable frame before a masked frame t; at an unmasked frame t itself where it is usable
+    for (int t = 0; t < T; ++t) {
+        const int64_t at = (int64_t)t * N + i0;
+        const unsigned md = load_mask<VEC>(dil + at), ms = load_mask<VEC>(ns + at);
+        unsigned cand[P], any = 0;
+#pragma unroll
+        for (int p = 0; p < P; ++p) { cand[p] = n[p] > 0 && ((ms >> (8 * p)) & 255u) == 0; any |= cand[p]; }
+        unsigned v[3 * P];
+#pragma unroll
+        for (int j = 0; j < 3 * P; ++j) v[j] = 0;
+        if (any) load_px<VEC>(frames + at * 3, v);
+        unsigned o[P];
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            bool us = cand[p] != 0;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int d = n[p] * (int)v[3 * p + c] - s1[3 * p + c];      // |.| <= 65535 * 255
+                us = us && (d < 0 ? -d : d) <= lim[p];
+            }
+            if (us) prev[p] = (unsigned)t;
+            o[p] = ((md >> (8 * p)) & 255u) ? prev[p] : (us ? (unsigned)t : NONE);
+        }
+        if constexpr (VEC) *reinterpret_cast<uint2*>(src + at) = make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));
+        else src[at] = (uint16_t)o[0];
+    }
+    // backward: the first usable frame after t against the one before it; this thread wrote every src it reads
+    int next[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) next[p] = -1;
+    for (int t = T - 1; t >= 0; --t) {
+        const int64_t at = (int64_t)t * N + i0;
+        const unsigned md = load_mask<VEC>(dil + at);
+        unsigned sv[P];
+        if constexpr (VEC) {
+            const uint2 q = *reinterpret_cast<const uint2*>(src + at);
+            sv[0] = q.x & 0xffffu; sv[1] = q.x >> 16; sv[2] = q.y & 0xffffu; sv[3] = q.y >> 16;
+        } else {
+            sv[0] = src[at];
+        }
+        unsigned o[P], r = 0;
+#pragma unroll
+        for (int p = 0; p < P; ++p) {
+            if (((md >> (8 * p)) & 255u) == 0) {
+                if (sv[p] == (unsigned)t) next[p] = t;
+                o[p] = NONE;
+            } else {
+                const int pv = sv[p] == NONE ? -1 : (int)sv[p];
+                int best = pv;
+                if (next[p] >= 0 && (pv < 0 || next[p] - t < t - pv)) best = next[p];      // a tie goes to the earlier frame
+                if (best >= 0 && max_gap > 0 && (best > t ? best - t : t - best) > max_gap) best = -1;
+                o[p] = best < 0 ? NONE : (unsigned)best;
+                if (best < 0) r |= 255u << (8 * p);
+            }
+        }
+        if constexpr (VEC) {
+            *reinterpret_cast<uint2*>(src + at) = make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));
+            *reinterpret_cast<unsigned*>(r0 + at) = r;
+        } else {
+            src[at] = (uint16_t)o[0];
+            r0[at] = (uint8_t)r;
+        }
+    }
+}
+
+// grid (ceil(units / PB), T): frame = blockIdx.y.  The only writes into frames are the three bytes of a pixel that leaves the mask.
+template <bool VEC>
+__global__ __launch_bounds__(PB) void fill_kernel(uint8_t* frames, const uint8_t* __restrict__ dil, const uint8_t* __restrict__ keep,
+                                                  const uint8_t* __restrict__ occ, const uint16_t* __restrict__ src, int T, int64_t N, int64_t units, int W,
+                                                  int tile, int tw, uint8_t* __restrict__ dil_out, u64* __restrict__ counts) {
+    constexpr int P = VEC ? 4 : 1;
+    __shared__ unsigned tot[2];
+    if (threadIdx.x < 2) tot[threadIdx.x] = 0;
+    __syncthreads();
+    const int t = (int)blockIdx.y;
+    const int64_t u = (int64_t)blockIdx.x * PB + threadIdx.x;
+    unsigned filled = 0, left = 0;
+    if (u < units && occupied(occ, u * P, W, tile, tw)) {
+        const int64_t i0 = u * P, at = (int64_t)t * N + i0;
+        const unsigned md = load_mask<VEC>(dil + at);
+        unsigned o = 0;
+        if (md) {
+            const unsigned mk = load_mask<VEC>(keep + at);
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                if (((md >> (8 * p)) & 255u) == 0) continue;
+                const unsigned s = ((mk >> (8 * p)) & 255u) ? NONE : src[at + p];
+                if (s < (unsigned)T) {
+                    const uint8_t* from = frames + ((int64_t)s * N + i0 + p) * 3;
+                    uint8_t* to = frames + (at + p) * 3;
+                    to[0] = from[0]; to[1] = from[1]; to[2] = from[2];
+                    ++filled;
+                } else {
+                    o |= 255u << (8 * p);
+                    ++left;
+                }
+            }
+        }
+        if constexpr (VEC) *reinterpret_cast<unsigned*>(dil_out + at) = o;
+        else dil_out[at] = (uint8_t)o;
+    }
+    const unsigned pk = wave_sum(filled | (left << 16));                 // <= 4 each per lane, <= 256 per wave
+    if ((threadIdx.x & 63) == 0 && pk) {
+        if (pk & 0xffffu) atomicAdd(&tot[0], pk & 0xffffu);
+        if (pk >> 16) atomicAdd(&tot[1], pk >> 16);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 && tot[threadIdx.x]) atomicAdd(&counts[(int64_t)t * 2 + threadIdx.x], (u64)tot[threadIdx.x]);
+}
+
+// the arguments every entry point shares; 0 = fine
+int bad_clip(const char* who, int T, int H, int W, const uint8_t* occ, int tile) {
+    if (T < 1 || H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 31) || (occ && tile < 1))
+        VV_FAIL(VV_E_ARG, "%s: bad args (T >= 1, H * W < 2^31, tile >= 1 with occ)", who);
+    if (T > VVP_MAX_T) VV_FAIL(VV_E_UNSUPPORTED, "%s: T <= %d is supported, not %d", who, VVP_MAX_T, T);
+    return VV_OK;
+}
+bool aligned(const void* p, unsigned a) { return (uintptr_t)p % a == 0; }
+bool vec_ok(int W, const uint8_t* occ, int tile) { return W % 4 == 0 && (!occ || tile % 4 == 0); }
+
+}  // namespace
+
+extern "C" int vvp_abi_version(void) { return VVP_ABI_VERSION; }
+extern "C" const char* vvp_last_error(void) { return vv_last_error(); }
+
+extern "C" int vvp_stats(const uint8_t* frames, const uint8_t* notsample, const uint8_t* occ, int T, int H, int W, int tile, int min_samples, int tol,
+                         uint8_t* steady, int32_t* n, int32_t* s1, void* stream) {
+    if (!frames || !notsample || !steady || !n || !s1 || min_samples < 1 || tol < 0)
+        VV_FAIL(VV_E_ARG, "vvp_stats: bad args (no null pointer but occ, min_samples >= 1, tol >= 0)");
+    const int rc = bad_clip("vvp_stats", T, H, W, occ, tile);
+    if (rc != VV_OK) return rc;
+    if (tol > VVP_MAX_TOL) VV_FAIL(VV_E_UNSUPPORTED, "vvp_stats: tol <= %d is supported, not %d", VVP_MAX_TOL, tol);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t N = (int64_t)H * W;
+    if (occ && (hipMemsetAsync(steady, 0, (size_t)N, st) != hipSuccess || hipMemsetAsync(n, 0, (size_t)N * 4, st) != hipSuccess ||
+                hipMemsetAsync(s1, 0, (size_t)N * 12, st) != hipSuccess))
+        VV_FAIL(VV_E_LAUNCH, "vvp_stats: memset failed");
+    const int tw = occ ? (W + tile - 1) / tile : 0;
+    const bool vec = vec_ok(W, occ, tile) && aligned(frames, 4) && aligned(notsample, 4);
+    const int64_t units = vec ? N / 4 : N;
+    const dim3 grid((unsigned)((units + PB - 1) / PB));
+    if (vec) hipLaunchKernelGGL(stats_kernel<true>, grid, dim3(PB), 0, st, frames, notsample, occ, T, N, units, W, tile, tw, min_samples, tol, steady, n, s1);
+    else hipLaunchKernelGGL(stats_kernel<false>, grid, dim3(PB), 0, st, frames, notsample, occ, T, N, units, W, tile, tw, min_samples, tol, steady, n, s1);
+    VV_CHECK_LAUNCH("vvp_stats");
+    return VV_OK;
+}
+
+extern "C" int vvp_sources(const uint8_t* frames, const uint8_t* dil, const uint8_t* notsample, const uint8_t* occ, const uint8_t* steady, const int32_t* n,
+                           const int32_t* s1, int T, int H, int W, int tile, int tol, int outlier, int max_gap, uint16_t* src, uint8_t* r0, void* stream) {
+    if (!frames || !dil || !notsample || !steady || !n || !s1 || !src || !r0 || tol < 0 || outlier < 0 || max_gap < 0)
+        VV_FAIL(VV_E_ARG, "vvp_sources: bad args (no null pointer but occ, tol >= 0, outlier >= 0, max_gap >= 0)");
+    const int rc = bad_clip("vvp_sources", T, H, W, occ, tile);
+    if (rc != VV_OK) return rc;
+    if (tol > VVP_MAX_TOL || outlier > VVP_MAX_OUTLIER || max_gap > VVP_MAX_GAP)
+        VV_FAIL(VV_E_UNSUPPORTED, "vvp_sources: tol <= %d, outlier <= %d and max_gap <= %d are supported, not tol %d, outlier %d, max_gap %d", VVP_MAX_TOL,
+                VVP_MAX_OUTLIER, VVP_MAX_GAP, tol, outlier, max_gap);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t N = (int64_t)H * W;
+    if (occ && (hipMemsetAsync(src, 0xff, (size_t)T * N * 2, st) != hipSuccess || hipMemsetAsync(r0, 0, (size_t)T * N, st) != hipSuccess))
+        VV_FAIL(VV_E_LAUNCH, "vvp_sources: memset failed");
+    const int tw = occ ? (W + tile - 1) / tile : 0;
+    const bool vec = vec_ok(W, occ, tile) && aligned(frames, 4) && aligned(dil, 4) && aligned(notsample, 4) && aligned(src, 8) && aligned(r0, 4);
+    const int64_t units = vec ? N / 4 : N;
+    const dim3 grid((unsigned)((units + PB - 1) / PB));
+    if (vec) hipLaunchKernelGGL(sources_kernel<true>, grid, dim3(PB), 0, st, frames, dil, notsample, occ, steady, n, s1, T, N, units, W, tile, tw, tol, outlier,
+                                max_gap, src, r0);
+    else hipLaunchKernelGGL(sources_kernel<false>, grid, dim3(PB), 0, st, frames, dil, notsample, occ, steady, n, s1, T, N, units, W, tile, tw, tol, outlier,
+                            max_gap, src, r0);
+    VV_CHECK_LAUNCH("vvp_sources");
+    return VV_OK;
+}
+
+extern "C" int vvp_fill(uint8_t* frames, const uint8_t* dil, const uint8_t* keep, const uint8_t* occ, const uint16_t* src, int T, int H, int W, int tile,
+                        uint8_t* dil_out, int64_t* counts, void* stream) {
+    if (!frames || !dil || !keep || !src || !dil_out || !counts || dil_out == dil)
+        VV_FAIL(VV_E_ARG, "vvp_fill: bad args (no null pointer but occ, dil_out is not dil)");
+    const int rc = bad_clip("vvp_fill", T, H, W, occ, tile);
+    if (rc != VV_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t N = (int64_t)H * W;
+    if (hipMemsetAsync(counts, 0, (size_t)T * 2 * sizeof(int64_t), st) != hipSuccess ||
+        (occ && hipMemsetAsync(dil_out, 0, (size_t)T * N, st) != hipSuccess))
+        VV_FAIL(VV_E_LAUNCH, "vvp_fill: memset failed");
+    const int tw = occ ? (W + tile - 1) / tile : 0;
+    const bool vec = vec_ok(W, occ, tile) && aligned(dil, 4) && aligned(keep, 4) && aligned(dil_out, 4);
+    const int64_t units = vec ? N / 4 : N;
+    const dim3 grid((unsigned)((units + PB - 1) / PB), (unsigned)T);
+    if (vec) hipLaunchKernelGGL(fill_kernel<true>, grid, dim3(PB), 0, st, frames, dil, keep, occ, src, T, N, units, W, tile, tw, dil_out, (u64*)counts);
+    else hipLaunchKernelGGL(fill_kernel<false>, grid, dim3(PB), 0, st, frames, dil, keep, occ, src, T, N, units, W, tile, tw, dil_out, (u64*)counts);
+    VV_CHECK_LAUNCH("vvp_fill");
+    return VV_OK;
+}

@@ -1,17 +1,17 @@
-"""The orchestration of one diffuerase.run_infill_on_frames call after the dilation: the mask clean-up (clean_masks), the temporal plan
-(span_plan, run_spans), and for each clip the windows (region_plans, run_clip), ONE crop -> prior -> model sequence (run_windows) and ONE closing step (finish).  The full frame is
+"""The orchestration of one diffuerase.run_infill_on_frames call after the dilation: the mask clean-up (clean_masks), the clean-plate fill
+(plate_fill), the temporal plan (span_plan, run_spans), and for each clip the windows (region_plans, run_clip), ONE crop -> prior -> model sequence (run_windows) and ONE closing step (finish).  The full frame is
 no window, roi= "static" / "follow" one, the "-regions" spellings several.  With tone matching the closing step fits each window's pixels to the
 ring round the mask first (finish, tone_report); with grain matching it gives them the grain the ring's originals have and the model's pixels lack
 (finish, grain_report); with seam blending it adds the membrane that carries the ring's difference original - model into the hole (finish,
 seam_blend_report).  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is
-module state.  Rules and reasons: DESIGN.md §10, §11, §12, §13, §14, §15."""
+module state.  Rules and reasons: DESIGN.md §10, §11, §12, §13, §14, §15, §16."""
 import dataclasses
 from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
 
-from . import blend_hip, grain_hip, grainmatch, hip, mask_hip, seamblend, spans_hip, tone_hip, tonematch
+from . import blend_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platefill, seamblend, spans_hip, tone_hip, tonematch
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -68,6 +68,69 @@ def clean_masks(m, dil_t, ccfg, cuts=None):
         dil_t = out
         counts[:, 2:] = c.cpu().numpy()
     return dil_t, MaskCleanReport(*(counts[:, k].copy() for k in range(4)), cuts)
+
+
+# ---- clean plate: what the clip itself shows behind the mask -------------------------------------------------------------------------------
+class PlateFillReport(NamedTuple):
+    """What plate_fill changed: per frame (int64 [T] each) the pixels filled from another frame and the masked pixels left to the model; per
+    segment of `segments` the steady pixels of its crop and whether it was skipped (its crop exceeded max_bytes or 65535 frames: nothing filled);
+    the cuts the segments come from."""
+    filled: np.ndarray
+    left: np.ndarray
+    steady: tuple
+    skipped: tuple
+    segments: tuple
+    cuts: tuple
+
+
+def plate_fill(frames_rgb, dil_t, pcfg, cuts=None):
+    """The clean-plate fill (platefill.py; rules: include/vvplate.h): frames_rgb = the T host frames [H,W,3] u8, dil_t = the masks
+    [T,H,W] u8 on the device, pcfg = a PlateFillConfig, cuts = frame indices or None (one segment).  Per segment of spans.segments: the crop of
+    the union box of its masks (platefill.crop_box) crosses to the device, the sample frames come from time_bridge_grow(., 0, guard), then
+    stats, sources, the margin (mask_collapse_dilate of the unfilled remainder), fill in place on the uploaded crop; only the crops of frames
+    that got a fill come back, into copies of those frames.  A segment without a mask pixel uploads nothing; one whose crop exceeds max_bytes
+    is left as it is and flagged.  Returns (frames', dil', PlateFillReport): a frame with nothing filled is the caller's array itself, dil' is
+    dil_t itself when nothing was filled at all, and neither the caller's frames nor dil_t is ever written.  Depends on nothing but its
+    arguments: every rank gets the same frames and masks."""
+    T, H, W = dil_t.shape
+    cuts = tuple(int(c) for c in (cuts or ()))
+    segs = tuple(span_planner.segments(T, cuts))
+    boxes = hip.mask_bbox(dil_t).cpu().numpy()
+    frames, dil = list(frames_rgb), dil_t
+    filled, left = np.zeros(T, np.int64), np.zeros(T, np.int64)
+    steady, skipped = [], []
+    for s, e in segs:
+        box = platefill.crop_box(boxes[s:e], H, W)
+        steady.append(0)
+        skipped.append(box is not None and (e - s > platefill.MAX_T or platefill.crop_bytes(e - s, box) > pcfg.max_bytes))
+        if box is None:
+            continue
+        y0, x0, y1, x1 = box
+        d = dil_t[s:e, y0:y1, x0:x1].contiguous()
+        if skipped[-1]:
+            left[s:e] = (d != 0).flatten(1).sum(1).cpu().numpy()
+            continue
+        f = torch.from_numpy(np.stack([fr[y0:y1, x0:x1] for fr in frames_rgb[s:e]])).to(dil_t.device)
+        occ = hip.mask_tile_union(d, plate_hip.TILE)
+        notsample = d if pcfg.guard == 0 else mask_hip.time_bridge_grow(d, 0, pcfg.guard)[0]
+        st, n, s1 = plate_hip.stats(f, notsample, occ, pcfg.min_samples, pcfg.tol)
+        src, r0 = plate_hip.sources(f, d, notsample, occ, st, n, s1, pcfg.tol, pcfg.outlier, pcfg.max_gap)
+        keep = r0 if pcfg.margin == 0 else hip.mask_collapse_dilate(r0[..., None], pcfg.margin)
+        d2, c = plate_hip.fill(f, d, keep, occ, src)
+        c = c.cpu().numpy()
+        filled[s:e], left[s:e] = c[:, 0], c[:, 1]
+        steady[-1] = int(st.sum().item())
+        idx = np.nonzero(c[:, 0])[0]
+        if len(idx):
+            if dil is dil_t:
+                dil = dil_t.clone()
+            dil[s:e, y0:y1, x0:x1] = d2
+            got = f[torch.from_numpy(idx).to(f.device)].cpu().numpy()
+            for j, i in enumerate(idx):
+                fr = np.array(frames_rgb[s + i], copy=True)
+                fr[y0:y1, x0:x1] = got[j]
+                frames[s + i] = fr
+    return frames, dil, PlateFillReport(filled, left, tuple(steady), tuple(skipped), segs, cuts)
 
 
 # ---- spans: the clip in time --------------------------------------------------------------------------------------------------------------
