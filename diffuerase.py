@@ -12,7 +12,8 @@ the original pixels of that ring have and the model's lack: videovanish_amd/grai
 difference original - model on that ring, interpolated harmonically into the hole and added to the pasted pixels: videovanish_amd/seamblend.py;
 also configure(seam_blend=...) and $VV_SEAM_BLEND), plate_fill (clean-plate fill: masked pixels whose background other frames of the shot show are
 filled from the nearest such frame and leave the mask before anything plans or runs the model: videovanish_amd/platefill.py; also
-configure(plate_fill=...) and $VV_PLATE_FILL).
+configure(plate_fill=...) and $VV_PLATE_FILL), plate_align (clean-plate alignment: with plate_fill, one integer translation per frame is
+tracked first, so that the fill follows a panning camera: videovanish_amd/platealign.py; also configure(plate_align=...) and $VV_PLATE_ALIGN).
 There is no CPU fallback: without the HIP extension / a GPU this raises.
 
 This file is the boundary: the reference's names and module state, the settings, and the stages (weights, prior, model) that read that state.
@@ -25,7 +26,7 @@ import numpy as np
 import torch
 
 from videovanish_amd import hip, infill
-from videovanish_amd import grainmatch, maskclean, platefill, seamblend, tonematch
+from videovanish_amd import grainmatch, maskclean, platealign, platefill, seamblend, tonematch
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
 from videovanish_amd.config import RunConfig
@@ -55,10 +56,12 @@ _seam_blend = None      # configure(seam_blend=...): seam membrane blending for 
 last_seam_blend = None  # the infill.SeamBlendReport of the last run_infill_on_frames call; None when the stage did not run
 _plate_fill = None      # configure(plate_fill=...): clean-plate fill for calls that do not pass plate_fill= themselves
 last_plate_fill = None  # the infill.PlateFillReport of the last run_infill_on_frames call; None when the stage did not run
+_plate_align = None     # configure(plate_align=...): clean-plate alignment for calls that do not pass plate_align= themselves
+last_plate_align = None # the infill.PlateAlignReport of the last run_infill_on_frames call; None when the tracker did not run
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
-              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, plate_fill=None):
+              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, plate_align=None, plate_fill=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -84,9 +87,12 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     seam_blend = None / "on" / "ring=12,presmooth=2,sweeps=8,max_shift=32,strength=1.0" (any subset) / a seamblend.SeamBlendConfig: seam membrane
     blending for calls that do not pass seam_blend=.
     plate_fill = None / "on" / "guard=1,min_samples=4,tol=6,outlier=3,max_gap=0,margin=2,max_bytes=N" (any subset) / a platefill.PlateFillConfig:
-    clean-plate fill for calls that do not pass plate_fill=."""
+    clean-plate fill for calls that do not pass plate_fill=.
+    plate_align = None / "on" / "levels=4,radius=4,min_overlap=25,max_residual=12" (any subset) / a platealign.PlateAlignConfig: clean-plate
+    alignment for calls that do not pass plate_align=."""
     global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi, _spans, _mask_clean, _tone_match, _grain_match
-    global _seam_blend, _plate_fill
+    global _seam_blend, _plate_fill, _plate_align
+    platealign.as_config(plate_align)
     platefill.as_config(plate_fill)
     seamblend.as_config(seam_blend)
     grainmatch.as_config(grain_match)
@@ -108,6 +114,7 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     _grain_match = grain_match
     _seam_blend = seam_blend
     _plate_fill = plate_fill
+    _plate_align = plate_align
 
 
 def _resolve_weights(ckpt):
@@ -210,10 +217,21 @@ def plate_fill_config(plate_fill=None):
     return platefill.as_config(os.environ.get("VV_PLATE_FILL"))
 
 
+def plate_align_config(plate_align=None):
+    """The clean-plate alignment setting a call runs with: its own plate_align= argument, else configure(plate_align=...), else $VV_PLATE_ALIGN
+    (on | off | levels=N,radius=N,min_overlap=N,max_residual=N).  None = no alignment.  plate_align="off" (or False) asks for none whatever
+    configure() or the environment say."""
+    if plate_align is not None:
+        return platealign.as_config(plate_align)
+    if _plate_align is not None:
+        return platealign.as_config(_plate_align)
+    return platealign.as_config(os.environ.get("VV_PLATE_ALIGN"))
+
+
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
-                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, plate_fill=None):
+                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, plate_align=None, plate_fill=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -254,15 +272,24 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     (infill.plate_fill; rules: include/vvplate.h) and takes it out of the mask; the segments are those between the cuts of spans= / cuts=.  The
     filled frames and the smaller masks replace the originals for the span and window planners, the prior, the model and the composite: windows
     shrink, and with spans="masked" frames that are filled completely drop out of inference.  A supplied propainer_frames is passed on
-    untouched.  What it filled is kept in last_plate_fill.  A clip in which nothing can be filled gives the bytes of the call without it."""
-    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill
+    untouched.  What it filled is kept in last_plate_fill.  A clip in which nothing can be filled gives the bytes of the call without it.
+    plate_align (clean-plate alignment, opt-in, needs plate_fill): "on" / "levels=4,radius=4,min_overlap=25,max_residual=12" / a
+    videovanish_amd.platealign.PlateAlignConfig tracks, per segment, one integer translation per frame against a held key frame (rules:
+    include/vvalign.h) and runs the fill on the canvas in which the background stands still, so that a slow pan or tilt, or a static overlay
+    over a panning shot, is filled from the frames that show its background at another place.  A frame the tracker loses gives no sample
+    and keeps its mask; a locked-off clip gives the bytes of the call without it.  What it found is kept in last_plate_align.  Without an
+    effective plate_fill it is a ValueError."""
+    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
     ccfg = mask_clean_config(mask_clean)
     tcfg = tone_match_config(tone_match)
     gcfg = grain_match_config(grain_match)
-    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = None
+    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = None
     pcfg = plate_fill_config(plate_fill)
+    acfg = plate_align_config(plate_align)
+    if acfg is not None and pcfg is None:
+        raise ValueError("plate_align= (clean-plate alignment) needs plate_fill= (clean-plate fill)")
     bcfg = seam_blend_config(seam_blend, feather_px if keep_unmasked_original else None)
     if rcfg is not None and compat_reference_early_return:
         raise ValueError("roi= (mask-region inference) cannot be combined with compat_reference_early_return=True")
@@ -294,7 +321,12 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         if scfg is not None and scfg.cuts == "auto":        # the detector has run: the span plan takes its cuts
             import dataclasses
             scfg = dataclasses.replace(scfg, cuts=tuple(found))
-        frames_rgb, dil_t, last_plate_fill = infill.plate_fill(frames_rgb, dil_t, pcfg, found)      # downstream these are the originals
+        if acfg is None:
+            frames_rgb, dil_t, last_plate_fill = infill.plate_fill(frames_rgb, dil_t, pcfg, found)      # downstream these are the originals
+        else:
+            found_align = []
+            frames_rgb, dil_t, last_plate_fill = infill.plate_fill(frames_rgb, dil_t, pcfg, found, acfg=acfg, align_out=found_align)
+            last_plate_align = found_align[0]
 
     stages = infill.Stages(lambda: _load_model(dev, ckpt), _load_prior, _run_prior,
                            lambda f, d, prior, p: _run_model(f, d, prior, max_img_size, p, num_inference_steps, scheduler))
@@ -414,6 +446,16 @@ def _plate_fill_arg(text):
     return text
 
 
+def _plate_align_arg(text):
+    """--plate-align's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --plate-fill)."""
+    try:
+        if platealign.as_config(text) is None:
+            raise ValueError("not a setting")
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return text
+
+
 def _mask_clean_arg(text):
     """--mask-clean's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --roi / --spans)."""
     try:
@@ -464,6 +506,10 @@ def main():
                          "standard deviation of at most `tol` over at least `min_samples` unmasked frames, `guard` frames away from the mask) is filled "
                          "from the nearest such frame and leaves the mask; what is never revealed stays with the model.  For locked-off shots.  "
                          "Prints one line with what it filled.")
+    ap.add_argument("--plate-align", type=_plate_align_arg, default=None, metavar="on|levels=4,radius=4,min_overlap=25,max_residual=12",
+                    help="With --plate-fill: track one integer translation per frame first (a coarse-to-fine search over `levels` pyramid levels, "
+                         "+-`radius` at the coarsest; a frame whose best match differs by more than `max_residual` levels on average is left out) "
+                         "and fill on the canvas in which the background stands still.  For slow pans and tilts.  Prints one line with what it tracked.")
     ap.add_argument("--cuts", type=span_plan.parse_cuts, default=None, metavar="120,431",
                     help="Frame indices (relative to --start_frame) where a new shot begins: used instead of the detector.")
     args = ap.parse_args()
@@ -488,6 +534,7 @@ def main():
     if args.grain_match is not None: kw["grain_match"] = args.grain_match
     if args.seam_blend is not None: kw["seam_blend"] = args.seam_blend
     if args.plate_fill is not None: kw["plate_fill"] = args.plate_fill
+    if args.plate_align is not None: kw["plate_align"] = args.plate_align
     out_frames = run_infill_on_frames(frames, mask_frames, propainer_frames=prior_frames, **kw)
     if args.mask_clean is not None and last_mask_clean is not None:
         r = last_mask_clean
@@ -511,6 +558,13 @@ def main():
         r = last_plate_fill
         print(f"plate fill: {int(r.filled.sum())} px filled in {int((r.filled > 0).sum())} frames, {int(r.left.sum())} px left to the model in "
               f"{int((r.left > 0).sum())} of {r.left.size} frames, {sum(r.skipped)} of {len(r.segments)} segments skipped")
+    if args.plate_align is not None and last_plate_align is not None:
+        r = last_plate_align
+        ok = np.concatenate(r.tracked)
+        span = [int(o[k][:, a].max() - o[k][:, a].min()) if k.any() else 0 for a in (0, 1) for o, k in zip(r.off, r.tracked)]
+        n = len(r.segments)
+        print(f"plate align: {int(ok.sum())} of {ok.size} frames tracked, pan extent {max(span[:n])} x {max(span[n:])} px, "
+              f"{sum(p == 'canvas' for p in r.path)} of {n} segments filled on a canvas")
     tools.write_video_frames_to_path(out_video, out_frames, fps, H0, W0)
 
 

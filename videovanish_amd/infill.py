@@ -4,14 +4,14 @@ no window, roi= "static" / "follow" one, the "-regions" spellings several.  With
 ring round the mask first (finish, tone_report); with grain matching it gives them the grain the ring's originals have and the model's pixels lack
 (finish, grain_report); with seam blending it adds the membrane that carries the ring's difference original - model into the hole (finish,
 seam_blend_report).  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is
-module state.  Rules and reasons: DESIGN.md §10, §11, §12, §13, §14, §15, §16."""
+module state.  Rules and reasons: DESIGN.md §10, §11, §12, §13, §14, §15, §16, §17."""
 import dataclasses
 from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
 
-from . import blend_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platefill, seamblend, spans_hip, tone_hip, tonematch
+from . import align_hip, blend_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platealign, platefill, seamblend, spans_hip, tone_hip, tonematch
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -83,7 +83,91 @@ class PlateFillReport(NamedTuple):
     cuts: tuple
 
 
-def plate_fill(frames_rgb, dil_t, pcfg, cuts=None):
+class PlateAlignReport(NamedTuple):
+    """What the tracker of plate_fill(acfg=) found, per segment of `segments` (a tuple each): off [T,2] int32 = the frame's (x, y) on the canvas,
+    key [T] = the key frame it was tracked against, tracked [T] bool, residual [T] = the mean absolute luma difference of its level-0 best
+    (0 for frame 0 and a lost frame), the canvas box (y0, x0, y1, x1 in canvas coordinates, or None) and the path that ran: "canvas", "static"
+    (every frame tracked at offset zero: the unaligned stage as it is), "fallback" (the canvas exceeds max_bytes: the unaligned stage),
+    "none" (no tracked frame has a mask pixel: nothing filled), "empty" (no mask pixel at all: nothing tracked) or "untracked" (the segment
+    is beyond the tracker's limits: the unaligned stage)."""
+    off: tuple
+    key: tuple
+    tracked: tuple
+    residual: tuple
+    box: tuple
+    path: tuple
+    segments: tuple
+
+
+def _track_segment(frames_rgb, d_seg, acfg, max_bytes):
+    """Pyramid in frame batches of at most max_bytes of image (only the luma planes stay resident), vva_track, and the ONE synchronisation:
+    -> (track on the device, track on the host)."""
+    T, H, W = d_seg.shape
+    L = platealign.coarsest_level(H, W, acfg.levels)
+    pyr = torch.empty((T, align_hip.frame_bytes(H, W, L)), dtype=torch.uint8, device=d_seg.device)
+    B = max(1, max_bytes // (H * W * 3))
+    for b in range(0, T, B):
+        f = torch.from_numpy(np.stack(frames_rgb[b:b + B])).to(d_seg.device)
+        align_hip.pyramid(f, d_seg[b:b + B], L, out=pyr[b:b + B])
+    track_t = align_hip.track(pyr, H, W, L, acfg.radius, acfg.min_overlap, acfg.max_residual)
+    return track_t, track_t.cpu().numpy()
+
+
+def _plan_alignment(frames_rgb, d_seg, boxes, pcfg, acfg):
+    """Steps 1 - 4 and 6 of DESIGN.md §17 for one segment -> (track on the device or None, track [T,8] on the host, the canvas box or None,
+    the path: see PlateAlignReport)."""
+    T, H, W = d_seg.shape
+    track = np.zeros((T, 8), np.int32)
+    track[:, 3] = 1
+    if not any(b[2] > b[0] and b[3] > b[1] for b in boxes):
+        return None, track, None, "empty"
+    if not platealign.trackable(T, H, W):
+        return None, track, None, "untracked"
+    track_t, track = _track_segment(frames_rgb, d_seg, acfg, pcfg.max_bytes)
+    ok = track[:, 3] == 1
+    if ok.all() and not track[:, :2].any():
+        return track_t, track, None, "static"
+    cbox = platealign.canvas_box(boxes, track[:, :2], ok)
+    if cbox is None:
+        return track_t, track, None, "none"
+    return track_t, track, cbox, "fallback" if platealign.canvas_bytes(T, cbox) > pcfg.max_bytes else "canvas"
+
+
+def _fill_on_canvas(frames_rgb, d_seg, track_t, track, box, pcfg):
+    """Steps 5 and 7 - 9 of DESIGN.md §17 for one segment: the canvas from per-frame slices, the unchanged vvp_ kernels on it, the filled pixels
+    back into copies of their frames -> ({frame index: new frame}, dil' [T,H,W] or None when nothing was filled, counts [T,2], steady)."""
+    T, H, W = d_seg.shape
+    y0, x0, y1, x1 = box
+    canvas = np.zeros((T, y1 - y0, x1 - x0, 3), np.uint8)
+    where = [platealign.frame_slices(box, track[t, :2], H, W) if track[t, 3] == 1 else None for t in range(T)]
+    for t, sl in enumerate(where):
+        if sl is not None:
+            canvas[t][sl[0]] = frames_rgb[t][sl[1]]
+    f = torch.from_numpy(canvas).to(d_seg.device)
+    d, invalid = align_hip.place_masks(d_seg, track_t, box)
+    occ = hip.mask_tile_union(d, plate_hip.TILE)
+    notsample = torch.bitwise_or(d if pcfg.guard == 0 else mask_hip.time_bridge_grow(d, 0, pcfg.guard)[0], invalid)
+    st, n, s1 = plate_hip.stats(f, notsample, occ, pcfg.min_samples, pcfg.tol)
+    src, r0 = plate_hip.sources(f, d, notsample, occ, st, n, s1, pcfg.tol, pcfg.outlier, pcfg.max_gap)
+    keep = r0 if pcfg.margin == 0 else hip.mask_collapse_dilate(r0[..., None], pcfg.margin)
+    d2, c = plate_hip.fill(f, d, keep, occ, src)
+    c = c.cpu().numpy()
+    idx = np.nonzero(c[:, 0])[0]
+    new = {}
+    if not len(idx):
+        return new, None, c, int(st.sum().item())
+    sel = torch.from_numpy(idx).to(f.device)
+    got, went = f[sel].cpu().numpy(), ((d[sel] != 0) & (d2[sel] == 0)).cpu().numpy()
+    for j, i in enumerate(idx):
+        cs, fs = where[i]
+        fr = np.array(frames_rgb[i], copy=True)
+        m = went[j][cs]
+        fr[fs][m] = got[j][cs][m]                                          # only the filled pixels; fr[fs] is a view
+        new[int(i)] = fr
+    return new, align_hip.unplace_mask(d2, d_seg, track_t, box), c, int(st.sum().item())
+
+
+def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None):
     """The clean-plate fill (platefill.py; rules: include/vvplate.h): frames_rgb = the T host frames [H,W,3] u8, dil_t = the masks
     [T,H,W] u8 on the device, pcfg = a PlateFillConfig, cuts = frame indices or None (one segment).  Per segment of spans.segments: the crop of
     the union box of its masks (platefill.crop_box) crosses to the device, the sample frames come from time_bridge_grow(., 0, guard), then
@@ -91,7 +175,12 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None):
     that got a fill come back, into copies of those frames.  A segment without a mask pixel uploads nothing; one whose crop exceeds max_bytes
     is left as it is and flagged.  Returns (frames', dil', PlateFillReport): a frame with nothing filled is the caller's array itself, dil' is
     dil_t itself when nothing was filled at all, and neither the caller's frames nor dil_t is ever written.  Depends on nothing but its
-    arguments: every rank gets the same frames and masks."""
+    arguments: every rank gets the same frames and masks.
+    acfg = a platealign.PlateAlignConfig (rules: include/vvalign.h), opt-in: every segment with a mask pixel is tracked first
+    (one integer translation per frame against a held key); a segment whose frames all sit at offset zero takes the path above as it is, any
+    other is filled on the canvas in which its background stands still (the same vvp_ kernels; the places no tracked frame covers are no
+    samples), unless the canvas exceeds max_bytes: then the path above runs and the segment is flagged "fallback".  An untracked frame gives
+    no sample, gets no fill and keeps its mask.  align_out = a list that receives the call's PlateAlignReport."""
     T, H, W = dil_t.shape
     cuts = tuple(int(c) for c in (cuts or ()))
     segs = tuple(span_planner.segments(T, cuts))
@@ -99,7 +188,27 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None):
     frames, dil = list(frames_rgb), dil_t
     filled, left = np.zeros(T, np.int64), np.zeros(T, np.int64)
     steady, skipped = [], []
+    arep = [[] for _ in range(6)]
     for s, e in segs:
+        if acfg is not None:
+            track_t, track, cbox, path = _plan_alignment(frames_rgb[s:e], dil_t[s:e], boxes[s:e], pcfg, acfg)
+            for k, v in enumerate((track[:, :2].copy(), track[:, 2].copy(), track[:, 3] == 1, _residual(track), cbox, path)):
+                arep[k].append(v)
+            if path in ("none", "canvas"):
+                steady.append(0)
+                skipped.append(False)
+                left[s:e] = (dil_t[s:e] != 0).flatten(1).sum(1).cpu().numpy()
+                if path == "canvas":
+                    new, d2, c, steady[-1] = _fill_on_canvas(frames_rgb[s:e], dil_t[s:e], track_t, track, cbox, pcfg)
+                    filled[s:e] = c[:, 0]
+                    left[s:e] = np.where(track[:, 3] == 1, c[:, 1], left[s:e])
+                    for i, fr in new.items():
+                        frames[s + i] = fr
+                    if d2 is not None:
+                        if dil is dil_t:
+                            dil = dil_t.clone()
+                        dil[s:e] = d2
+                continue
         box = platefill.crop_box(boxes[s:e], H, W)
         steady.append(0)
         skipped.append(box is not None and (e - s > platefill.MAX_T or platefill.crop_bytes(e - s, box) > pcfg.max_bytes))
@@ -130,7 +239,15 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None):
                 fr = np.array(frames_rgb[s + i], copy=True)
                 fr[y0:y1, x0:x1] = got[j]
                 frames[s + i] = fr
+    if acfg is not None and align_out is not None:
+        align_out.append(PlateAlignReport(*(tuple(v) for v in arep), segs))
     return frames, dil, PlateFillReport(filled, left, tuple(steady), tuple(skipped), segs, cuts)
+
+
+def _residual(track):
+    """Mean absolute luma difference of every frame's level-0 best from the records' (sad_lo, sad_hi, n); 0 where n == 0."""
+    sad = track[:, 4].astype(np.int64) % (1 << 32) + (track[:, 5].astype(np.int64) << 32)
+    return sad / np.maximum(track[:, 6], 1)
 
 
 # ---- spans: the clip in time --------------------------------------------------------------------------------------------------------------
