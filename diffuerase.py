@@ -13,7 +13,10 @@ difference original - model on that ring, interpolated harmonically into the hol
 also configure(seam_blend=...) and $VV_SEAM_BLEND), plate_fill (clean-plate fill: masked pixels whose background other frames of the shot show are
 filled from the nearest such frame and leave the mask before anything plans or runs the model: videovanish_amd/platefill.py; also
 configure(plate_fill=...) and $VV_PLATE_FILL), plate_align (clean-plate alignment: with plate_fill, one integer translation per frame is
-tracked first, so that the fill follows a panning camera: videovanish_amd/platealign.py; also configure(plate_align=...) and $VV_PLATE_ALIGN).
+tracked first, so that the fill follows a panning camera: videovanish_amd/platealign.py; also configure(plate_align=...) and $VV_PLATE_ALIGN),
+deflicker (inpaint deflicker: the model's pixels are filtered along time before every other seam stage reads them, each the mean of its temporal
+neighbours within a tolerance, so that the patch stops shimmering while moving edges stay as they are: videovanish_amd/deflicker.py; also
+configure(deflicker=...) and $VV_DEFLICKER).
 There is no CPU fallback: without the HIP extension / a GPU this raises.
 
 This file is the boundary: the reference's names and module state, the settings, and the stages (weights, prior, model) that read that state.
@@ -26,6 +29,7 @@ import numpy as np
 import torch
 
 from videovanish_amd import hip, infill
+from videovanish_amd import deflicker as deflicker_settings
 from videovanish_amd import grainmatch, maskclean, platealign, platefill, seamblend, tonematch
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
@@ -58,10 +62,12 @@ _plate_fill = None      # configure(plate_fill=...): clean-plate fill for calls 
 last_plate_fill = None  # the infill.PlateFillReport of the last run_infill_on_frames call; None when the stage did not run
 _plate_align = None     # configure(plate_align=...): clean-plate alignment for calls that do not pass plate_align= themselves
 last_plate_align = None # the infill.PlateAlignReport of the last run_infill_on_frames call; None when the tracker did not run
+_deflicker = None       # configure(deflicker=...): inpaint deflicker for calls that do not pass deflicker= themselves
+last_deflicker = None   # the infill.DeflickerReport of the last run_infill_on_frames call; None when the stage did not run
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
-              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, plate_align=None, plate_fill=None):
+              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, plate_align=None, plate_fill=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -89,9 +95,12 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     plate_fill = None / "on" / "guard=1,min_samples=4,tol=6,outlier=3,max_gap=0,margin=2,max_bytes=N" (any subset) / a platefill.PlateFillConfig:
     clean-plate fill for calls that do not pass plate_fill=.
     plate_align = None / "on" / "levels=4,radius=4,min_overlap=25,max_residual=12" (any subset) / a platealign.PlateAlignConfig: clean-plate
-    alignment for calls that do not pass plate_align=."""
+    alignment for calls that do not pass plate_align=.
+    deflicker = None / "on" / "radius=2,tol=12" (any subset) / a deflicker.DeflickerConfig: inpaint deflicker for calls that do not pass
+    deflicker=."""
     global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi, _spans, _mask_clean, _tone_match, _grain_match
-    global _seam_blend, _plate_fill, _plate_align
+    global _seam_blend, _plate_fill, _plate_align, _deflicker
+    deflicker_settings.as_config(deflicker)
     platealign.as_config(plate_align)
     platefill.as_config(plate_fill)
     seamblend.as_config(seam_blend)
@@ -115,6 +124,7 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     _seam_blend = seam_blend
     _plate_fill = plate_fill
     _plate_align = plate_align
+    _deflicker = deflicker
 
 
 def _resolve_weights(ckpt):
@@ -228,10 +238,20 @@ def plate_align_config(plate_align=None):
     return platealign.as_config(os.environ.get("VV_PLATE_ALIGN"))
 
 
+def deflicker_config(deflicker=None):
+    """The inpaint deflicker setting a call runs with: its own deflicker= argument, else configure(deflicker=...), else $VV_DEFLICKER (on | off |
+    radius=N,tol=N).  None = no deflicker.  deflicker="off" (or False) asks for none whatever configure() or the environment say."""
+    if deflicker is not None:
+        return deflicker_settings.as_config(deflicker)
+    if _deflicker is not None:
+        return deflicker_settings.as_config(_deflicker)
+    return deflicker_settings.as_config(os.environ.get("VV_DEFLICKER"))
+
+
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
-                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, plate_align=None, plate_fill=None):
+                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, plate_align=None, plate_fill=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -278,14 +298,22 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     include/vvalign.h) and runs the fill on the canvas in which the background stands still, so that a slow pan or tilt, or a static overlay
     over a panning shot, is filled from the frames that show its background at another place.  A frame the tracker loses gives no sample
     and keeps its mask; a locked-off clip gives the bytes of the call without it.  What it found is kept in last_plate_align.  Without an
-    effective plate_fill it is a ValueError."""
-    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align
+    effective plate_fill it is a ValueError.
+    deflicker (inpaint deflicker, opt-in): "on" / "radius=2,tol=12" / a videovanish_amd.deflicker.DeflickerConfig filters the model's pixels
+    along time where they reach the device, for the full frame and for every roi window, inside each span (infill.finish; rules:
+    include/vvflicker.h): every pixel becomes the rounded mean of those of its neighbours at most `radius` frames away that lie within `tol`
+    levels of it in all three channels.  Flicker is averaged, a moving edge or a real change fails the gate and stays as it is; no byte moves
+    more than `tol` levels.  Tone matching, membrane blending and grain matching then measure the filtered rendering, and grain matching puts
+    back as moving grain the texture the averaging took out.  Nothing crosses the ends of a span.  What it changed is kept in
+    last_deflicker.  radius=0 gives the bytes of the call without it."""
+    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_deflicker
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
     ccfg = mask_clean_config(mask_clean)
     tcfg = tone_match_config(tone_match)
     gcfg = grain_match_config(grain_match)
-    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = None
+    fcfg = deflicker_config(deflicker)
+    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_deflicker = None
     pcfg = plate_fill_config(plate_fill)
     acfg = plate_align_config(plate_align)
     if acfg is not None and pcfg is None:
@@ -305,6 +333,8 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         raise ValueError("seam_blend= (seam membrane blending) cannot be combined with compat_reference_early_return=True")
     if pcfg is not None and compat_reference_early_return:
         raise ValueError("plate_fill= (clean-plate fill) cannot be combined with compat_reference_early_return=True")
+    if fcfg is not None and compat_reference_early_return:
+        raise ValueError("deflicker= (inpaint deflicker) cannot be combined with compat_reference_early_return=True")
 
     if prog is not None: prog(5, "dilating frames")
     dev = get_device()
@@ -334,11 +364,14 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     tone_parts = None if tcfg is None else []       # one report per clip call, in the order of the spans
     grain_parts = None if gcfg is None else []
     blend_parts = None if bcfg is None else []
+    flicker_parts = None if fcfg is None else []
 
     def body(frames, dil, prior, p, frame0=0):
         more = {} if gcfg is None else dict(grain=gcfg, grain_out=grain_parts, frame0=frame0)     # passed only when grain matching is on
         if bcfg is not None:                                                                       # likewise
             more.update(blend=bcfg, blend_out=blend_parts)
+        if fcfg is not None:                                                                       # likewise
+            more.update(flicker=fcfg, flicker_out=flicker_parts)
         return infill.run_clip(frames, dil, prior, rcfg, stages, p, dev, feather_px, keep_unmasked_original, compat_reference_early_return,
                                tone=tcfg, tone_out=tone_parts, **more)
 
@@ -356,6 +389,8 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         last_grain_match = infill.grain_report(grain_parts, plan, T)
     if bcfg is not None:
         last_seam_blend = infill.seam_blend_report(blend_parts, plan, T)
+    if fcfg is not None:
+        last_deflicker = infill.deflicker_report(flicker_parts, plan, T)
     return out
 
 
@@ -456,6 +491,16 @@ def _plate_align_arg(text):
     return text
 
 
+def _deflicker_arg(text):
+    """--deflicker's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --plate-align)."""
+    try:
+        if deflicker_settings.as_config(text) is None:
+            raise ValueError("not a setting")
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return text
+
+
 def _mask_clean_arg(text):
     """--mask-clean's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --roi / --spans)."""
     try:
@@ -510,6 +555,10 @@ def main():
                     help="With --plate-fill: track one integer translation per frame first (a coarse-to-fine search over `levels` pyramid levels, "
                          "+-`radius` at the coarsest; a frame whose best match differs by more than `max_residual` levels on average is left out) "
                          "and fill on the canvas in which the background stands still.  For slow pans and tilts.  Prints one line with what it tracked.")
+    ap.add_argument("--deflicker", type=_deflicker_arg, default=None, metavar="on|radius=2,tol=12",
+                    help="Inpaint deflicker before the seam stages: every pixel of the model's output becomes the mean of those of its neighbours at "
+                         "most `radius` frames away (on: 2) that lie within `tol` levels of it (on: 12), so the patch stops shimmering; what changes by "
+                         "more (a moving edge) stays as it is.  Prints one line with what it changed.")
     ap.add_argument("--cuts", type=span_plan.parse_cuts, default=None, metavar="120,431",
                     help="Frame indices (relative to --start_frame) where a new shot begins: used instead of the detector.")
     args = ap.parse_args()
@@ -535,6 +584,7 @@ def main():
     if args.seam_blend is not None: kw["seam_blend"] = args.seam_blend
     if args.plate_fill is not None: kw["plate_fill"] = args.plate_fill
     if args.plate_align is not None: kw["plate_align"] = args.plate_align
+    if args.deflicker is not None: kw["deflicker"] = args.deflicker
     out_frames = run_infill_on_frames(frames, mask_frames, propainer_frames=prior_frames, **kw)
     if args.mask_clean is not None and last_mask_clean is not None:
         r = last_mask_clean
@@ -565,6 +615,13 @@ def main():
         n = len(r.segments)
         print(f"plate align: {int(ok.sum())} of {ok.size} frames tracked, pan extent {max(span[:n])} x {max(span[n:])} px, "
               f"{sum(p == 'canvas' for p in r.path)} of {n} segments filled on a canvas")
+    if args.deflicker is not None and last_deflicker is not None:
+        r = last_deflicker
+        touched = (r.changed > 0).any(axis=0)
+        inside = int(r.n_mask.sum())
+        mean_n = float((r.samples_mask * r.n_mask).sum() / inside) if inside else 0.0
+        print(f"deflicker: {int(touched.sum())} of {touched.size} frames changed, mean accepted samples inside the mask {mean_n:.2f}, "
+              f"largest mean |shift| {float(r.shift.max(initial=0.0)):.2f}")
     tools.write_video_frames_to_path(out_video, out_frames, fps, H0, W0)
 
 

@@ -3,15 +3,15 @@
 no window, roi= "static" / "follow" one, the "-regions" spellings several.  With tone matching the closing step fits each window's pixels to the
 ring round the mask first (finish, tone_report); with grain matching it gives them the grain the ring's originals have and the model's pixels lack
 (finish, grain_report); with seam blending it adds the membrane that carries the ring's difference original - model into the hole (finish,
-seam_blend_report).  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is
-module state.  Rules and reasons: DESIGN.md §10, §11, §12, §13, §14, §15, §16, §17."""
+seam_blend_report); with the deflicker each window's model pixels are first filtered along time (finish, deflicker_report).  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is
+module state.  Rules and reasons: DESIGN.md §10, §11, §12, §13, §14, §15, §16, §17, §18."""
 import dataclasses
 from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
 
-from . import align_hip, blend_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platealign, platefill, seamblend, spans_hip, tone_hip, tonematch
+from . import align_hip, blend_hip, deflicker, flicker_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platealign, platefill, seamblend, spans_hip, tone_hip, tonematch
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -348,9 +348,9 @@ def region_plans(dil_t, H0, W0, feather_px, cfg):
 
 
 def run_clip(frames_rgb, dil_t, propainer_frames, rcfg, stages, prog, dev, feather_px=3, keep_unmasked_original=True,
-             compat_reference_early_return=False, tone=None, tone_out=None, grain=None, grain_out=None, frame0=0, blend=None, blend_out=None):
+             compat_reference_early_return=False, tone=None, tone_out=None, grain=None, grain_out=None, frame0=0, blend=None, blend_out=None, flicker=None, flicker_out=None):
     """One clip after the dilation: the windows rcfg asks for (none without it, or where the planner falls back to the full frame), run_windows,
-    finish.  The whole call without spans=, and each span's call with it.  tone / tone_out / grain / grain_out / frame0 / blend / blend_out: finish's."""
+    finish.  The whole call without spans=, and each span's call with it.  tone / tone_out / grain / grain_out / frame0 / blend / blend_out / flicker / flicker_out: finish's."""
     H0, W0 = frames_rgb[0].shape[:2]
     if rcfg is None:
         plans = []
@@ -363,6 +363,8 @@ def run_clip(frames_rgb, dil_t, propainer_frames, rcfg, stages, prog, dev, feath
     more = {} if grain is None else dict(grain=grain, grain_out=grain_out, frame0=frame0)       # passed only when grain matching is on
     if blend is not None:                                                                        # likewise
         more.update(blend=blend, blend_out=blend_out)
+    if flicker is not None:                                                                      # likewise
+        more.update(flicker=flicker, flicker_out=flicker_out)
     return finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return, tone, tone_out, **more)
 
 
@@ -467,8 +469,35 @@ def seam_blend_report(parts, spans, T, K=1):
     return rep
 
 
+class DeflickerReport(NamedTuple):
+    """What the inpaint deflicker did, per window k and frame t (K = 1 for the full frame), over the whole window and over its masked pixels
+    (`_mask`): the pixels counted, the pixels with any byte changed, the mean number of accepted samples and the mean |out - in| per channel in
+    8-bit levels (deflicker.DeflickerFit, stacked: closed forms of exact integer sums).  Frames outside every span, frames this rank does not
+    hold and windows a span does not have are zero rows."""
+    n: np.ndarray               # [K,T] int64
+    changed: np.ndarray         # [K,T] int64
+    samples: np.ndarray         # [K,T] float64
+    shift: np.ndarray           # [K,T,3] float64
+    n_mask: np.ndarray          # [K,T] int64
+    changed_mask: np.ndarray    # [K,T] int64
+    samples_mask: np.ndarray    # [K,T] float64
+    shift_mask: np.ndarray      # [K,T,3] float64
+
+
+def deflicker_report(parts, spans, T, K=1):
+    """The report of a call over T frames from its clips' reports: parts[i] (finish's flicker_out) covers the frames spans[i] = (a, b); at least K
+    windows."""
+    K = max([len(p.n) for p in parts] + [K])
+    half = lambda: (np.zeros((K, T), np.int64), np.zeros((K, T), np.int64), np.zeros((K, T)), np.zeros((K, T, 3)))
+    rep = DeflickerReport(*half(), *half())
+    for part, (a, b) in zip(parts, spans):
+        for whole, piece in zip(rep, part):
+            whole[:len(piece), a:b] = piece
+    return rep
+
+
 def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return=False, tone=None, tone_out=None,
-           grain=None, grain_out=None, frame0=0, blend=None, blend_out=None):
+           grain=None, grain_out=None, frame0=0, blend=None, blend_out=None, flicker=None, flicker_out=None):
     """The model's frames into frames of the original size.  No plan (reference :69-112): resize when the model ran at another size, feathered
     composite with the originals when keep_unmasked_original, in place in outs[0].  The reference returns from inside its loop (:114) so only
     frame 0 is post-processed; the evident intent (all frames) is the default here, compat_reference_early_return=True reproduces the quirk.
@@ -489,12 +518,34 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
     looked-up pixels against the running buffer gives the membrane, over groups of frames (seamblend.groups) that share one scratch buffer;
     paste_blend_composite in place of the paste adds it after the table and before the grain (zero amplitudes without grain, whose statistic
     stays on the tabled pixel without the membrane).  The clip's SeamBlendReport is appended to blend_out.  Without blend nothing here
-    changes and no vvb_ symbol is resolved."""
+    changes and no vvb_ symbol is resolved.
+    flicker (a deflicker.DeflickerConfig): per window, where its model frames are uploaded (model_px): the window's pixels
+    materialised at the window's size (flicker_hip.window_pixels), filtered along time inside this clip call (flicker_hip.hold; rules:
+    include/vvflicker.h); everything above then reads the filtered [n,h,w,3] patch at equal size with the same offsets, so tone, membrane and
+    grain measure the filtered rendering.  Two more window-sized clip buffers live on the device meanwhile.  A rank holds every frame of the
+    clip or none.  The clip's DeflickerReport is appended to flicker_out.  Without flicker model_px is the upload, nothing here changes and
+    no vvf_ symbol is resolved."""
     H0, W0 = frames_rgb[0].shape[:2]
     T = len(outs[0])
+    fsums = []      # deflicker: the [T,12] sums of every window filtered so far
+
+    def model_px(o, idx, up, offsets=None, size=None, offs=None, mask=None):
+        """Window frames o of the model on the device.  With flicker: as the window's h x w pixels (size; offsets [T,2] = the window's place per
+        frame, None = the full frame), filtered along time; offs / mask = offsets[idx] and dil_t[idx] where the caller has them on the device."""
+        if flicker is None:
+            return up(o).contiguous()
+        if len(idx) != T:
+            raise RuntimeError(f"deflicker: a rank holds every frame of a clip call or none, not {len(idx)} of {T}")
+        h, w = size or (H0, W0)
+        place = np.zeros((T, 2), np.int32) if offsets is None else np.ascontiguousarray(offsets[idx], np.int32)
+        win = flicker_hip.window_pixels(up(o).contiguous(), h, w)
+        held, sums = flicker_hip.hold(win, torch.from_numpy(place).to(dev) if offs is None else offs, dil_t[idx].contiguous() if mask is None else mask,
+                                      flicker.radius, flicker.tol, fixed=bool((place == place[0]).all()))
+        fsums.append(sums.cpu().numpy())
+        return held
 
     def full_frame(idx, up):
-        out = up(outs[0])
+        out = model_px(outs[0], idx, up)
         if tuple(out.shape[1:3]) != (H0, W0):
             out = hip.resize_u8(out.contiguous(), H0, W0, mode="bilinear")          # cv2.resize(f,(W0,H0)), :73
         if keep_unmasked_original:
@@ -507,7 +558,7 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
         mask = dil_t[idx].contiguous()
         for k, (plan, o) in enumerate(zip(plans, outs)):
             offs = torch.from_numpy(np.ascontiguousarray(plan.offsets[idx])).to(dev)
-            hip.roi_paste_composite(up(o).contiguous(), bufs[k % 2], mask, offs, *plan.size, float(feather_px if keep_unmasked_original else -1.0),
+            hip.roi_paste_composite(model_px(o, idx, up, plan.offsets, plan.size, offs, mask), bufs[k % 2], mask, offs, *plan.size, float(feather_px if keep_unmasked_original else -1.0),
                                     out=bufs[(k + 1) % 2])
         return bufs[len(plans) % 2]
 
@@ -519,7 +570,7 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
         fits = []
         for k, ((offsets, (h, w)), o) in enumerate(zip(wins, outs)):
             offs = torch.from_numpy(np.ascontiguousarray(offsets[idx], np.int32)).to(dev)
-            patch = up(o).contiguous()
+            patch = model_px(o, idx, up, offsets, (h, w), offs, mask)
             sums = np.zeros((T, tonematch.NSUM), np.int64)
             sums[idx] = tone_hip.ring_stats(patch, bufs[k % 2], mask, offs, h, w, tone.ring).cpu().numpy()
             fits.append(tonematch.fit(sums, tone))
@@ -540,7 +591,7 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
         tfits, gfits = [], []
         for k, ((offsets, (h, w)), o) in enumerate(zip(wins, outs)):
             offs = torch.from_numpy(np.ascontiguousarray(offsets[idx], np.int32)).to(dev)
-            patch = up(o).contiguous()
+            patch = model_px(o, idx, up, offsets, (h, w), offs, mask)
             lut = ident
             if tone is not None:
                 sums = np.zeros((T, tonematch.NSUM), np.int64)
@@ -577,7 +628,7 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
         tone_cfg = None if tone is None else dataclasses.replace(tone, mode="offset")
         for k, ((offsets, (h, w)), o) in enumerate(zip(wins, outs)):
             offs = torch.from_numpy(np.ascontiguousarray(offsets[idx], np.int32)).to(dev)
-            patch = up(o).contiguous()
+            patch = model_px(o, idx, up, offsets, (h, w), offs, mask)
             lut = ident
             if tone is not None:
                 sums = np.zeros((T, tonematch.NSUM), np.int64)
@@ -618,7 +669,13 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
             tone_out.append(tone_report([], [], T, K=max(len(plans), 1)))
         if grain is not None and grain_out is not None and len(grain_out) == done[1]:     # likewise: zero rows
             grain_out.append(grain_report([], [], T, K=max(len(plans), 1)))
-        return res
-    if not plans:
-        return _on_device(outs[0], 1 if compat_reference_early_return else len(outs[0]), dev, full_frame)
-    return _on_device(list(outs[0]), len(outs[0]), dev, windows)
+    elif not plans:
+        res = _on_device(outs[0], 1 if compat_reference_early_return else len(outs[0]), dev, full_frame)
+    else:
+        res = _on_device(list(outs[0]), len(outs[0]), dev, windows)
+    if flicker is not None and flicker_out is not None:
+        if fsums:
+            flicker_out.append(DeflickerReport(*(np.stack(f) for f in zip(*(deflicker.fit(s) for s in fsums)))))
+        else:                                                                             # this rank holds no frame of the clip: zero rows
+            flicker_out.append(deflicker_report([], [], T, K=max(len(plans), 1)))
+    return res
