@@ -435,14 +435,24 @@ def groupnorm(dtype, x0, gamma, beta, groups, eps, *, x1=None, F, HW, silu=False
     return out
 
 
-def motion_module_c320(dtype, x, stream_w, params, gamma, beta, groups, eps, *, F, HW, res1=None, out_dtype=torch.float32):
-    """The fused motion module (vv_motion.hip): clip-pooled GroupNorm statistics -> per-channel affine -> ONE kernel for the whole block."""
+def _own_out(out, shape, dtype, like, what):
+    """the caller's output tensor (out= of the fused level-0 wrappers; tests pass views into sentinel-filled buffers), or a fresh one"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != like.device or not out.is_contiguous():
+        raise RuntimeError(f"{what}: the given output must be a contiguous {dtype} tensor of shape {tuple(shape)} on {like.device}")
+    return out
+
+
+def motion_module_c320(dtype, x, stream_w, params, gamma, beta, groups, eps, *, F, HW, res1=None, out_dtype=torch.float32, out=None):
+    """The fused motion module (vv_motion.hip): clip-pooled GroupNorm statistics -> per-channel affine -> ONE kernel for the whole block.
+    out: write into the caller's contiguous [F * HW, C] tensor (its dtype is the output type) instead of a fresh one."""
     _need_cuda(x, stream_w, params, gamma, beta, res1)
     Cc = x.shape[-1]
     fin, keep = _gn_stats(dtype, x, gamma, beta, groups, eps, F, HW, 1)      # keep: owns fin until the launches below are enqueued
     aff = torch.empty((2, Cc), dtype=torch.float32, device=x.device)
     _check(lib().vv_gn_affine(fin, _p(gamma), _p(beta), Cc, groups, _p(aff), _stream()), "vv_gn_affine")
-    out = torch.empty((F * HW, Cc), dtype=out_dtype, device=x.device)
+    out = _own_out(out, (F * HW, Cc), out_dtype if out is None else out.dtype, x, "motion_module_c320")
     mp = MotionParams(x=_p(x), res1=_p(res1), out=_p(out), out_dtype=dt_of(out), stream=_p(stream_w), params=_p(params), gn_affine=_p(aff), C=Cc, F=F, heads=8, HW=HW,
                       n_slabs=stream_w.shape[0], n_params=params.numel())
     with _Prof("motion_module_fused[c320]", 2.0 * 22 * Cc * Cc * F * HW + 8.0 * F * Cc * F * HW, F * HW * Cc * (x.element_size() * 2 + out.element_size())):
@@ -792,15 +802,15 @@ def _packing():
     return packing
 
 
-def spatial_chain_c320(dtype, o, t_in, x, stream_w, params, *, res1=None, out_dtype=torch.float32, o_hw=0):
+def spatial_chain_c320(dtype, o, t_in, x, stream_w, params, *, res1=None, out_dtype=torch.float32, o_hw=0, out=None):
     """The fused tail of a level-0 spatial transformer block (vv_chain.hip): attn1 out-proj + residual, cross-attention to the text tokens,
     GEGLU feed-forward, proj_out + block residual in ONE kernel.  o: h16 [M,320] (o_hw = 0), or head-major [M / o_hw, 8, o_hw, 40] as vv_attention writes it
-    with o_hs = o_hw * 40; t_in, x (, res1): fp32 [M,320]."""
+    with o_hs = o_hw * 40; t_in, x (, res1): fp32 [M,320].  out: write into the caller's contiguous [M,320] tensor (its dtype is the output type)."""
     _need_cuda(o, t_in, x, stream_w, params, res1)
     M, Cc = t_in.shape
     assert o.numel() == M * Cc and x.shape == (M, Cc) and o.dtype == h16(dtype) and t_in.dtype == x.dtype == torch.float32
     assert (o.shape == (M, Cc)) if o_hw == 0 else (M % o_hw == 0 and o.is_contiguous())
-    out = torch.empty((M, Cc), dtype=out_dtype, device=x.device)
+    out = _own_out(out, (M, Cc), out_dtype if out is None else out.dtype, x, "spatial_chain_c320")
     cp = ChainParams(o=_p(o), t_in=_p(t_in), x=_p(x), res1=_p(res1), out=_p(out),
                      out_dtype=dt_of(out), stream=_p(stream_w), params=_p(params), M=M, C=Cc, heads=8, text_len=77,
                      n_slabs=stream_w.shape[0], n_params=params.numel(), layout=CHAIN_LAYOUT_IDS[_packing().CHAIN_LAYOUT], o_hw=int(o_hw))
@@ -813,10 +823,11 @@ def spatial_chain_c320(dtype, o, t_in, x, stream_w, params, *, res1=None, out_dt
 CHAIN_FRONT_MIN_HW = 9      # vv_spatial_chain_front_c320 stages the GroupNorm affine rows of the <= 127 / HW + 2 frames a 128-token block touches: 16 fit
 
 
-def spatial_chain_front_c320(dtype, x, gamma, beta, groups, eps, stream_w, params, *, F, HW, partials=None):
+def spatial_chain_front_c320(dtype, x, gamma, beta, groups, eps, stream_w, params, *, F, HW, partials=None, t_out=None, qkv_out=None):
     """The fused front of a level-0 spatial transformer block (vv_chain.hip): per-frame GroupNorm statistics -> per-channel affine -> ONE kernel for
     GroupNorm apply + proj_in + LayerNorm + the fused q|k|v projection.  Returns (t fp32 [M,320] = the block's residual stream, qkv h16 head-major
-    [F][3][8][HW][40]).  HW >= CHAIN_FRONT_MIN_HW tokens per frame: the library refuses smaller frames (nn.SpatialTransformer runs them layer by layer)."""
+    [F][3][8][HW][40]).  HW >= CHAIN_FRONT_MIN_HW tokens per frame: the library refuses smaller frames (nn.SpatialTransformer runs them layer by layer).
+    t_out / qkv_out: write into the caller's contiguous tensors of those shapes instead of fresh ones."""
     _need_cuda(x, gamma, beta, stream_w, params)
     M, Cc = x.shape
     assert M == F * HW and x.dtype == torch.float32
@@ -828,8 +839,8 @@ def spatial_chain_front_c320(dtype, x, gamma, beta, groups, eps, stream_w, param
     else:
         fin, keep = _gn_stats(dtype, x, gamma, beta, groups, eps, F, HW, 0)
     _check(lib().vv_gn_affine_frames(fin, _p(gamma), _p(beta), Cc, groups, F, _p(aff), _stream()), "vv_gn_affine_frames")
-    t = torch.empty((M, Cc), dtype=torch.float32, device=x.device)
-    qkv = torch.empty((F, 3, 8, HW, Cc // 8), dtype=h16(dtype), device=x.device)
+    t = _own_out(t_out, (M, Cc), torch.float32, x, "spatial_chain_front_c320 (t_out)")
+    qkv = _own_out(qkv_out, (F, 3, 8, HW, Cc // 8), h16(dtype), x, "spatial_chain_front_c320 (qkv_out)")
     fp = ChainFrontParams(x=_p(x), gn_affine=_p(aff), t_out=_p(t), qkv=_p(qkv), stream=_p(stream_w),
                           params=_p(params), M=M, HW=HW, C=Cc, heads=8, n_slabs=stream_w.shape[0], n_params=params.numel())
     with _Prof("spatial_chain_front_fused[c320]", 2.0 * M * Cc * Cc * 4, M * Cc * (4 + 4 + 6)):
