@@ -16,7 +16,9 @@ configure(plate_fill=...) and $VV_PLATE_FILL), plate_align (clean-plate alignmen
 tracked first, so that the fill follows a panning camera: videovanish_amd/platealign.py; also configure(plate_align=...) and $VV_PLATE_ALIGN),
 deflicker (inpaint deflicker: the model's pixels are filtered along time before every other seam stage reads them, each the mean of its temporal
 neighbours within a tolerance, so that the patch stops shimmering while moving edges stay as they are: videovanish_amd/deflicker.py; also
-configure(deflicker=...) and $VV_DEFLICKER).
+configure(deflicker=...) and $VV_DEFLICKER), deflicker_align (aligned inpaint deflicker: with deflicker, one integer translation per frame is
+tracked first, so that the filter follows a panning camera: videovanish_amd/deflickeralign.py; also configure(deflicker_align=...) and
+$VV_DEFLICKER_ALIGN).
 There is no CPU fallback: without the HIP extension / a GPU this raises.
 
 This file is the boundary: the reference's names and module state, the settings, and the stages (weights, prior, model) that read that state.
@@ -30,7 +32,7 @@ import torch
 
 from videovanish_amd import hip, infill
 from videovanish_amd import deflicker as deflicker_settings
-from videovanish_amd import grainmatch, maskclean, platealign, platefill, seamblend, tonematch
+from videovanish_amd import deflickeralign, grainmatch, maskclean, platealign, platefill, seamblend, tonematch
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
 from videovanish_amd.config import RunConfig
@@ -64,10 +66,12 @@ _plate_align = None     # configure(plate_align=...): clean-plate alignment for 
 last_plate_align = None # the infill.PlateAlignReport of the last run_infill_on_frames call; None when the tracker did not run
 _deflicker = None       # configure(deflicker=...): inpaint deflicker for calls that do not pass deflicker= themselves
 last_deflicker = None   # the infill.DeflickerReport of the last run_infill_on_frames call; None when the stage did not run
+_deflicker_align = None      # configure(deflicker_align=...): aligned inpaint deflicker for calls that do not pass deflicker_align= themselves
+last_deflicker_align = None  # the infill.DeflickerAlignReport of the last run_infill_on_frames call; None when the tracker did not run
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
-              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, plate_align=None, plate_fill=None):
+              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, plate_align=None, plate_fill=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -97,9 +101,12 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     plate_align = None / "on" / "levels=4,radius=4,min_overlap=25,max_residual=12" (any subset) / a platealign.PlateAlignConfig: clean-plate
     alignment for calls that do not pass plate_align=.
     deflicker = None / "on" / "radius=2,tol=12" (any subset) / a deflicker.DeflickerConfig: inpaint deflicker for calls that do not pass
-    deflicker=."""
+    deflicker=.
+    deflicker_align = None / "on" / "levels=4,radius=4,min_overlap=25,max_residual=12" (any subset) / a platealign.PlateAlignConfig: aligned
+    inpaint deflicker for calls that do not pass deflicker_align=."""
     global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi, _spans, _mask_clean, _tone_match, _grain_match
-    global _seam_blend, _plate_fill, _plate_align, _deflicker
+    global _seam_blend, _plate_fill, _plate_align, _deflicker, _deflicker_align
+    deflickeralign.as_config(deflicker_align)
     deflicker_settings.as_config(deflicker)
     platealign.as_config(plate_align)
     platefill.as_config(plate_fill)
@@ -125,6 +132,7 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     _plate_fill = plate_fill
     _plate_align = plate_align
     _deflicker = deflicker
+    _deflicker_align = deflicker_align
 
 
 def _resolve_weights(ckpt):
@@ -248,10 +256,21 @@ def deflicker_config(deflicker=None):
     return deflicker_settings.as_config(os.environ.get("VV_DEFLICKER"))
 
 
+def deflicker_align_config(deflicker_align=None):
+    """The aligned-deflicker setting a call runs with: its own deflicker_align= argument, else configure(deflicker_align=...), else
+    $VV_DEFLICKER_ALIGN (on | off | levels=N,radius=N,min_overlap=N,max_residual=N).  None = the filter stays at a fixed frame place.
+    deflicker_align="off" (or False) asks for none whatever configure() or the environment say."""
+    if deflicker_align is not None:
+        return deflickeralign.as_config(deflicker_align)
+    if _deflicker_align is not None:
+        return deflickeralign.as_config(_deflicker_align)
+    return deflickeralign.as_config(os.environ.get("VV_DEFLICKER_ALIGN"))
+
+
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
-                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, plate_align=None, plate_fill=None):
+                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, plate_align=None, plate_fill=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -305,19 +324,29 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     levels of it in all three channels.  Flicker is averaged, a moving edge or a real change fails the gate and stays as it is; no byte moves
     more than `tol` levels.  Tone matching, membrane blending and grain matching then measure the filtered rendering, and grain matching puts
     back as moving grain the texture the averaging took out.  Nothing crosses the ends of a span.  What it changed is kept in
-    last_deflicker.  radius=0 gives the bytes of the call without it."""
-    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_deflicker
+    last_deflicker.  radius=0 gives the bytes of the call without it.
+    deflicker_align (aligned inpaint deflicker, opt-in, needs deflicker): "on" / "levels=4,radius=4,min_overlap=25,max_residual=12" / a
+    videovanish_amd.platealign.PlateAlignConfig tracks, per clip call (per span), one integer translation per frame on the frames and dilated
+    masks that call works on (the tracker of plate_align; rules: include/vvalign.h) and reads every temporal neighbour of the filter at the
+    place where the same piece of background sits in that neighbour frame (rules: include/vvflickalign.h), so that the patch stops shimmering
+    under a pan or tilt too.  A frame the tracker loses takes no sample and gives none; after a cut inside a clip call every later frame is
+    lost and stays unfiltered: spans="cuts" (or "masked-cuts") splits the call there.  A locked-off clip gives the bytes of deflicker alone.
+    What it found is kept in last_deflicker_align.  Without an effective deflicker it is a ValueError."""
+    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_deflicker, last_deflicker_align
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
     ccfg = mask_clean_config(mask_clean)
     tcfg = tone_match_config(tone_match)
     gcfg = grain_match_config(grain_match)
     fcfg = deflicker_config(deflicker)
-    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_deflicker = None
+    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_deflicker = last_deflicker_align = None
     pcfg = plate_fill_config(plate_fill)
     acfg = plate_align_config(plate_align)
     if acfg is not None and pcfg is None:
         raise ValueError("plate_align= (clean-plate alignment) needs plate_fill= (clean-plate fill)")
+    facfg = deflicker_align_config(deflicker_align)
+    if facfg is not None and fcfg is None:
+        raise ValueError("deflicker_align= (aligned inpaint deflicker) needs deflicker= (inpaint deflicker)")
     bcfg = seam_blend_config(seam_blend, feather_px if keep_unmasked_original else None)
     if rcfg is not None and compat_reference_early_return:
         raise ValueError("roi= (mask-region inference) cannot be combined with compat_reference_early_return=True")
@@ -365,6 +394,7 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     grain_parts = None if gcfg is None else []
     blend_parts = None if bcfg is None else []
     flicker_parts = None if fcfg is None else []
+    falign_parts = None if facfg is None else []
 
     def body(frames, dil, prior, p, frame0=0):
         more = {} if gcfg is None else dict(grain=gcfg, grain_out=grain_parts, frame0=frame0)     # passed only when grain matching is on
@@ -372,6 +402,8 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
             more.update(blend=bcfg, blend_out=blend_parts)
         if fcfg is not None:                                                                       # likewise
             more.update(flicker=fcfg, flicker_out=flicker_parts)
+        if facfg is not None:                                                                      # likewise
+            more.update(flicker_align=facfg, flicker_align_out=falign_parts)
         return infill.run_clip(frames, dil, prior, rcfg, stages, p, dev, feather_px, keep_unmasked_original, compat_reference_early_return,
                                tone=tcfg, tone_out=tone_parts, **more)
 
@@ -391,6 +423,8 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         last_seam_blend = infill.seam_blend_report(blend_parts, plan, T)
     if fcfg is not None:
         last_deflicker = infill.deflicker_report(flicker_parts, plan, T)
+    if facfg is not None:
+        last_deflicker_align = infill.deflicker_align_report(falign_parts, plan)
     return out
 
 
@@ -501,6 +535,16 @@ def _deflicker_arg(text):
     return text
 
 
+def _deflicker_align_arg(text):
+    """--deflicker-align's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --deflicker)."""
+    try:
+        if deflickeralign.as_config(text) is None:
+            raise ValueError("not a setting")
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return text
+
+
 def _mask_clean_arg(text):
     """--mask-clean's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --roi / --spans)."""
     try:
@@ -559,6 +603,10 @@ def main():
                     help="Inpaint deflicker before the seam stages: every pixel of the model's output becomes the mean of those of its neighbours at "
                          "most `radius` frames away (on: 2) that lie within `tol` levels of it (on: 12), so the patch stops shimmering; what changes by "
                          "more (a moving edge) stays as it is.  Prints one line with what it changed.")
+    ap.add_argument("--deflicker-align", type=_deflicker_align_arg, default=None, metavar="on|levels=4,radius=4,min_overlap=25,max_residual=12",
+                    help="With --deflicker: track one integer translation per frame first (the tracker of --plate-align, per span) and read the "
+                         "filter's temporal neighbours along it, so the patch stops shimmering under a pan or tilt too.  A frame the tracker "
+                         "loses stays unfiltered; split at cuts with --spans cuts.  Prints one line with what it tracked.")
     ap.add_argument("--cuts", type=span_plan.parse_cuts, default=None, metavar="120,431",
                     help="Frame indices (relative to --start_frame) where a new shot begins: used instead of the detector.")
     args = ap.parse_args()
@@ -585,6 +633,7 @@ def main():
     if args.plate_fill is not None: kw["plate_fill"] = args.plate_fill
     if args.plate_align is not None: kw["plate_align"] = args.plate_align
     if args.deflicker is not None: kw["deflicker"] = args.deflicker
+    if args.deflicker_align is not None: kw["deflicker_align"] = args.deflicker_align
     out_frames = run_infill_on_frames(frames, mask_frames, propainer_frames=prior_frames, **kw)
     if args.mask_clean is not None and last_mask_clean is not None:
         r = last_mask_clean
@@ -622,6 +671,12 @@ def main():
         mean_n = float((r.samples_mask * r.n_mask).sum() / inside) if inside else 0.0
         print(f"deflicker: {int(touched.sum())} of {touched.size} frames changed, mean accepted samples inside the mask {mean_n:.2f}, "
               f"largest mean |shift| {float(r.shift.max(initial=0.0)):.2f}")
+    if args.deflicker_align is not None and last_deflicker_align is not None:
+        r = last_deflicker_align
+        paths = ", ".join(f"{sum(p == name for p in r.path)} {name}" for name in deflickeralign.PATHS if name in r.path) or "no clip call"
+        lost = sum(int((~k).sum()) for k in r.tracked)
+        far = max([int(np.abs(o[k]).max()) for o, k in zip(r.off, r.tracked) if k.any()] + [0])
+        print(f"deflicker align: {len(r.path)} clip calls ({paths}), {lost} of {sum(len(k) for k in r.tracked)} frames lost, largest |offset| {far} px")
     tools.write_video_frames_to_path(out_video, out_frames, fps, H0, W0)
 
 

@@ -2,6 +2,7 @@
 // The rules are include/vvflicker.h's; all arithmetic is integer.
 //   vvf_window_pixels   the window's pixels as vv_roi_paste_composite reads them (vv_paste_px.h), materialised: patch [T][Hm][Wm][3] -> win [T][h][w][3]
 //   vvf_hold            per pixel the rounded mean of the temporal neighbours within tol, out [T][h][w][3], and 12 integer sums per frame
+//   vvc_hold            the same along a tracked camera translation (include/vvflickalign.h): the gather form's body
 // vvf_hold has two forms, chosen by the launcher from its arguments alone.
 //   fixed    the window stands at one place in every frame and w % 4 == 0.  A streaming kernel over [T][h][w][3] u8, as vv_plate.hip's family:
 //            a thread owns 4 adjacent pixels of one row (12 bytes: one dwordx3 load per frame, lane after lane contiguous) and walks the frames
@@ -14,6 +15,7 @@
 // integer adds in any order.  out_c = (2 S_c + n) / (2 n) is a multiplication by a 20-bit reciprocal, exact for every S_c <= 255 n, n <= 9.
 #include "vv_paste_px.h"
 #include "../../include/vvflicker.h"
+#include "../../include/vvflickalign.h"
 
 namespace {
 
@@ -21,6 +23,7 @@ constexpr int FB = 256;                     // threads per block
 constexpr int NSUM = 12;
 typedef unsigned long long u64;
 static_assert(VVF_MAX_RADIUS == 4 && 2 * VVF_MAX_RADIUS + 1 <= 9, "n <= 9: the reciprocals, the packed sums");
+static_assert(VVC_MAX_RADIUS == VVF_MAX_RADIUS && VVC_MAX_T == VVF_MAX_T, "vvc_hold shares vvf_hold's limits");
 static_assert(64 * 4 * 255 < (1 << 16) && 64 * 4 * 9 < (1 << 16), "a wave's sums of 4 pixels per lane fit the 16-bit halves");
 
 struct __attribute__((aligned(4))) U3 { unsigned a, b, c; };
@@ -167,28 +170,46 @@ __global__ __launch_bounds__(FB) void hold_fixed_kernel(const uint8_t* __restric
 }
 
 // grid (ceil(h w / FB), T): frame = blockIdx.y.  Reads of win are bounds-checked against the window of the frame they come from, reads of the mask
-// against the frame, whatever the offsets hold; the writes are the thread's own 3 bytes of out and the atomics into sums[t].
-__global__ __launch_bounds__(FB) void hold_gather_kernel(const uint8_t* __restrict__ win, const int* __restrict__ offsets, const uint8_t* __restrict__ mask,
-                                                         int T, int H0, int W0, int h, int w, int R, int tol, uint8_t* __restrict__ out,
-                                                         u64* __restrict__ sums) {
+// against the frame, whatever the offsets (and the track) hold; the writes are the thread's own 3 bytes of out and the atomics into sums[t].
+// TRACKED (vvc_hold, include/vvflickalign.h): the neighbour s is read at the pixel's place moved by e_t - e_s, e = offsets + the tracked offset.
+// That displacement (taken in 64 bits) and whether s gives a sample at all (not t, both frames tracked, the windows overlap) are the same for
+// every pixel of the block: they come from scalar loads at addresses made of blockIdx and the loop counter and stay in scalar registers.
+template <bool TRACKED>
+__global__ __launch_bounds__(FB) void hold_gather_kernel(const uint8_t* __restrict__ win, const int* __restrict__ offsets, const int32_t* __restrict__ track,
+                                                         const uint8_t* __restrict__ mask, int T, int H0, int W0, int h, int w, int R, int tol,
+                                                         uint8_t* __restrict__ out, u64* __restrict__ sums) {
     __shared__ unsigned mg[10];
     __shared__ unsigned tot[NSUM];
+    const int t = (int)blockIdx.y;
     if (threadIdx.x < NSUM) tot[threadIdx.x] = 0;
     if (threadIdx.x < 10) mg[threadIdx.x] = threadIdx.x ? recip(threadIdx.x) : 0u;
     __syncthreads();
-    const int t = (int)blockIdx.y;
     const int64_t N = (int64_t)h * w, i = (int64_t)blockIdx.x * FB + threadIdx.x;
     const bool active = i < N;
     unsigned lo[3] = {0u, 0u, 0u}, hi[3] = {0u, 0u, 0u};
     if (active) {
-        const int py = offsets[t * 2 + 0] + (int)(i / w), px = offsets[t * 2 + 1] + (int)(i % w);
+        const int yy = (int)(i / w), xx = (int)(i % w);
+        const int py = offsets[t * 2 + 0] + yy, px = offsets[t * 2 + 1] + xx;
         const uint8_t* c = win + ((int64_t)t * N + i) * 3;
         const unsigned x[3] = {c[0], c[1], c[2]};
         unsigned S[3] = {x[0], x[1], x[2]}, n = 1;
         const int s0 = max(t - R, 0), s1 = min(t + R, T - 1);
+        // TRACKED: e_t, and below e_s and whether s gives samples at all, depend on blockIdx and the loop counter only: scalar loads, scalar registers
+        const bool t_tracked = TRACKED && track[t * VVC_TRACK_INTS + 3] == 1;
+        const int64_t ety = TRACKED ? (int64_t)offsets[t * 2 + 0] + track[t * VVC_TRACK_INTS + 1] : 0, etx = TRACKED ? (int64_t)offsets[t * 2 + 1] + track[t * VVC_TRACK_INTS + 0] : 0;
         for (int s = s0; s <= s1; ++s) {
-            const int ys = py - offsets[s * 2 + 0], xs = px - offsets[s * 2 + 1];
-            if (s == t || ys < 0 || ys >= h || xs < 0 || xs >= w) continue;
+            int ys, xs;
+            if constexpr (TRACKED) {
+                if (s == t || !t_tracked || track[s * VVC_TRACK_INTS + 3] != 1) continue;
+                const int64_t dy = ety - ((int64_t)offsets[s * 2 + 0] + track[s * VVC_TRACK_INTS + 1]), dx = etx - ((int64_t)offsets[s * 2 + 1] + track[s * VVC_TRACK_INTS + 0]);
+                if (dy <= -(int64_t)h || dy >= h || dx <= -(int64_t)w || dx >= w) continue;         // the windows share no pixel
+                // |dy| < h, |dx| < w: the sums lie in (-2^31, 2^32), so one unsigned compare per axis tells inside from outside
+                ys = (int)((unsigned)yy + (unsigned)(int)dy); xs = (int)((unsigned)xx + (unsigned)(int)dx);
+                if ((unsigned)ys >= (unsigned)h || (unsigned)xs >= (unsigned)w) continue;
+            } else {
+                ys = py - offsets[s * 2 + 0]; xs = px - offsets[s * 2 + 1];
+                if (s == t || ys < 0 || ys >= h || xs < 0 || xs >= w) continue;
+            }
             const uint8_t* q = win + (((int64_t)s * h + ys) * w + xs) * 3;
             const unsigned v[3] = {q[0], q[1], q[2]};
             const unsigned ok = max(max(absdiff(v[0], x[0]), absdiff(v[1], x[1])), absdiff(v[2], x[2])) <= (unsigned)tol ? 1u : 0u;
@@ -255,9 +276,29 @@ extern "C" int vvf_hold(const uint8_t* win, const int* offsets, const uint8_t* m
         }
 #undef VVF_FIXED
     } else {
-        hipLaunchKernelGGL(hold_gather_kernel, dim3((unsigned)((N + FB - 1) / FB), (unsigned)T), dim3(FB), 0, st, win, offsets, mask2d, T, H0, W0, h, w, radius,
-                           tol, out, (u64*)sums);
+        hipLaunchKernelGGL(hold_gather_kernel<false>, dim3((unsigned)((N + FB - 1) / FB), (unsigned)T), dim3(FB), 0, st, win, offsets, (const int32_t*)nullptr,
+                           mask2d, T, H0, W0, h, w, radius, tol, out, (u64*)sums);
     }
     VV_CHECK_LAUNCH("vvf_hold");
+    return VV_OK;
+}
+
+extern "C" int vvc_abi_version(void) { return VVC_ABI_VERSION; }
+extern "C" const char* vvc_last_error(void) { return vv_last_error(); }
+
+extern "C" int vvc_hold(const uint8_t* win, const int* offsets, const int32_t* track, const uint8_t* mask2d, int T, int H0, int W0, int h, int w, int radius,
+                        int tol, uint8_t* out, int64_t* sums, void* stream) {
+    if (!win || !offsets || !track || !mask2d || !out || !sums || T <= 0 || H0 <= 0 || W0 <= 0 || h <= 0 || w <= 0 || h > H0 || w > W0 || radius < 0 ||
+        tol < 0 || out == win)
+        VV_FAIL(VV_E_ARG, "vvc_hold: bad args (no null pointer, sizes > 0, h <= H0, w <= W0, radius >= 0, tol >= 0, out is not win)");
+    if (radius > VVC_MAX_RADIUS || tol > 255 || T > VVC_MAX_T || (int64_t)h * w >= ((int64_t)1 << 31))
+        VV_FAIL(VV_E_UNSUPPORTED, "vvc_hold: radius <= %d, tol <= 255, T <= %d and h * w < 2^31 are supported, not radius %d, tol %d, T %d, %d x %d",
+                VVC_MAX_RADIUS, VVC_MAX_T, radius, tol, T, h, w);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(sums, 0, (size_t)T * NSUM * sizeof(int64_t), st) != hipSuccess) VV_FAIL(VV_E_LAUNCH, "vvc_hold: memset failed");
+    const int64_t N = (int64_t)h * w;
+    hipLaunchKernelGGL(hold_gather_kernel<true>, dim3((unsigned)((N + FB - 1) / FB), (unsigned)T), dim3(FB), 0, st, win, offsets, track, mask2d, T, H0, W0, h, w,
+                       radius, tol, out, (u64*)sums);
+    VV_CHECK_LAUNCH("vvc_hold");
     return VV_OK;
 }

@@ -3,15 +3,16 @@
 no window, roi= "static" / "follow" one, the "-regions" spellings several.  With tone matching the closing step fits each window's pixels to the
 ring round the mask first (finish, tone_report); with grain matching it gives them the grain the ring's originals have and the model's pixels lack
 (finish, grain_report); with seam blending it adds the membrane that carries the ring's difference original - model into the hole (finish,
-seam_blend_report); with the deflicker each window's model pixels are first filtered along time (finish, deflicker_report).  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is
-module state.  Rules and reasons: DESIGN.md §10, §11, §12, §13, §14, §15, §16, §17, §18."""
+seam_blend_report); with the deflicker each window's model pixels are first filtered along time (finish, deflicker_report), with its alignment along a translation tracked per clip call
+(finish, deflicker_align_report).  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is
+module state.  Rules and reasons: DESIGN.md §10, §11, §12, §13, §14, §15, §16, §17, §18, §19."""
 import dataclasses
 from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
 
-from . import align_hip, blend_hip, deflicker, flicker_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platealign, platefill, seamblend, spans_hip, tone_hip, tonematch
+from . import align_hip, blend_hip, deflicker, deflickeralign, flickalign_hip, flicker_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platealign, platefill, seamblend, spans_hip, tone_hip, tonematch
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -348,9 +349,11 @@ def region_plans(dil_t, H0, W0, feather_px, cfg):
 
 
 def run_clip(frames_rgb, dil_t, propainer_frames, rcfg, stages, prog, dev, feather_px=3, keep_unmasked_original=True,
-             compat_reference_early_return=False, tone=None, tone_out=None, grain=None, grain_out=None, frame0=0, blend=None, blend_out=None, flicker=None, flicker_out=None):
+             compat_reference_early_return=False, tone=None, tone_out=None, grain=None, grain_out=None, frame0=0, blend=None, blend_out=None, flicker=None, flicker_out=None,
+             flicker_align=None, flicker_align_out=None):
     """One clip after the dilation: the windows rcfg asks for (none without it, or where the planner falls back to the full frame), run_windows,
-    finish.  The whole call without spans=, and each span's call with it.  tone / tone_out / grain / grain_out / frame0 / blend / blend_out / flicker / flicker_out: finish's."""
+    finish.  The whole call without spans=, and each span's call with it.  tone / tone_out / grain / grain_out / frame0 / blend / blend_out / flicker / flicker_out /
+    flicker_align / flicker_align_out: finish's."""
     H0, W0 = frames_rgb[0].shape[:2]
     if rcfg is None:
         plans = []
@@ -365,6 +368,8 @@ def run_clip(frames_rgb, dil_t, propainer_frames, rcfg, stages, prog, dev, feath
         more.update(blend=blend, blend_out=blend_out)
     if flicker is not None:                                                                      # likewise
         more.update(flicker=flicker, flicker_out=flicker_out)
+    if flicker_align is not None:                                                                # likewise
+        more.update(flicker_align=flicker_align, flicker_align_out=flicker_align_out)
     return finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return, tone, tone_out, **more)
 
 
@@ -496,8 +501,30 @@ def deflicker_report(parts, spans, T, K=1):
     return rep
 
 
+class DeflickerAlignReport(NamedTuple):
+    """What the tracker of finish(flicker_align=) found, per clip call of `segments` (a tuple each; the spans of the call, (0, T) without spans):
+    off [n,2] int32 = the frame's (x, y) on the canvas in which the background stands still, key [n] = the key frame it was tracked against,
+    tracked [n] bool (a lost frame is left unfiltered), residual [n] = the mean absolute luma difference of its level-0 best (0 for frame 0 and
+    a lost frame), and the path that ran: "tracked" (flickalign_hip.hold), "static" (one frame, or every frame tracked at offset zero: the
+    unaligned filter as it is), "untracked" (the clip is beyond the tracker's limits: the unaligned filter) or "none" (this rank holds no
+    frame of the clip call: nothing tracked, nothing filtered)."""
+    off: tuple
+    key: tuple
+    tracked: tuple
+    residual: tuple
+    path: tuple
+    segments: tuple
+
+
+def deflicker_align_report(parts, spans):
+    """The report of a call from its clips' records: parts[i] (finish's flicker_align_out) = (track [n,8] on the host, path) of the clip call
+    over the frames spans[i] = (a, b)."""
+    cols = [(tr[:, :2].copy(), tr[:, 2].copy(), tr[:, 3] == 1, _residual(tr), path) for tr, path in parts]
+    return DeflickerAlignReport(*(tuple(c) for c in ([list(v) for v in zip(*cols)] or [[] for _ in range(5)])), tuple(tuple(s) for s in spans))
+
+
 def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return=False, tone=None, tone_out=None,
-           grain=None, grain_out=None, frame0=0, blend=None, blend_out=None, flicker=None, flicker_out=None):
+           grain=None, grain_out=None, frame0=0, blend=None, blend_out=None, flicker=None, flicker_out=None, flicker_align=None, flicker_align_out=None):
     """The model's frames into frames of the original size.  No plan (reference :69-112): resize when the model ran at another size, feathered
     composite with the originals when keep_unmasked_original, in place in outs[0].  The reference returns from inside its loop (:114) so only
     frame 0 is post-processed; the evident intent (all frames) is the default here, compat_reference_early_return=True reproduces the quirk.
@@ -524,10 +551,29 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
     include/vvflicker.h); everything above then reads the filtered [n,h,w,3] patch at equal size with the same offsets, so tone, membrane and
     grain measure the filtered rendering.  Two more window-sized clip buffers live on the device meanwhile.  A rank holds every frame of the
     clip or none.  The clip's DeflickerReport is appended to flicker_out.  Without flicker model_px is the upload, nothing here changes and
-    no vvf_ symbol is resolved."""
+    no vvf_ symbol is resolved.
+    flicker_align (a platealign.PlateAlignConfig, with flicker; rules: include/vvflickalign.h): the first model_px of the clip
+    call tracks one integer translation per frame on the call's own frames and dilated masks (_track_segment: the pyramid in batches of
+    deflickeralign.TRACK_BYTES, one synchronisation); the track stays on the device and serves every window, whose neighbours are then read
+    along it (flickalign_hip.hold in place of flicker_hip.hold).  A clip beyond the tracker's limits ("untracked"), a single frame and a clip
+    whose frames all sit at offset zero ("static") take the unaligned filter exactly as above, fixed form included.  A frame the tracker
+    loses (after a cut inside the clip call: every later frame) stays unfiltered.  (track, path) of the clip call is appended to
+    flicker_align_out (deflicker_align_report).  Without flicker_align nothing here changes and no vvc_ symbol is resolved."""
     H0, W0 = frames_rgb[0].shape[:2]
     T = len(outs[0])
     fsums = []      # deflicker: the [T,12] sums of every window filtered so far
+    ftrack = []     # deflicker_align: (track on the device | None, track on the host, path) of this clip call, found by the first model_px
+
+    def tracked():
+        if not ftrack:
+            if not platealign.trackable(T, H0, W0):
+                ftrack.append((None, deflickeralign.identity_track(T), "untracked"))
+            elif T == 1:
+                ftrack.append((None, deflickeralign.identity_track(T), "static"))
+            else:
+                track_t, track = _track_segment(frames_rgb, dil_t, flicker_align, deflickeralign.TRACK_BYTES)
+                ftrack.append((track_t, track, deflickeralign.path_of(track)))
+        return ftrack[0]
 
     def model_px(o, idx, up, offsets=None, size=None, offs=None, mask=None):
         """Window frames o of the model on the device.  With flicker: as the window's h x w pixels (size; offsets [T,2] = the window's place per
@@ -539,8 +585,12 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
         h, w = size or (H0, W0)
         place = np.zeros((T, 2), np.int32) if offsets is None else np.ascontiguousarray(offsets[idx], np.int32)
         win = flicker_hip.window_pixels(up(o).contiguous(), h, w)
-        held, sums = flicker_hip.hold(win, torch.from_numpy(place).to(dev) if offs is None else offs, dil_t[idx].contiguous() if mask is None else mask,
-                                      flicker.radius, flicker.tol, fixed=bool((place == place[0]).all()))
+        offs = torch.from_numpy(place).to(dev) if offs is None else offs
+        mask = dil_t[idx].contiguous() if mask is None else mask
+        if flicker_align is not None and tracked()[2] == "tracked":
+            held, sums = flickalign_hip.hold(win, offs, tracked()[0], mask, flicker.radius, flicker.tol)
+        else:
+            held, sums = flicker_hip.hold(win, offs, mask, flicker.radius, flicker.tol, fixed=bool((place == place[0]).all()))
         fsums.append(sums.cpu().numpy())
         return held
 
@@ -678,4 +728,6 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
             flicker_out.append(DeflickerReport(*(np.stack(f) for f in zip(*(deflicker.fit(s) for s in fsums)))))
         else:                                                                             # this rank holds no frame of the clip: zero rows
             flicker_out.append(deflicker_report([], [], T, K=max(len(plans), 1)))
+    if flicker_align is not None and flicker_align_out is not None:                       # no model_px on this rank: nothing tracked
+        flicker_align_out.append(ftrack[0][1:] if ftrack else (deflickeralign.identity_track(T), "none"))
     return res
