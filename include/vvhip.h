@@ -485,7 +485,7 @@ int vv_blur_compose(const float* pix01, const uint8_t* orig, const uint8_t* mask
  * s2d > 1 (space-to-depth): out [(H/s2d)*(W/s2d)][cpad], channel (dy*s2d + dx)*3 + c = pixel (s2d*Y + dy, s2d*X + dx): a k x k stride-s2d convolution
  * becomes a stride-1 convolution over blocks (the patch embedding of the Hiera trunk: 7x7 stride 4 -> 2x2 over 48 channels) */
 int vv_u8_normalize(const uint8_t* src, int H, int W, const float* mean3, const float* istd3, void* out, int cpad, int s2d, int dtype, void* stream);
-/* LayerNorm over the last dim of fp32 [M][C] (any C), given eps, optional VV_ACT_* after the affine, out h16 or fp32 (LayerNorm2d of NCHW
+/* LayerNorm over the last dim of fp32 [M][C] (any C), given eps, optional VV_ACT_SILU / RELU / GELU / SIGMOID after the affine (VV_ACT_LRELU is refused: no slope), out h16 or fp32 (LayerNorm2d of NCHW
  * modules is this on NHWC rows) */
 int vv_layernorm_ex(const float* x, int64_t M, int C, const float* gamma, const float* beta, float eps, int act, void* out, int out_dtype,
                     int cpad /* output row length >= C (0 = C): columns past C are written as zeros */, int dtype, void* stream);
@@ -496,14 +496,15 @@ int vv_maxpool2x2(const void* x, int x_dtype, int B, int H, int W, int C, int64_
 int vv_rope_apply(void* x, int64_t rows_rope, int ld, int col0, int D, const float* cos_sin, int n_table, int dtype, void* stream);
 /* depthwise k x k convolution (zero padding k/2), fp32 [H][W][C], weights [C][k][k] */
 int vv_dwconv(const float* x, int H, int W, int C, const float* w, const float* bias, int k, float* out, void* stream);
-/* tail of ConvTranspose2d(kernel 2, stride 2): y [h*w][4*C] with columns (dy, dx, c) -> out [2h*2w][C] = act(y + bias (+ add)) */
+/* tail of ConvTranspose2d(kernel 2, stride 2): y [h*w][4*C] with columns (dy, dx, c) -> out [2h*2w][C] = act(y + bias (+ add)), act as for
+ * vv_layernorm_ex */
 int vv_pixel_shuffle2(const float* y, const float* bias, const float* add, int h, int w, int C, int act, void* out, int out_dtype, int dtype,
                       void* stream);
 /* bilinear resize of fp32 [Hs][Ws][C] with torch semantics (align_corners = False, no antialias) */
 int vv_resize_bilinear_f32(const float* src, int Hs, int Ws, int C, float* dst, int Hd, int Wd, void* stream);
 /* mask logits -> input of the memory encoder's mask downsampler: (binarize ? (x > 0) : sigmoid(x)) * scale + bias, h16 [n][8] (channel 0) */
 int vv_mask_mem_input(const float* logits, int64_t n, int binarize, float scale, float bias, void* out, int dtype, void* stream);
-/* in-place activation (VV_ACT_RELU / GELU / SIGMOID / SILU) on fp32 or h16 */
+/* in-place activation (VV_ACT_RELU / GELU / SIGMOID / SILU; VV_ACT_NONE leaves x as it is, VV_ACT_LRELU is refused) on fp32 or h16 */
 int vv_act(void* x, int x_dtype, int64_t n, int act, void* stream);
 /* prompt encoder: out[p] = label < 0 ? table[0] : pe((coords[p] + 0.5) * inv_size) + table[label + 1]; pe(c) = [sin | cos](2 pi (2c - 1) @ gauss);
  * table [5][D] = not_a_point_embed, point_embeddings 0..3 */

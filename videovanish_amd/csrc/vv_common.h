@@ -50,6 +50,11 @@ template <typename T> __device__ __forceinline__ void unpack8(uint4 u, float* v)
     v[6] = T::to_f32(u.w & 0xffff); v[7] = T::to_f32(u.w >> 16);
 }
 
+// An fp32 result that is converted to h16 next, as a value of its own.  Without it the compiler may fold the last fp32 operation into the conversion
+// (fp16: v_fma_mixlo_f16, ONE rounding instead of two), whatever `fp contract` says, and about 1 output in 20 000 is an fp16 ulp away from h16(fp32(...)), which is what
+// the bf16 form, the contract and the CPU oracle compute.  The kernels whose contract is "equal to the separately rounded fp32 operations" pass their last result through it.
+__device__ __forceinline__ float f32_value(float v) { asm volatile("" : "+v"(v)); return v; }
+
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
 // exact (erf) GELU, matching torch.nn.functional.gelu default.  erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, far below the h16 rounding
 // that follows: one v_rcp + one v_exp + 6 FMAs instead of ocml's two-branch erff) -- the form the fused kernels (vv_motion.hip, vv_chain.hip) have

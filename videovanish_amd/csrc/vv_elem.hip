@@ -45,7 +45,7 @@ __global__ void preprocess_kernel(const uint8_t* frames, const uint8_t* mask, in
         float v[8], w[8];
         const float keep = (mask && mask[i] > 0) ? 0.f : 1.f;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) { v[c] = (float)frames[i * 3 + c] / 127.5f - 1.0f; w[c] = v[c] * keep; }
+        for (int c = 0; c < 3; ++c) { v[c] = f32_value((float)frames[i * 3 + c] / 127.5f - 1.0f); w[c] = f32_value(v[c] * keep); }
 #pragma unroll
         for (int c = 3; c < 8; ++c) { v[c] = 0.f; w[c] = 0.f; }
         if (img) *(uint4*)(img + i * 8) = pack8<T>(v);
@@ -75,7 +75,7 @@ __global__ void pad_channels_kernel(const float* x, int64_t rows, int cin, int c
     const int64_t n = rows * cpad;
     for (int64_t i = blockIdx.x * (int64_t)EB + threadIdx.x; i < n; i += (int64_t)gridDim.x * EB) {
         const int c = (int)(i % cpad); const int64_t r = i / cpad;
-        out[i] = T::from_f32(c < cin ? x[r * cin + c] * scale : 0.f);
+        out[i] = T::from_f32(c < cin ? f32_value(x[r * cin + c] * scale) : 0.f);
     }
 }
 
@@ -193,7 +193,7 @@ __global__ void split_f32_kernel(const float* x, int64_t n4, float lo_scale, uns
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             h[c] = T::from_f32(a[c]);
-            l[c] = T::from_f32((a[c] - T::to_f32(h[c])) * lo_scale);
+            l[c] = T::from_f32(f32_value((a[c] - T::to_f32(h[c])) * lo_scale));
         }
         ((uint2*)hi)[i] = make_uint2(h[0] | ((unsigned)h[1] << 16), h[2] | ((unsigned)h[3] << 16));
         ((uint2*)lo)[i] = make_uint2(l[0] | ((unsigned)l[1] << 16), l[2] | ((unsigned)l[3] << 16));
@@ -227,8 +227,8 @@ __global__ void split3_kernel(const IN* x, int64_t rows, int C, unsigned short* 
         for (int e = 0; e < 4; ++e) {
             h[e] = T::from_f32(a[e]);
             const float hf = T::to_f32(h[e]);
-            l[e] = T::from_f32((a[e] - hf) * 16.0f);
-            g[e] = T::from_f32(hf * 0.0009765625f);
+            l[e] = T::from_f32(f32_value((a[e] - hf) * 16.0f));
+            g[e] = T::from_f32(f32_value(hf * 0.0009765625f));
         }
         unsigned short* o = out + row * 3 * C + c;
         *(uint2*)o = make_uint2(h[0] | ((unsigned)h[1] << 16), h[2] | ((unsigned)h[3] << 16));

@@ -82,7 +82,7 @@ template <typename T>
 __global__ void flow_prep_kernel(const float* coords1, int64_t M, int w, int h, unsigned short* flow8, unsigned short* xbuf) {
     GRID_STRIDE(m, M) {
         const float fx = coords1[m * 2] - (float)(m % w), fy = coords1[m * 2 + 1] - (float)((m / w) % h);      // rows of stacked h x w grids
-        const unsigned pk = pack2<T>(fx, fy);
+        const unsigned pk = pack2<T>(f32_value(fx), f32_value(fy));
         *(uint4*)(flow8 + m * 8) = make_uint4(pk, 0, 0, 0);
         *(unsigned*)(xbuf + m * 256 + 254) = pk;
     }
@@ -231,7 +231,7 @@ __global__ void raft_prep_kernel(const uint8_t* img, int64_t npix, unsigned shor
     GRID_STRIDE(i, npix) {
         float v[8];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = 2.0f * ((float)img[i * 3 + c] / 255.0f) - 1.0f;
+        for (int c = 0; c < 3; ++c) v[c] = f32_value(2.0f * ((float)img[i * 3 + c] / 255.0f) - 1.0f);
 #pragma unroll
         for (int c = 3; c < 8; ++c) v[c] = 0.f;
         *(uint4*)(out + i * 8) = pack8<T>(v);

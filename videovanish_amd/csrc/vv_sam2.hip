@@ -450,6 +450,8 @@ __global__ __launch_bounds__(256) void conv3s2_ln_gelu_kernel(const unsigned sho
 }
 
 inline dim3 grid1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
+// the activations act_f knows: VV_ACT_LRELU needs a slope these entry points do not take
+inline bool act_ok(int act) { return act == VV_ACT_NONE || act == VV_ACT_SILU || act == VV_ACT_RELU || act == VV_ACT_GELU || act == VV_ACT_SIGMOID; }
 
 }  // namespace
 
@@ -470,6 +472,7 @@ extern "C" int vv_layernorm_ex(const float* x, int64_t M, int C, const float* ga
                                int cpad, int dtype, void* stream) {
     if (cpad <= 0) cpad = C;
     if (!x || !gamma || !beta || !out || M <= 0 || C <= 0 || cpad < C) VV_FAIL(VV_E_ARG, "vv_layernorm_ex: bad arguments");
+    if (!act_ok(act)) VV_FAIL(VV_E_ARG, "vv_layernorm_ex: act must be VV_ACT_NONE / SILU / RELU / GELU / SIGMOID");
     const int of32 = out_dtype == VV_F32;
     if (!of32 && out_dtype != dtype) VV_FAIL(VV_E_ARG, "vv_layernorm_ex: out_dtype must be VV_F32 or the h16 dtype");
     hipStream_t st = (hipStream_t)stream;
@@ -522,7 +525,7 @@ extern "C" int vv_dwconv(const float* x, int H, int W, int C, const float* w, co
 
 extern "C" int vv_pixel_shuffle2(const float* y, const float* bias, const float* add, int h, int w, int C, int act, void* out, int out_dtype, int dtype,
                                  void* stream) {
-    if (!y || !bias || !out || h <= 0 || w <= 0 || C <= 0) VV_FAIL(VV_E_ARG, "vv_pixel_shuffle2: bad arguments");
+    if (!y || !bias || !out || h <= 0 || w <= 0 || C <= 0 || !act_ok(act)) VV_FAIL(VV_E_ARG, "vv_pixel_shuffle2: bad arguments (act: VV_ACT_NONE / SILU / RELU / GELU / SIGMOID)");
     const int of32 = out_dtype == VV_F32;
     if (!of32 && out_dtype != dtype) VV_FAIL(VV_E_ARG, "vv_pixel_shuffle2: out_dtype must be VV_F32 or the h16 dtype");
     hipStream_t st = (hipStream_t)stream;
@@ -564,7 +567,7 @@ __global__ __launch_bounds__(256) void act_vec8_kernel(uint4* __restrict__ x, in
 }  // namespace
 
 extern "C" int vv_act(void* x, int x_dtype, int64_t n, int act, void* stream) {
-    if (!x || n <= 0) VV_FAIL(VV_E_ARG, "vv_act: bad arguments");
+    if (!x || n <= 0 || !act_ok(act)) VV_FAIL(VV_E_ARG, "vv_act: bad arguments (act: VV_ACT_NONE / SILU / RELU / GELU / SIGMOID)");
     hipStream_t st = (hipStream_t)stream;
     if (x_dtype != VV_F32 && n % 8 == 0 && ((uintptr_t)x & 15) == 0) {       // h16, 16 bytes per thread
         if (x_dtype == VV_BF16) hipLaunchKernelGGL(act_vec8_kernel<BF16>, grid1(n / 8), dim3(256), 0, st, (uint4*)x, n / 8, act);

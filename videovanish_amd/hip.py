@@ -460,10 +460,10 @@ def motion_module_c320(dtype, x, stream_w, params, gamma, beta, groups, eps, *, 
     return out
 
 
-def layernorm(dtype, x, gamma, beta, pe=None, rows_per_frame=1):
+def layernorm(dtype, x, gamma, beta, pe=None, rows_per_frame=1, out=None):
     _need_cuda(x, gamma, beta, pe)
     M, Cc = x.shape
-    out = torch.empty((M, Cc), dtype=h16(dtype), device=x.device)
+    out = _own_out(out, (M, Cc), h16(dtype), x, "layernorm")
     with _Prof("layernorm", 0.0, M * Cc * 6):
         _check(lib().vv_layernorm(_p(x), M, Cc, _p(gamma), _p(beta), _p(pe), rows_per_frame, _p(out), dtype, _stream()), "vv_layernorm")
     return out
@@ -532,14 +532,14 @@ def attention_route(dtype, q, k, v, out, **kw):
 
 
 def deform_im2col(dtype, x, *, B, H, W, kh=3, kw=3, stride=1, pad=1, dil=1, deform_groups=1, offset=None, mask=None, raw=None, flow=None,
-                  max_residue=0.0):
+                  max_residue=0.0, out=None):
     """Deformed, modulated im2col matrix [M, kh*kw*C] (h16) of an NHWC tensor x [B*H*W, C]: see vv_deform_im2col in include/vvhip.h.
     Either (offset [M, 2*dg*K], mask [M, dg*K] | None) or raw [M, 3*dg*K] (+ flow [M, 2]) -- the DeformableAlignment front end."""
     _need_cuda(x, offset, mask, raw, flow)
     Cc = x.shape[-1]
     Ho = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1
     Wo = (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
-    col = torch.empty((B * Ho * Wo, kh * kw * Cc), dtype=h16(dtype), device=x.device)
+    col = _own_out(out, (B * Ho * Wo, kh * kw * Cc), h16(dtype), x, "deform_im2col")
     for t in (offset, mask, raw, flow):
         if t is not None and t.dtype != torch.float32:
             raise RuntimeError("vv_deform_im2col: offset / mask / raw / flow must be fp32")
@@ -632,9 +632,9 @@ def sched_step(x, eps, z, sa_t, sb_t, c_x0, c_eps, c_z=0.0, out=None):
     return out
 
 
-def silu(x):
+def silu(x, out=None):
     _need_cuda(x)
-    out = torch.empty_like(x)
+    out = _own_out(out, x.shape, x.dtype, x, "silu")
     _check(lib().vv_silu_f32(_p(x), _p(out), x.numel(), _stream()), "vv_silu_f32")
     return out
 
@@ -743,56 +743,56 @@ def chamfer_dt(bin_u8, R):
     return out
 
 
-def preprocess(dtype, frames, mask2d, want_img=True, want_masked=True):
+def preprocess(dtype, frames, mask2d, want_img=True, want_masked=True, img=None, masked=None):
     _need_cuda(frames, mask2d)
     T, H, W, _ = frames.shape
-    img = torch.empty((T, H, W, 8), dtype=h16(dtype), device=frames.device) if want_img else None
-    msk = torch.empty((T, H, W, 8), dtype=h16(dtype), device=frames.device) if want_masked else None
+    img = _own_out(img, (T, H, W, 8), h16(dtype), frames, "preprocess (img)") if want_img else None
+    msk = _own_out(masked, (T, H, W, 8), h16(dtype), frames, "preprocess (masked)") if want_masked else None
     _check(lib().vv_preprocess(_p(frames), _p(mask2d), T, H, W, _p(img), _p(msk), dtype, _stream()), "vv_preprocess")
     return img, msk
 
 
-def brushnet_input(dtype, lat, cond, mask2d, H, W):
+def brushnet_input(dtype, lat, cond, mask2d, H, W, out=None):
     _need_cuda(lat, cond, mask2d)
     F, h, w, _ = lat.shape
-    out = torch.empty((F, h, w, 16), dtype=h16(dtype), device=lat.device)
+    out = _own_out(out, (F, h, w, 16), h16(dtype), lat, "brushnet_input")
     _check(lib().vv_brushnet_input(_p(lat), _p(cond), _p(mask2d), F, h, w, H, W, _p(out), dtype, _stream()), "vv_brushnet_input")
     return out
 
 
-def pad_channels(dtype, x, cpad, scale=1.0):
+def pad_channels(dtype, x, cpad, scale=1.0, out=None):
     _need_cuda(x)
     cin = x.shape[-1]
     rows = x.numel() // cin
-    out = torch.empty(x.shape[:-1] + (cpad,), dtype=h16(dtype), device=x.device)
+    out = _own_out(out, x.shape[:-1] + (cpad,), h16(dtype), x, "pad_channels")
     _check(lib().vv_pad_channels(_p(x), rows, cin, cpad, scale, _p(out), dtype, _stream()), "vv_pad_channels")
     return out
 
 
-def window_average(value, count):
+def window_average(value, count, out=None):
     """value fp32 [T, ...], count fp32 [T] -> value / count per frame."""
     _need_cuda(value, count)
     T = value.shape[0]
-    out = torch.empty_like(value)
+    out = _own_out(out, value.shape, value.dtype, value, "window_average")
     _check(lib().vv_window_average(_p(value), _p(count), T, value.numel() // T, _p(out), _stream()), "vv_window_average")
     return out
 
 
-def pad_channels_f32(x, cpad, scale=1.0):
+def pad_channels_f32(x, cpad, scale=1.0, out=None):
     _need_cuda(x)
     cin = x.shape[-1]
     rows = x.numel() // cin
-    out = torch.empty(x.shape[:-1] + (cpad,), dtype=torch.float32, device=x.device)
+    out = _own_out(out, x.shape[:-1] + (cpad,), torch.float32, x, "pad_channels_f32")
     _check(lib().vv_pad_channels_f32(_p(x), rows, cin, cpad, scale, _p(out), _stream()), "vv_pad_channels_f32")
     return out
 
 
-def split_f32(dtype, x, lo_scale):
+def split_f32(dtype, x, lo_scale, hi=None, lo=None):
     """fp32 tensor -> (hi, lo) h16 tensors of the same shape: hi = h16(x), lo = h16((x - hi) * lo_scale)."""
     _need_cuda(x)
     assert x.dtype == torch.float32
-    hi = torch.empty(x.shape, dtype=h16(dtype), device=x.device)
-    lo = torch.empty(x.shape, dtype=h16(dtype), device=x.device)
+    hi = _own_out(hi, x.shape, h16(dtype), x, "split_f32 (hi)")
+    lo = _own_out(lo, x.shape, h16(dtype), x, "split_f32 (lo)")
     _check(lib().vv_split_f32(_p(x), x.numel(), lo_scale, _p(hi), _p(lo), dtype, _stream()), "vv_split_f32")
     return hi, lo
 
@@ -848,12 +848,12 @@ def spatial_chain_front_c320(dtype, x, gamma, beta, groups, eps, stream_w, param
     return t, qkv
 
 
-def split3(dtype, x):
+def split3(dtype, x, out=None):
     """[M, C] fp32 (or h16) -> [M, 3C] h16 = [hi | (x - hi) * 2^4 | hi * 2^-10]: the A operand of a K-concatenated split-precision GEMM (vv_split3)."""
     _need_cuda(x)
     assert x.dim() == 2 and x.is_contiguous()
     M, Cc = x.shape
-    out = torch.empty((M, 3 * Cc), dtype=h16(dtype), device=x.device)
+    out = _own_out(out, (M, 3 * Cc), h16(dtype), x, "split3")
     with _Prof("split3", 0.0, x.numel() * (x.element_size() + 6)):
         _check(lib().vv_split3(_p(x), dt_of(x), M, Cc, _p(out), dtype, _stream()), "vv_split3")
     return out
@@ -878,21 +878,21 @@ def blur_compose(pix01, orig, mask2d, taps21):
 
 
 # ---- K9/K10: RAFT / flow-guided propagation kernels ----------------------------------------------------------------
-def avgpool2(x):
+def avgpool2(x, out=None):
     """[N,h,w] fp32 -> [N,h//2,w//2]."""
     _need_cuda(x)
     N, h, w = x.shape
-    out = torch.empty((N, h // 2, w // 2), dtype=torch.float32, device=x.device)
+    out = _own_out(out, (N, h // 2, w // 2), torch.float32, x, "avgpool2")
     with _Prof("avgpool2[corr pyramid]", 0.0, x.numel() * 5):
         _check(lib().vv_avgpool2_f32(_p(x), N, h, w, _p(out), _stream()), "vv_avgpool2_f32")
     return out
 
 
-def corr_lookup(dtype, pyr, coords, cpad=384):
+def corr_lookup(dtype, pyr, coords, cpad=384, out=None):
     """pyr: 4 fp32 tensors [N,h_l,w_l]; coords [N,2] fp32 (x,y) -> h16 [N,cpad] (324 real channels)."""
     _need_cuda(*pyr, coords)
     N, h, w = pyr[0].shape
-    out = torch.empty((N, cpad), dtype=h16(dtype), device=coords.device)
+    out = _own_out(out, (N, cpad), h16(dtype), coords, "corr_lookup")
     with _Prof("corr_lookup", 0.0, N * (4 * 100 * 4 + 324 * 2 + 8)):
         _check(lib().vv_corr_lookup(_p(pyr[0]), _p(pyr[1]), _p(pyr[2]), _p(pyr[3]), h, w, _p(coords), N, cpad, _p(out), dtype, _stream()),
                "vv_corr_lookup")
@@ -929,27 +929,27 @@ def add_flow(coords1, dflow):
         _check(lib().vv_add_flow(_p(coords1), _p(dflow), dflow.shape[-1], coords1.shape[0], _stream()), "vv_add_flow")
 
 
-def add_relu(a, b):
+def add_relu(a, b, out=None):
     _need_cuda(a, b)
-    out = torch.empty_like(a)
+    out = _own_out(out, a.shape, a.dtype, a, "add_relu")
     with _Prof("add_relu", 0.0, a.numel() * 12):
         _check(lib().vv_add_relu_f32(_p(a), _p(b), _p(out), a.numel(), _stream()), "vv_add_relu_f32")
     return out
 
 
-def convex_upsample(coords1, mask, h, w, F=1):
+def convex_upsample(coords1, mask, h, w, F=1, out=None):
     """coords1 [F*h*w, 2], mask [F*h*w, 576] -> flow [8h, 8w, 2] (F = 1) or [F, 8h, 8w, 2]."""
     _need_cuda(coords1, mask)
-    out = torch.empty((F, 8 * h, 8 * w, 2), dtype=torch.float32, device=coords1.device)
+    out = _own_out(out, (F, 8 * h, 8 * w, 2), torch.float32, coords1, "convex_upsample")
     with _Prof("convex_upsample", 0.0, mask.numel() * mask.element_size() + coords1.numel() * 4 + out.numel() * 4):
         _check(lib().vv_convex_upsample(_p(coords1), _p(mask), F, h, w, _p(out), _stream()), "vv_convex_upsample")
     return out[0] if F == 1 else out
 
 
-def fb_valid(f_ab, f_ba):
+def fb_valid(f_ab, f_ba, out=None):
     _need_cuda(f_ab, f_ba)
     H, W, _ = f_ab.shape
-    out = torch.empty((H, W), dtype=torch.uint8, device=f_ab.device)
+    out = _own_out(out, (H, W), torch.uint8, f_ab, "fb_valid")
     with _Prof("fb_valid[bilinear warp of the backward flow]", 0.0, H * W * (8 + 8 + 1)):
         _check(lib().vv_fb_valid(_p(f_ab), _p(f_ba), H, W, _p(out), _stream()), "vv_fb_valid")
     return out
@@ -962,66 +962,67 @@ def prop_fill(cur_t, cur_nb, known_t, known_nb, valid, flow, filled_t):
         _check(lib().vv_prop_fill(_p(cur_t), _p(cur_nb), _p(known_t), _p(known_nb), _p(valid), _p(flow), H, W, _p(filled_t), _stream()), "vv_prop_fill")
 
 
-def prop_combine(orig, a, b, fa, fb, hole, mean3):
+def prop_combine(orig, a, b, fa, fb, hole, mean3, out=None, filled=None, want_filled=True):
+    """-> (out u8 [H,W,3], filled u8 [H,W]); want_filled=False: the library gets no `filled` map (None is returned in its place)"""
     _need_cuda(orig, a, b, fa, fb, hole, mean3)
     H, W, _ = orig.shape
-    out = torch.empty((H, W, 3), dtype=torch.uint8, device=orig.device)
-    filled = torch.empty((H, W), dtype=torch.uint8, device=orig.device)
+    out = _own_out(out, (H, W, 3), torch.uint8, orig, "prop_combine (out)")
+    filled = _own_out(filled, (H, W), torch.uint8, orig, "prop_combine (filled)") if want_filled else None
     with _Prof("prop_combine", 0.0, H * W * (3 * 3 + 3 + 3 + 1)):
         _check(lib().vv_prop_combine(_p(orig), _p(a), _p(b), _p(fa), _p(fb), _p(hole), H, W, _p(mean3), _p(out), _p(filled), _stream()), "vv_prop_combine")
     return out, filled
 
 
-def masked_sum_u8(frame, hole):
+def masked_sum_u8(frame, hole, out=None):
     """-> int64 tensor [4] (sum r, g, b over non-hole pixels, count) on the device."""
     _need_cuda(frame, hole)
-    sums = torch.empty(4, dtype=torch.int64, device=frame.device)
+    sums = _own_out(out, (4,), torch.int64, frame, "masked_sum_u8")
     _check(lib().vv_masked_sum_u8(_p(frame), _p(hole), hole.numel(), _p(sums), _stream()), "vv_masked_sum_u8")
     return sums
 
 
-def u8_to_f32(x):
+def u8_to_f32(x, out=None):
     _need_cuda(x)
-    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    out = _own_out(out, x.shape, torch.float32, x, "u8_to_f32")
     _check(lib().vv_u8_to_f32(_p(x), _p(out), x.numel(), _stream()), "vv_u8_to_f32")
     return out
 
 
-def u8_is_zero(x):
+def u8_is_zero(x, out=None):
     _need_cuda(x)
-    out = torch.empty_like(x)
+    out = _own_out(out, x.shape, x.dtype, x, "u8_is_zero")
     _check(lib().vv_u8_is_zero(_p(x), _p(out), x.numel(), _stream()), "vv_u8_is_zero")
     return out
 
 
-def raft_prep(dtype, img):
+def raft_prep(dtype, img, out=None):
     """u8 [..., 3] -> h16 [..., 8] scaled to [-1,1]."""
     _need_cuda(img)
-    out = torch.empty(img.shape[:-1] + (8,), dtype=h16(dtype), device=img.device)
+    out = _own_out(out, img.shape[:-1] + (8,), h16(dtype), img, "raft_prep")
     with _Prof("raft_prep", 0.0, img.numel() + out.numel() * 2):
         _check(lib().vv_raft_prep(_p(img), img.numel() // 3, _p(out), dtype, _stream()), "vv_raft_prep")
     return out
 
 
 # ---- SAM 2 (SURVEY row n4; include/vvhip.h "SAM 2" section) ---------------------------------------------------------------------
-def u8_normalize(dtype, img_u8, mean, std, cpad=8, s2d=1):
+def u8_normalize(dtype, img_u8, mean, std, cpad=8, s2d=1, out=None):
     """uint8 [H, W, 3] -> h16 [(H/s2d)*(W/s2d), cpad] = ((x / 255) - mean) / std; s2d > 1: space-to-depth blocks, channel (dy*s2d + dx)*3 + c."""
     _need_cuda(img_u8)
     H, W = img_u8.shape[:2]
-    out = torch.empty(((H // s2d) * (W // s2d), cpad), dtype=h16(dtype), device=img_u8.device)
+    out = _own_out(out, ((H // s2d) * (W // s2d), cpad), h16(dtype), img_u8, "u8_normalize")
     m = (C.c_float * 3)(*[float(v) for v in mean])
     s = (C.c_float * 3)(*[1.0 / float(v) for v in std])
     _check(lib().vv_u8_normalize(_p(img_u8), H, W, m, s, _p(out), cpad, s2d, dtype, _stream()), "vv_u8_normalize")
     return out
 
 
-def layernorm_ex(dtype, x, gamma, beta, eps, act=ACT_NONE, out_dtype=None, cpad=None):
+def layernorm_ex(dtype, x, gamma, beta, eps, act=ACT_NONE, out_dtype=None, cpad=None, out=None):
     """LayerNorm over the last dim of fp32 [M, C] (any C) + optional activation; out_dtype None = h16, torch.float32 = fp32;
     cpad: output row length (zero padded channels, for a following conv whose input channels are padded)."""
     _need_cuda(x, gamma, beta)
     M, Cc = x.shape
     cp = Cc if cpad is None else cpad
-    out = torch.empty((M, cp), dtype=h16(dtype) if out_dtype is None else out_dtype, device=x.device)
+    out = _own_out(out, (M, cp), h16(dtype) if out_dtype is None else out_dtype, x, "layernorm_ex")
     _check(lib().vv_layernorm_ex(_p(x), M, Cc, _p(gamma), _p(beta), eps, act, _p(out), dt_of(out), cp, dtype, _stream()), "vv_layernorm_ex")
     return out
 
@@ -1068,10 +1069,10 @@ def resize_bilinear_f32(src, Hs, Ws, Hd, Wd):
     return out
 
 
-def mask_mem_input(dtype, logits, binarize, scale, bias):
+def mask_mem_input(dtype, logits, binarize, scale, bias, out=None):
     _need_cuda(logits)
     n = logits.numel()
-    out = torch.empty((n, 8), dtype=h16(dtype), device=logits.device)
+    out = _own_out(out, (n, 8), h16(dtype), logits, "mask_mem_input")
     _check(lib().vv_mask_mem_input(_p(logits), n, int(bool(binarize)), scale, bias, _p(out), dtype, _stream()), "vv_mask_mem_input")
     return out
 
@@ -1097,9 +1098,9 @@ def sine_pe_1d(pos, dim, temperature=10000.0):
     return out
 
 
-def sam_select(masks, iou, obj_logit, multimask, delta, thresh):
+def sam_select(masks, iou, obj_logit, multimask, delta, thresh, out=None):
     _need_cuda(masks, iou, obj_logit)
-    sel = torch.empty(4, dtype=torch.int32, device=masks.device)
+    sel = _own_out(out, (4,), torch.int32, masks, "sam_select")
     _check(lib().vv_sam_select(_p(masks), masks.shape[-1], masks.shape[0], _p(iou), _p(obj_logit), int(bool(multimask)), delta, thresh, _p(sel),
                                _stream()), "vv_sam_select")
     return sel
@@ -1112,9 +1113,9 @@ def sam_pick(masks, sel, no_obj_score):
     return out
 
 
-def select_f32(a, b, flag):
+def select_f32(a, b, flag, out=None):
     _need_cuda(a, b, flag)
-    out = torch.empty_like(a)
+    out = _own_out(out, a.shape, a.dtype, a, "select_f32")
     _check(lib().vv_select_f32(_p(a), _p(b), _p(flag), a.numel(), _p(out), _stream()), "vv_select_f32")
     return out
 
@@ -1126,9 +1127,9 @@ def add_rowvec_unless(x, vec, score):
     return x
 
 
-def clamp_f32(x, lo, hi):
+def clamp_f32(x, lo, hi, out=None):
     _need_cuda(x)
-    out = torch.empty_like(x)
+    out = _own_out(out, x.shape, x.dtype, x, "clamp_f32")
     _check(lib().vv_clamp_f32(_p(x), x.numel(), lo, hi, _p(out), _stream()), "vv_clamp_f32")
     return out
 
@@ -1173,11 +1174,11 @@ def ycbcr_to_rgb(y, cb, cr, hshift, vshift, full_range=False):
     return out
 
 
-def sam2_maskdown(dtype, logits, lo, S, binarize, scale, bias, l1, l2, eps=1e-6):
+def sam2_maskdown(dtype, logits, lo, S, binarize, scale, bias, l1, l2, eps=1e-6, mid=None, out=None):
     """fused front of the SAM 2 memory encoder's mask path (vv_sam2_maskdown): logits fp32 [lo*lo] -> h16 [(S/4)^2, 16].  l1 / l2: (w, b, gamma, beta)."""
     _need_cuda(logits, *l1, *l2)
-    mid = torch.empty(((S // 2) ** 2, 8), dtype=h16(dtype), device=logits.device)
-    out = torch.empty(((S // 4) ** 2, 16), dtype=h16(dtype), device=logits.device)
+    mid = _own_out(mid, ((S // 2) ** 2, 8), h16(dtype), logits, "sam2_maskdown (mid)")      # the first stage's output, a workspace to the caller
+    out = _own_out(out, ((S // 4) ** 2, 16), h16(dtype), logits, "sam2_maskdown (out)")
     _check(lib().vv_sam2_maskdown(_p(logits), lo, S, int(bool(binarize)), scale, bias, _p(l1[0]), _p(l1[1]), _p(l1[2]), _p(l1[3]), _p(l2[0]), _p(l2[1]),
                                   _p(l2[2]), _p(l2[3]), eps, _p(mid), _p(out), dtype, _stream()), "vv_sam2_maskdown")
     return out
