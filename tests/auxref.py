@@ -24,6 +24,7 @@ SENTINEL = 1000.0          # exact in fp32, fp16 and bf16
 SENTINEL_INT = 0xA5        # guard value of the integer buffers
 ELEM_CAP = 8192 * 256      # threads of the largest grid of vv_elem.hip: an index past it is reached in a second pass of the grid-stride loop
 FLOW_CAP = 16384 * 256     # the same for vv_flow.hip
+IMAGE_CAP = 16384 * 256    # the same for vv_image.hip (grid_for)
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_GELU, ACT_SIGMOID = 0, 1, 2, 4, 5
 GELU_ERF_ERR = 1.5e-7      # |error| of the erf approximation in gelu_f (vv_common.h)
 
@@ -51,9 +52,9 @@ def gen(seed):
     return torch.Generator().manual_seed(seed)
 
 
-def bound(key, out_dtype, ref, gelu_x=None):
-    """B for a rounded kernel; key: entry of NOISE; gelu_x: max |x| that went through gelu_f into an fp32 output"""
-    k = math.ceil(4 * max(1.0, NOISE[key]))
+def bound(key, out_dtype, ref, gelu_x=None, table=None):
+    """B for a rounded kernel; key: entry of NOISE (or of `table`, the NOISE of a sibling file); gelu_x: max |x| that went through gelu_f into an fp32 output"""
+    k = math.ceil(4 * max(1.0, (NOISE if table is None else table)[key]))
     b = k * U[out_dtype] * max(1.0, ref.abs().max().item())
     if gelu_x is not None and out_dtype == torch.float32:
         b += 0.5 * gelu_x * GELU_ERF_ERR

@@ -41,29 +41,29 @@ class Guarded:
         return bool((self.buf[:GUARD] == self.sent).all()) and bool((self.buf[GUARD + self.n:] == self.sent).all())
 
 
-def _exact(name, label, got, ref, *guards):
-    """got (on the GPU) must equal ref (CPU) bit for bit; compared where the data is"""
+def _exact(name, label, got, ref, *guards, tag="aux"):
+    """got (on the GPU) must equal ref (CPU) bit for bit; compared where the data is; tag: the first word of the logged line"""
     assert got.dtype == ref.dtype and got.shape == ref.shape, (got.dtype, ref.dtype, got.shape, ref.shape)
     r = ref.to(got.device)
     bad = int((got != r).sum().item())
     fin = bool(torch.isfinite(got).all()) if got.dtype.is_floating_point else True
     ok = all(g.intact() for g in guards)
-    _log(f"aux {name} {label}: " + ("exact" if bad == 0 else f"{bad} of {got.numel()} elements differ") + ("" if ok else ", GUARDS TOUCHED") + ("" if fin else ", NOT FINITE"))
+    _log(f"{tag} {name} {label}: " + ("exact" if bad == 0 else f"{bad} of {got.numel()} elements differ") + ("" if ok else ", GUARDS TOUCHED") + ("" if fin else ", NOT FINITE"))
     assert bad == 0 and fin and ok
 
 
-def _close(name, key, label, got, ref, out_dtype, *guards, gelu_x=None, keep=None):
-    """rounded kernel: got (GPU) against the fp64 ref (CPU), B from auxref.NOISE[key]; keep: the elements compared (threshold elements are left out)"""
+def _close(name, key, label, got, ref, out_dtype, *guards, gelu_x=None, keep=None, table=None, tag="aux"):
+    """rounded kernel: got (GPU) against the fp64 ref (CPU), B from auxref.NOISE[key] (or table[key]); keep: the elements compared (threshold elements are left out)"""
     g = got.detach().cpu().double()
     assert g.shape == ref.shape, (g.shape, ref.shape)
     fin = bool(torch.isfinite(g).all())
-    B = R.bound(key, out_dtype, ref, gelu_x)
+    B = R.bound(key, out_dtype, ref, gelu_x, table)
     d = (g - ref).abs()
     if keep is not None:
         d = d[keep]
     err = d.max().item()
     ok = all(x.intact() for x in guards)
-    _log(f"aux {name} {label}: max |got - ref| {err:.3e} = {err / B:.3f} B (B = {B:.3e}, max |ref| {ref.abs().max().item():.2f})" + ("" if ok else ", GUARDS TOUCHED")
+    _log(f"{tag} {name} {label}: max |got - ref| {err:.3e} = {err / B:.3f} B (B = {B:.3e}, max |ref| {ref.abs().max().item():.2f})" + ("" if ok else ", GUARDS TOUCHED")
          + ("" if fin else ", NOT FINITE"))
     assert fin and ok and err <= B
     return err / B

@@ -550,63 +550,63 @@ def deform_im2col(dtype, x, *, B, H, W, kh=3, kw=3, stride=1, pad=1, dil=1, defo
     return col, Ho, Wo
 
 
-def fc_input(flow, mask_u8, pad):
+def fc_input(flow, mask_u8, pad, out=None):
     """flow fp32 [T,H,W,2] + mask u8 [T,H,W] -> fp32 [T, H+2pad, W+2pad, 8] = (flow*(1-m) | m | 0..) replicate-padded."""
     _need_cuda(flow, mask_u8)
     T, H, W, _ = flow.shape
-    out = torch.empty((T, H + 2 * pad, W + 2 * pad, 8), dtype=torch.float32, device=flow.device)
+    out = _own_out(out, (T, H + 2 * pad, W + 2 * pad, 8), torch.float32, flow, "fc_input")
     _check(lib().vv_fc_input(_p(flow), _p(mask_u8), T, H, W, pad, _p(out), _stream()), "vv_fc_input")
     return out
 
 
-def upsample2x_bilinear(dtype, x, B, H, W):
+def upsample2x_bilinear(dtype, x, B, H, W, out=None):
     """NHWC rows [B*H*W, C] (h16 or fp32) -> [B*2H*2W, C], bilinear, align_corners=True."""
     _need_cuda(x)
     Cc = x.shape[-1]
-    out = torch.empty((B * 4 * H * W, Cc), dtype=x.dtype, device=x.device)
+    out = _own_out(out, (B * 4 * H * W, Cc), x.dtype, x, "upsample2x_bilinear")
     _check(lib().vv_upsample2x_bilinear(_p(x), dt_of(x), B, H, W, Cc, _p(out), dtype, _stream()), "vv_upsample2x_bilinear")
     return out
 
 
-def flow_combine(pred, flow, mask_u8):
+def flow_combine(pred, flow, mask_u8, out=None):
     """pred fp32 [N, ld>=2], flow fp32 [..., 2] with N pixels, mask u8 [N] -> fp32 like flow: pred in the hole, flow outside."""
     _need_cuda(pred, flow, mask_u8)
-    out = torch.empty_like(flow)
+    out = _own_out(out, flow.shape, torch.float32, flow, "flow_combine")
     _check(lib().vv_flow_combine(_p(pred), pred.shape[-1], _p(flow), _p(mask_u8), mask_u8.numel(), _p(out), _stream()), "vv_flow_combine")
     return out
 
 
-def gather_rows(src, idx):
+def gather_rows(src, idx, out=None):
     """out[i] = src[idx[i]] (idx int32 on the device, < 0 -> zero row); rows must be multiples of 16 bytes."""
     _need_cuda(src, idx)
-    out = torch.empty((idx.numel(), src.shape[-1]), dtype=src.dtype, device=src.device)
+    out = _own_out(out, (idx.numel(), src.shape[-1]), src.dtype, src, "gather_rows")
     _check(lib().vv_gather_rows(_p(src), _p(idx), idx.numel(), src.shape[-1] * src.element_size(), _p(out), _stream()), "vv_gather_rows")
     return out
 
 
-def fold_patches(dtype, x, B, fh, fw, Cc, h, w, k=7, stride=3, pad=3, normalise=False, gelu=False, out_dtype=torch.float32):
+def fold_patches(dtype, x, B, fh, fw, Cc, h, w, k=7, stride=3, pad=3, normalise=False, gelu=False, out_dtype=torch.float32, out=None):
     """tap-major patch rows [B*fh*fw, k*k*C] -> [B*h*w, C] (F.fold; optional overlap normalisation and GELU)."""
     _need_cuda(x)
-    out = torch.empty((B * h * w, Cc), dtype=out_dtype, device=x.device)
+    out = _own_out(out, (B * h * w, Cc), out_dtype, x, "fold_patches")
     _check(lib().vv_fold_patches(_p(x), dt_of(x), B, fh, fw, Cc, h, w, k, stride, pad, int(normalise), int(gelu), _p(out), dt_of(out), dtype, _stream()),
            "vv_fold_patches")
     return out
 
 
-def flow_down4(flow):
+def flow_down4(flow, out=None):
     """fp32 [T,H,W,2] -> fp32 [T,H/4,W/4,2] (bilinear 1/4, align_corners=False, values / 4)."""
     _need_cuda(flow)
     T, H, W, _ = flow.shape
-    out = torch.empty((T, H // 4, W // 4, 2), dtype=torch.float32, device=flow.device)
+    out = _own_out(out, (T, H // 4, W // 4, 2), torch.float32, flow, "flow_down4")
     _check(lib().vv_flow_down4(_p(flow), T, H, W, _p(out), _stream()), "vv_flow_down4")
     return out
 
 
-def gen_input(frames_u8, mask_in_u8, mask_up_u8):
+def gen_input(frames_u8, mask_in_u8, mask_up_u8, out=None):
     """u8 [T,H,W,3] + two u8 [T,H,W] masks -> fp32 [T*H*W, 8] encoder input rows."""
     _need_cuda(frames_u8, mask_in_u8, mask_up_u8)
     n = mask_in_u8.numel()
-    out = torch.empty((n, 8), dtype=torch.float32, device=frames_u8.device)
+    out = _own_out(out, (n, 8), torch.float32, frames_u8, "gen_input")
     _check(lib().vv_gen_input(_p(frames_u8), _p(mask_in_u8), _p(mask_up_u8), n, _p(out), _stream()), "vv_gen_input")
     return out
 
@@ -646,13 +646,13 @@ def add_inplace(dtype, x, y):
     return x
 
 
-def mask_collapse_dilate(masks, iters):
+def mask_collapse_dilate(masks, iters, out=None):
     """masks [T,H,W,ch] u8 -> [T,H,W] u8 {0,255}  (reference diffuerase.py:27-31)."""
     _need_cuda(masks)
     if masks.dim() == 3:
         masks = masks[..., None].contiguous()
     T, H, W, ch = masks.shape
-    out = torch.empty((T, H, W), dtype=torch.uint8, device=masks.device)
+    out = _own_out(out, (T, H, W), torch.uint8, masks, "mask_collapse_dilate")
     tmp = torch.empty_like(out)
     flags = torch.empty(T, dtype=torch.int32, device=masks.device)
     with _Prof("mask_collapse_dilate", 0.0, T * H * W * (ch + 1)):
@@ -660,21 +660,21 @@ def mask_collapse_dilate(masks, iters):
     return out
 
 
-def resize_u8(src, Hd, Wd, mode="bilinear"):
+def resize_u8(src, Hd, Wd, mode="bilinear", out=None):
     _need_cuda(src)
     s4 = src if src.dim() == 4 else src[..., None]
     T, Hs, Ws, ch = s4.shape
-    dst = torch.empty((T, Hd, Wd, ch), dtype=torch.uint8, device=src.device)
+    dst = _own_out(out, (T, Hd, Wd, ch), torch.uint8, src, "resize_u8")
     fn = lib().vv_resize_bilinear_u8 if mode == "bilinear" else lib().vv_resize_nearest_u8
     with _Prof("resize_u8", 0.0, src.numel() + dst.numel()):
         _check(fn(_p(src), T, Hs, Ws, ch, _p(dst), Hd, Wd, _stream()), "vv_resize_u8")
     return dst if src.dim() == 4 else dst[..., 0]
 
 
-def feather_composite(inpainted, orig, mask2d, feather_px):
+def feather_composite(inpainted, orig, mask2d, feather_px, out=None):
     _need_cuda(inpainted, orig, mask2d)
     T, H, W, _ = inpainted.shape
-    out = torch.empty_like(inpainted)
+    out = _own_out(out, inpainted.shape, torch.uint8, inpainted, "feather_composite")
     with _Prof("feather_composite", 0.0, T * H * W * (3 + 3 + 1 + 3)):
         _check(lib().vv_feather_composite(_p(inpainted), _p(orig), _p(mask2d), T, H, W, feather_px, _p(out), _stream()), "vv_feather_composite")
     return out
@@ -735,10 +735,10 @@ def roi_paste_composite(patch, orig, mask2d, offsets, h, w, feather_px, out=None
     return out
 
 
-def chamfer_dt(bin_u8, R):
+def chamfer_dt(bin_u8, R, out=None):
     _need_cuda(bin_u8)
     T, H, W = bin_u8.shape
-    out = torch.empty((T, H, W), dtype=torch.float32, device=bin_u8.device)
+    out = _own_out(out, (T, H, W), torch.float32, bin_u8, "chamfer_dt")
     _check(lib().vv_chamfer_dt(_p(bin_u8), T, H, W, R, _p(out), _stream()), "vv_chamfer_dt")
     return out
 
@@ -867,11 +867,11 @@ def decode_blend(dec, w, acc):
     return acc
 
 
-def blur_compose(pix01, orig, mask2d, taps21):
+def blur_compose(pix01, orig, mask2d, taps21, out=None):
     _need_cuda(pix01, orig, mask2d)
     T, H, W, _ = pix01.shape
     tmp = torch.empty((T, H, W), dtype=torch.float32, device=pix01.device)
-    out = torch.empty((T, H, W, 3), dtype=torch.uint8, device=pix01.device)
+    out = _own_out(out, (T, H, W, 3), torch.uint8, pix01, "blur_compose")
     taps = (C.c_float * 21)(*[float(x) for x in taps21])
     _check(lib().vv_blur_compose(_p(pix01), _p(orig), _p(mask2d), T, H, W, taps, _p(tmp), _p(out), _stream()), "vv_blur_compose")
     return out
@@ -1027,11 +1027,11 @@ def layernorm_ex(dtype, x, gamma, beta, eps, act=ACT_NONE, out_dtype=None, cpad=
     return out
 
 
-def maxpool2x2(x, B, H, W, Cc=None, in_bs=0, x_off=0):
+def maxpool2x2(x, B, H, W, Cc=None, in_bs=0, x_off=0, out=None):
     """B images [H, W, C] (fp32 or h16; image b starts x_off + b * in_bs elements into x, in_bs = 0: contiguous) -> [B*(H/2)*(W/2), C]."""
     _need_cuda(x)
     Cc = x.shape[-1] if Cc is None else Cc
-    out = torch.empty((B * (H // 2) * (W // 2), Cc), dtype=x.dtype, device=x.device)
+    out = _own_out(out, (B * (H // 2) * (W // 2), Cc), x.dtype, x, "maxpool2x2")
     _check(lib().vv_maxpool2x2(x.data_ptr() + x_off * x.element_size(), dt_of(x), B, H, W, Cc, in_bs, _p(out), _stream()),
            "vv_maxpool2x2")
     return out
@@ -1045,26 +1045,26 @@ def rope_apply(dtype, x, rows_rope, cos_sin, D, col0=0, ld=None):
     return x
 
 
-def dwconv(x, H, W, w, bias):
+def dwconv(x, H, W, w, bias, out=None):
     _need_cuda(x, w, bias)
-    out = torch.empty_like(x)
+    out = _own_out(out, x.shape, torch.float32, x, "dwconv")
     _check(lib().vv_dwconv(_p(x), H, W, x.shape[-1], _p(w), _p(bias), w.shape[-1], _p(out), _stream()), "vv_dwconv")
     return out
 
 
-def pixel_shuffle2(dtype, y, bias, h, w, add=None, act=ACT_NONE, out_dtype=torch.float32):
+def pixel_shuffle2(dtype, y, bias, h, w, add=None, act=ACT_NONE, out_dtype=torch.float32, out=None):
     _need_cuda(y, bias, add)
     Cc = y.shape[-1] // 4
-    out = torch.empty((4 * h * w, Cc), dtype=out_dtype, device=y.device)
+    out = _own_out(out, (4 * h * w, Cc), out_dtype, y, "pixel_shuffle2")
     _check(lib().vv_pixel_shuffle2(_p(y), _p(bias), _p(add), h, w, Cc, act, _p(out), dt_of(out), dtype, _stream()), "vv_pixel_shuffle2")
     return out
 
 
-def resize_bilinear_f32(src, Hs, Ws, Hd, Wd):
+def resize_bilinear_f32(src, Hs, Ws, Hd, Wd, out=None):
     """fp32 [Hs*Ws, C] -> [Hd*Wd, C], F.interpolate(mode="bilinear", align_corners=False)."""
     _need_cuda(src)
     Cc = src.shape[-1]
-    out = torch.empty((Hd * Wd, Cc), dtype=torch.float32, device=src.device)
+    out = _own_out(out, (Hd * Wd, Cc), torch.float32, src, "resize_bilinear_f32")
     _check(lib().vv_resize_bilinear_f32(_p(src), Hs, Ws, Cc, _p(out), Hd, Wd, _stream()), "vv_resize_bilinear_f32")
     return out
 
@@ -1083,17 +1083,17 @@ def act_inplace(x, act):
     return x
 
 
-def prompt_points(coords, labels, inv_size, gauss, table):
+def prompt_points(coords, labels, inv_size, gauss, table, out=None):
     _need_cuda(coords, labels, gauss, table)
     P, D = labels.numel(), table.shape[-1]
-    out = torch.empty((P, D), dtype=torch.float32, device=coords.device)
+    out = _own_out(out, (P, D), torch.float32, coords, "prompt_points")
     _check(lib().vv_prompt_points(_p(coords), _p(labels), P, inv_size, _p(gauss), _p(table), D, _p(out), _stream()), "vv_prompt_points")
     return out
 
 
-def sine_pe_1d(pos, dim, temperature=10000.0):
+def sine_pe_1d(pos, dim, temperature=10000.0, out=None):
     _need_cuda(pos)
-    out = torch.empty((pos.numel(), dim), dtype=torch.float32, device=pos.device)
+    out = _own_out(out, (pos.numel(), dim), torch.float32, pos, "sine_pe_1d")
     _check(lib().vv_sine_pe_1d(_p(pos), pos.numel(), dim, temperature, _p(out), _stream()), "vv_sine_pe_1d")
     return out
 
@@ -1106,9 +1106,9 @@ def sam_select(masks, iou, obj_logit, multimask, delta, thresh, out=None):
     return sel
 
 
-def sam_pick(masks, sel, no_obj_score):
+def sam_pick(masks, sel, no_obj_score, out=None):
     _need_cuda(masks, sel)
-    out = torch.empty(masks.shape[-1], dtype=torch.float32, device=masks.device)
+    out = _own_out(out, (masks.shape[-1],), torch.float32, masks, "sam_pick")
     _check(lib().vv_sam_pick(_p(masks), masks.shape[-1], _p(sel), no_obj_score, _p(out), _stream()), "vv_sam_pick")
     return out
 
@@ -1134,19 +1134,19 @@ def clamp_f32(x, lo, hi, out=None):
     return out
 
 
-def fill_holes(mask, H, W, max_area):
-    """in place on fp32 [H*W]."""
+def fill_holes(mask, H, W, max_area, ws=None):
+    """in place on fp32 [H*W].  ws: the caller's int32 [3*H*W] workspace instead of a fresh one."""
     _need_cuda(mask)
-    ws = torch.empty(3 * H * W, dtype=torch.int32, device=mask.device)
+    ws = _own_out(ws, (3 * H * W,), torch.int32, mask, "fill_holes (ws)")
     _check(lib().vv_fill_holes(_p(mask), H, W, max_area, _p(ws), _stream()), "vv_fill_holes")
     return mask
 
 
-def hyper_masks(hyper, up):
+def hyper_masks(hyper, up, out=None):
     """masks [nm, HW] = hyper [nm, C] @ up [HW, C]^T, fp32."""
     _need_cuda(hyper, up)
     nm, Cc = hyper.shape
-    out = torch.empty((nm, up.shape[0]), dtype=torch.float32, device=up.device)
+    out = _own_out(out, (nm, up.shape[0]), torch.float32, up, "hyper_masks")
     _check(lib().vv_hyper_masks(_p(hyper), _p(up), up.shape[0], Cc, nm, _p(out), _stream()), "vv_hyper_masks")
     return out
 
@@ -1165,11 +1165,11 @@ def attention_split_kv(dtype, q, k, v, out, *, heads, Nq, Nkv, D, S, q_rs, k_rs,
     return out
 
 
-def ycbcr_to_rgb(y, cb, cr, hshift, vshift, full_range=False):
+def ycbcr_to_rgb(y, cb, cr, hshift, vshift, full_range=False, out=None):
     """planar uint8 YCbCr on the device (y [T, H, W], cb / cr [T, ceil(H >> vshift), ceil(W >> hshift)]) -> RGB uint8 [T, H, W, 3] (row n3)."""
     _need_cuda(y, cb, cr)
     T, H, W = y.shape
-    out = torch.empty((T, H, W, 3), dtype=torch.uint8, device=y.device)
+    out = _own_out(out, (T, H, W, 3), torch.uint8, y, "ycbcr_to_rgb")
     _check(lib().vv_ycbcr_to_rgb(_p(y), _p(cb), _p(cr), T, H, W, int(hshift), int(vshift), int(bool(full_range)), _p(out), _stream()), "vv_ycbcr_to_rgb")
     return out
 
