@@ -26,6 +26,7 @@ What a call does with them -- spans, windows, crop -> prior -> model, resize / p
 """
 import argparse
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -50,24 +51,41 @@ _gather = "all"
 _prior_stages = {}      # configure(prior=...): optional learned stages of the ProPainter prior (flow_completion, generator)
 _weights = None         # configure(weights=...) / $VV_WEIGHTS_DIR: a local model store (videovanish_amd/modelhub.py) or a CheckpointWeights
 _loaded = None          # (CheckpointWeights, prior stages) resolved from _weights, cached until configure() is called again
-_roi = None             # configure(roi=...): mask-region inference for calls that do not pass roi= themselves
-_spans = None           # configure(spans=...): mask-span inference for calls that do not pass spans= themselves
-_mask_clean = None      # configure(mask_clean=...): mask clean-up for calls that do not pass mask_clean= themselves
 last_mask_clean = None  # the infill.MaskCleanReport of the last run_infill_on_frames call; None when the stage did not run
-_tone_match = None      # configure(tone_match=...): seam tone matching for calls that do not pass tone_match= themselves
 last_tone_match = None  # the infill.ToneMatchReport of the last run_infill_on_frames call; None when the stage did not run
-_grain_match = None     # configure(grain_match=...): seam grain matching for calls that do not pass grain_match= themselves
 last_grain_match = None # the infill.GrainMatchReport of the last run_infill_on_frames call; None when the stage did not run
-_seam_blend = None      # configure(seam_blend=...): seam membrane blending for calls that do not pass seam_blend= themselves
 last_seam_blend = None  # the infill.SeamBlendReport of the last run_infill_on_frames call; None when the stage did not run
-_plate_fill = None      # configure(plate_fill=...): clean-plate fill for calls that do not pass plate_fill= themselves
 last_plate_fill = None  # the infill.PlateFillReport of the last run_infill_on_frames call; None when the stage did not run
-_plate_align = None     # configure(plate_align=...): clean-plate alignment for calls that do not pass plate_align= themselves
 last_plate_align = None # the infill.PlateAlignReport of the last run_infill_on_frames call; None when the tracker did not run
-_deflicker = None       # configure(deflicker=...): inpaint deflicker for calls that do not pass deflicker= themselves
 last_deflicker = None   # the infill.DeflickerReport of the last run_infill_on_frames call; None when the stage did not run
-_deflicker_align = None      # configure(deflicker_align=...): aligned inpaint deflicker for calls that do not pass deflicker_align= themselves
 last_deflicker_align = None  # the infill.DeflickerAlignReport of the last run_infill_on_frames call; None when the tracker did not run
+
+
+class Option(NamedTuple):
+    """One opt-in setting: the keyword of run_infill_on_frames and configure(), the module whose as_config reads its spellings, the environment
+    variable behind both, the words for it in messages, and what --help shows for the command-line value (None: a choice of the module's
+    SPELLINGS)."""
+    name: str
+    settings: object
+    env: str
+    phrase: str
+    metavar: str = None
+
+
+OPTIONS = (
+    Option("roi", roi_plan, "VV_ROI", "mask-region inference"),
+    Option("spans", span_plan, "VV_SPANS", "mask-span inference"),
+    Option("mask_clean", maskclean, "VV_MASK_CLEAN", "mask clean-up", "on|area=64,bridge=2,grow=1"),
+    Option("tone_match", tonematch, "VV_TONE_MATCH", "seam tone matching", "on|affine|offset|mode=offset,ring=8,smooth=0"),
+    Option("grain_match", grainmatch, "VV_GRAIN_MATCH", "seam grain matching", "on|luma|rgb|mode=rgb,ring=8,strength=0.8,seed=3"),
+    Option("seam_blend", seamblend, "VV_SEAM_BLEND", "seam membrane blending", "on|ring=12,presmooth=2,sweeps=8,max_shift=32,strength=1.0"),
+    Option("plate_fill", platefill, "VV_PLATE_FILL", "clean-plate fill", "on|guard=1,min_samples=4,tol=6,outlier=3,max_gap=0,margin=2"),
+    Option("plate_align", platealign, "VV_PLATE_ALIGN", "clean-plate alignment", "on|levels=4,radius=4,min_overlap=25,max_residual=12"),
+    Option("deflicker", deflicker_settings, "VV_DEFLICKER", "inpaint deflicker", "on|radius=2,tol=12"),
+    Option("deflicker_align", deflickeralign, "VV_DEFLICKER_ALIGN", "aligned inpaint deflicker", "on|levels=4,radius=4,min_overlap=25,max_residual=12"),
+)
+_OPTION = {o.name: o for o in OPTIONS}
+_configured = {}        # configure(<option>=...): the value for calls that do not pass that keyword themselves, as given
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
@@ -104,18 +122,10 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     deflicker=.
     deflicker_align = None / "on" / "levels=4,radius=4,min_overlap=25,max_residual=12" (any subset) / a platealign.PlateAlignConfig: aligned
     inpaint deflicker for calls that do not pass deflicker_align=."""
-    global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded, _roi, _spans, _mask_clean, _tone_match, _grain_match
-    global _seam_blend, _plate_fill, _plate_align, _deflicker, _deflicker_align
-    deflickeralign.as_config(deflicker_align)
-    deflicker_settings.as_config(deflicker)
-    platealign.as_config(plate_align)
-    platefill.as_config(plate_fill)
-    seamblend.as_config(seam_blend)
-    grainmatch.as_config(grain_match)
-    tonematch.as_config(tone_match)
-    maskclean.as_config(mask_clean)
-    span_plan.as_config(spans)
-    roi_plan.as_config(roi)                 # validated now, kept as given: configure(roi="off") means the full frame whatever $VV_ROI says
+    global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded
+    given = locals()
+    for o in reversed(OPTIONS):             # validated now, kept as given: configure(roi="off") means the full frame whatever $VV_ROI says
+        o.settings.as_config(given[o.name])
     if reference_defaults:
         import dataclasses
         run = dataclasses.replace(run or RunConfig(), windowing="reference")
@@ -123,16 +133,7 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     _run_config, _dist, _gather, last_ckpt = run, dist, gather, None
     _prior_stages, propainter = dict(prior or {}), None
     _weights, _loaded = weights, None
-    _roi = roi
-    _spans = spans
-    _mask_clean = mask_clean
-    _tone_match = tone_match
-    _grain_match = grain_match
-    _seam_blend = seam_blend
-    _plate_fill = plate_fill
-    _plate_align = plate_align
-    _deflicker = deflicker
-    _deflicker_align = deflicker_align
+    _configured.update({o.name: given[o.name] for o in OPTIONS})
 
 
 def _resolve_weights(ckpt):
@@ -154,27 +155,28 @@ def _resolve_weights(ckpt):
     return w, stages
 
 
+def _setting(name, value, *more):
+    """The setting `name` a call runs with: its own argument, else configure()'s, else the environment's; "off" (or False) at any level ends
+    the search with None.  more = what the option's as_config takes besides the value."""
+    o = _OPTION[name]
+    for v in (value, _configured.get(name)):
+        if v is not None:
+            return o.settings.as_config(v, *more)
+    return o.settings.as_config(os.environ.get(o.env), *more)
+
+
 def roi_config(roi=None):
     """The mask-region setting a call runs with: its own roi= argument, else configure(roi=...), else $VV_ROI (static | follow | static-regions |
     follow-regions | off).
     None = full frame.  roi="off" (or False) asks for the full frame whatever configure() or the environment say."""
-    if roi is not None:
-        return roi_plan.as_config(roi)
-    if _roi is not None:
-        return roi_plan.as_config(_roi)
-    return roi_plan.as_config(os.environ.get("VV_ROI"))
+    return _setting("roi", roi)
 
 
 def spans_config(spans=None, cuts=None):
     """The mask-span setting a call runs with: its own spans= argument, else configure(spans=...), else $VV_SPANS (masked | cuts | masked-cuts | off).
     None = the full clip.  spans="off" (or False) asks for the full clip whatever configure() or the environment say.  cuts (frame indices) replaces
     the setting's own cuts: explicit cuts always override the detector; given alone it means "every frame, split at these cuts"."""
-    if spans is not None:
-        cfg = span_plan.as_config(spans)
-    elif _spans is not None:
-        cfg = span_plan.as_config(_spans)
-    else:
-        cfg = span_plan.as_config(os.environ.get("VV_SPANS"))
+    cfg = _setting("spans", spans)
     if cuts is not None and not (spans is not None and cfg is None):        # spans="off" wins over cuts=
         import dataclasses
         cfg = span_plan.SpanConfig("all", cuts=cuts) if cfg is None else dataclasses.replace(cfg, cuts=cuts)
@@ -184,87 +186,55 @@ def spans_config(spans=None, cuts=None):
 def mask_clean_config(mask_clean=None):
     """The mask clean-up setting a call runs with: its own mask_clean= argument, else configure(mask_clean=...), else $VV_MASK_CLEAN (on | off |
     area=N,bridge=N,grow=N).  None = no clean-up.  mask_clean="off" (or False) asks for none whatever configure() or the environment say."""
-    if mask_clean is not None:
-        return maskclean.as_config(mask_clean)
-    if _mask_clean is not None:
-        return maskclean.as_config(_mask_clean)
-    return maskclean.as_config(os.environ.get("VV_MASK_CLEAN"))
+    return _setting("mask_clean", mask_clean)
 
 
 def tone_match_config(tone_match=None):
     """The seam tone matching setting a call runs with: its own tone_match= argument, else configure(tone_match=...), else $VV_TONE_MATCH (on |
     affine | offset | off | mode=..,ring=N,..).  None = no tone matching.  tone_match="off" (or False) asks for none whatever configure() or the
     environment say."""
-    if tone_match is not None:
-        return tonematch.as_config(tone_match)
-    if _tone_match is not None:
-        return tonematch.as_config(_tone_match)
-    return tonematch.as_config(os.environ.get("VV_TONE_MATCH"))
+    return _setting("tone_match", tone_match)
 
 
 def grain_match_config(grain_match=None):
     """The seam grain matching setting a call runs with: its own grain_match= argument, else configure(grain_match=...), else $VV_GRAIN_MATCH (on |
     luma | rgb | off | mode=..,ring=N,..).  None = no grain matching.  grain_match="off" (or False) asks for none whatever configure() or the
     environment say."""
-    if grain_match is not None:
-        return grainmatch.as_config(grain_match)
-    if _grain_match is not None:
-        return grainmatch.as_config(_grain_match)
-    return grainmatch.as_config(os.environ.get("VV_GRAIN_MATCH"))
+    return _setting("grain_match", grain_match)
 
 
 def seam_blend_config(seam_blend=None, feather_px=None):
     """The seam membrane blending setting a call runs with: its own seam_blend= argument, else configure(seam_blend=...), else $VV_SEAM_BLEND (on |
     off | ring=N,presmooth=N,sweeps=N,max_shift=N,strength=X).  None = no blending.  seam_blend="off" (or False) asks for none whatever
     configure() or the environment say.  feather_px: the call's feather, which the ring has to be wider than."""
-    if seam_blend is not None:
-        return seamblend.as_config(seam_blend, feather_px)
-    if _seam_blend is not None:
-        return seamblend.as_config(_seam_blend, feather_px)
-    return seamblend.as_config(os.environ.get("VV_SEAM_BLEND"), feather_px)
+    return _setting("seam_blend", seam_blend, feather_px)
 
 
 def plate_fill_config(plate_fill=None):
     """The clean-plate fill setting a call runs with: its own plate_fill= argument, else configure(plate_fill=...), else $VV_PLATE_FILL (on | off |
     guard=N,min_samples=N,tol=N,outlier=N,max_gap=N,margin=N,max_bytes=N).  None = no fill.  plate_fill="off" (or False) asks for none whatever
     configure() or the environment say."""
-    if plate_fill is not None:
-        return platefill.as_config(plate_fill)
-    if _plate_fill is not None:
-        return platefill.as_config(_plate_fill)
-    return platefill.as_config(os.environ.get("VV_PLATE_FILL"))
+    return _setting("plate_fill", plate_fill)
 
 
 def plate_align_config(plate_align=None):
     """The clean-plate alignment setting a call runs with: its own plate_align= argument, else configure(plate_align=...), else $VV_PLATE_ALIGN
     (on | off | levels=N,radius=N,min_overlap=N,max_residual=N).  None = no alignment.  plate_align="off" (or False) asks for none whatever
     configure() or the environment say."""
-    if plate_align is not None:
-        return platealign.as_config(plate_align)
-    if _plate_align is not None:
-        return platealign.as_config(_plate_align)
-    return platealign.as_config(os.environ.get("VV_PLATE_ALIGN"))
+    return _setting("plate_align", plate_align)
 
 
 def deflicker_config(deflicker=None):
     """The inpaint deflicker setting a call runs with: its own deflicker= argument, else configure(deflicker=...), else $VV_DEFLICKER (on | off |
     radius=N,tol=N).  None = no deflicker.  deflicker="off" (or False) asks for none whatever configure() or the environment say."""
-    if deflicker is not None:
-        return deflicker_settings.as_config(deflicker)
-    if _deflicker is not None:
-        return deflicker_settings.as_config(_deflicker)
-    return deflicker_settings.as_config(os.environ.get("VV_DEFLICKER"))
+    return _setting("deflicker", deflicker)
 
 
 def deflicker_align_config(deflicker_align=None):
     """The aligned-deflicker setting a call runs with: its own deflicker_align= argument, else configure(deflicker_align=...), else
     $VV_DEFLICKER_ALIGN (on | off | levels=N,radius=N,min_overlap=N,max_residual=N).  None = the filter stays at a fixed frame place.
     deflicker_align="off" (or False) asks for none whatever configure() or the environment say."""
-    if deflicker_align is not None:
-        return deflickeralign.as_config(deflicker_align)
-    if _deflicker_align is not None:
-        return deflickeralign.as_config(_deflicker_align)
-    return deflickeralign.as_config(os.environ.get("VV_DEFLICKER_ALIGN"))
+    return _setting("deflicker_align", deflicker_align)
 
 
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
@@ -348,22 +318,12 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     if facfg is not None and fcfg is None:
         raise ValueError("deflicker_align= (aligned inpaint deflicker) needs deflicker= (inpaint deflicker)")
     bcfg = seam_blend_config(seam_blend, feather_px if keep_unmasked_original else None)
-    if rcfg is not None and compat_reference_early_return:
-        raise ValueError("roi= (mask-region inference) cannot be combined with compat_reference_early_return=True")
-    if scfg is not None and compat_reference_early_return:
-        raise ValueError("spans= (mask-span inference) cannot be combined with compat_reference_early_return=True")
-    if ccfg is not None and compat_reference_early_return:
-        raise ValueError("mask_clean= (mask clean-up) cannot be combined with compat_reference_early_return=True")
-    if tcfg is not None and compat_reference_early_return:
-        raise ValueError("tone_match= (seam tone matching) cannot be combined with compat_reference_early_return=True")
-    if gcfg is not None and compat_reference_early_return:
-        raise ValueError("grain_match= (seam grain matching) cannot be combined with compat_reference_early_return=True")
-    if bcfg is not None and compat_reference_early_return:
-        raise ValueError("seam_blend= (seam membrane blending) cannot be combined with compat_reference_early_return=True")
-    if pcfg is not None and compat_reference_early_return:
-        raise ValueError("plate_fill= (clean-plate fill) cannot be combined with compat_reference_early_return=True")
-    if fcfg is not None and compat_reference_early_return:
-        raise ValueError("deflicker= (inpaint deflicker) cannot be combined with compat_reference_early_return=True")
+    if compat_reference_early_return:
+        on = dict(roi=rcfg, spans=scfg, mask_clean=ccfg, tone_match=tcfg, grain_match=gcfg, seam_blend=bcfg, plate_fill=pcfg, plate_align=acfg,
+                  deflicker=fcfg, deflicker_align=facfg)
+        for o in OPTIONS:
+            if on[o.name] is not None:
+                raise ValueError(f"{o.name}= ({o.phrase}) cannot be combined with compat_reference_early_return=True")
 
     if prog is not None: prog(5, "dilating frames")
     dev = get_device()
@@ -390,22 +350,13 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     stages = infill.Stages(lambda: _load_model(dev, ckpt), _load_prior, _run_prior,
                            lambda f, d, prior, p: _run_model(f, d, prior, max_img_size, p, num_inference_steps, scheduler))
 
-    tone_parts = None if tcfg is None else []       # one report per clip call, in the order of the spans
-    grain_parts = None if gcfg is None else []
-    blend_parts = None if bcfg is None else []
-    flicker_parts = None if fcfg is None else []
-    falign_parts = None if facfg is None else []
+    seam = {}               # finish's keywords of the stages that are on; each *_out list gets one report per clip call, in the order of the spans
+    for key, cfg in (("tone", tcfg), ("grain", gcfg), ("blend", bcfg), ("flicker", fcfg), ("flicker_align", facfg)):
+        if cfg is not None:
+            seam.update({key: cfg, key + "_out": []})
 
-    def body(frames, dil, prior, p, frame0=0):
-        more = {} if gcfg is None else dict(grain=gcfg, grain_out=grain_parts, frame0=frame0)     # passed only when grain matching is on
-        if bcfg is not None:                                                                       # likewise
-            more.update(blend=bcfg, blend_out=blend_parts)
-        if fcfg is not None:                                                                       # likewise
-            more.update(flicker=fcfg, flicker_out=flicker_parts)
-        if facfg is not None:                                                                      # likewise
-            more.update(flicker_align=facfg, flicker_align_out=falign_parts)
-        return infill.run_clip(frames, dil, prior, rcfg, stages, p, dev, feather_px, keep_unmasked_original, compat_reference_early_return,
-                               tone=tcfg, tone_out=tone_parts, **more)
+    def body(frames, dil, prior, p, **at):          # at: frame0, which run_spans passes when grain matching is on
+        return infill.run_clip(frames, dil, prior, rcfg, stages, p, dev, feather_px, keep_unmasked_original, compat_reference_early_return, **seam, **at)
 
     T = len(frames_rgb)
     if scfg is None:
@@ -416,15 +367,15 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         more = {} if gcfg is None else dict(frame0=True)        # each span's clip call learns where it starts
         out = infill.run_spans(frames_rgb, dil_t, propainer_frames, plan, body, prog, load=stages.load_model, **more)
     if tcfg is not None:
-        last_tone_match = infill.tone_report(tone_parts, plan, T)
+        last_tone_match = infill.tone_report(seam["tone_out"], plan, T)
     if gcfg is not None:
-        last_grain_match = infill.grain_report(grain_parts, plan, T)
+        last_grain_match = infill.grain_report(seam["grain_out"], plan, T)
     if bcfg is not None:
-        last_seam_blend = infill.seam_blend_report(blend_parts, plan, T)
+        last_seam_blend = infill.seam_blend_report(seam["blend_out"], plan, T)
     if fcfg is not None:
-        last_deflicker = infill.deflicker_report(flicker_parts, plan, T)
+        last_deflicker = infill.deflicker_report(seam["flicker_out"], plan, T)
     if facfg is not None:
-        last_deflicker_align = infill.deflicker_align_report(falign_parts, plan)
+        last_deflicker_align = infill.deflicker_align_report(seam["flicker_align_out"], plan)
     return out
 
 
@@ -475,84 +426,17 @@ def _frame_io():
     return frameio
 
 
-def _tone_match_arg(text):
-    """--tone-match's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --mask-clean)."""
-    try:
-        if tonematch.as_config(text) is None:
-            raise ValueError("not a setting")
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
-    return text
-
-
-def _grain_match_arg(text):
-    """--grain-match's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --tone-match)."""
-    try:
-        if grainmatch.as_config(text) is None:
-            raise ValueError("not a setting")
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
-    return text
-
-
-def _seam_blend_arg(text):
-    """--seam-blend's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --grain-match)."""
-    try:
-        if seamblend.as_config(text) is None:
-            raise ValueError("not a setting")
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
-    return text
-
-
-def _plate_fill_arg(text):
-    """--plate-fill's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --seam-blend)."""
-    try:
-        if platefill.as_config(text) is None:
-            raise ValueError("not a setting")
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
-    return text
-
-
-def _plate_align_arg(text):
-    """--plate-align's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --plate-fill)."""
-    try:
-        if platealign.as_config(text) is None:
-            raise ValueError("not a setting")
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
-    return text
-
-
-def _deflicker_arg(text):
-    """--deflicker's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --plate-align)."""
-    try:
-        if deflicker_settings.as_config(text) is None:
-            raise ValueError("not a setting")
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
-    return text
-
-
-def _deflicker_align_arg(text):
-    """--deflicker-align's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --deflicker)."""
-    try:
-        if deflickeralign.as_config(text) is None:
-            raise ValueError("not a setting")
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
-    return text
-
-
-def _mask_clean_arg(text):
-    """--mask-clean's value, checked while the arguments are parsed and passed on as written ("off" is refused, as for --roi / --spans)."""
-    try:
-        if maskclean.as_config(text) is None:
-            raise ValueError("not a setting")
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e))
-    return text
+def _setting_arg(name):
+    """The argparse type of an option's command-line value: checked while the arguments are parsed and passed on as written ("off" is refused,
+    as for --roi / --spans)."""
+    def check(text):
+        try:
+            if _OPTION[name].settings.as_config(text) is None:
+                raise ValueError("not a setting")
+        except ValueError as e:
+            raise argparse.ArgumentTypeError(str(e))
+        return text
+    return check
 
 
 # =============================
@@ -574,36 +458,36 @@ def main():
     ap.add_argument("--spans", choices=span_plan.SPELLINGS, default=None,
                     help="Mask-span inference: masked = process only the frame runs that have a mask (with some context), the other frames stay "
                          "the original ones; cuts = process every frame but split the clip at hard cuts found in the video; masked-cuts = both.")
-    ap.add_argument("--mask-clean", type=_mask_clean_arg, default=None, metavar="on|area=64,bridge=2,grow=1",
+    ap.add_argument("--mask-clean", type=_setting_arg("mask_clean"), default=None, metavar=_OPTION["mask_clean"].metavar,
                     help="Mask clean-up before anything reads the masks: drop components of the dilated mask that hold fewer than `area` mask pixels "
                          "(on: four cells of a 256 x 256 grid at the clip's size), fill dropouts of at most `bridge` frames (on: 2), hold the mask "
                          "`grow` frames longer at both ends (on: 0).  Prints one line with what it changed.")
-    ap.add_argument("--tone-match", type=_tone_match_arg, default=None, metavar="on|affine|offset|mode=offset,ring=8,smooth=0",
+    ap.add_argument("--tone-match", type=_setting_arg("tone_match"), default=None, metavar=_OPTION["tone_match"].metavar,
                     help="Seam tone matching before the composite: per frame and channel, fit the model's pixels to the original ones over the ring of "
                          "unmasked pixels within `ring` px of the mask (on: a gain and an offset, ring 12, pooled over 2 frames either side; offset: "
                          "an offset only) and correct every pasted pixel with it.  Prints one line with what it applied.")
-    ap.add_argument("--grain-match", type=_grain_match_arg, default=None, metavar="on|luma|rgb|mode=rgb,ring=8,strength=0.8,seed=3",
+    ap.add_argument("--grain-match", type=_setting_arg("grain_match"), default=None, metavar=_OPTION["grain_match"].metavar,
                     help="Seam grain matching before the composite: measure, over the flat part of the ring of unmasked pixels within `ring` px of the "
                          "mask, the grain the original pixels have and the model's lack, and add white noise of that level to every pasted pixel (on / "
                          "luma: one noise value per pixel; rgb: one per channel).  Prints one line with what it added.")
-    ap.add_argument("--seam-blend", type=_seam_blend_arg, default=None, metavar="on|ring=12,presmooth=2,sweeps=8,max_shift=32,strength=1.0",
+    ap.add_argument("--seam-blend", type=_setting_arg("seam_blend"), default=None, metavar=_OPTION["seam_blend"].metavar,
                     help="Seam membrane blending before the composite: interpolate the difference original - model from the ring of unmasked pixels "
                          "within `ring` px of the mask harmonically into the hole and add it to every pasted pixel, so that the patch meets the "
                          "original along the whole outline (a correction that varies across the hole).  Prints one line with what it added.")
-    ap.add_argument("--plate-fill", type=_plate_fill_arg, default=None, metavar="on|guard=1,min_samples=4,tol=6,outlier=3,max_gap=0,margin=2",
+    ap.add_argument("--plate-fill", type=_setting_arg("plate_fill"), default=None, metavar=_OPTION["plate_fill"].metavar,
                     help="Clean-plate fill before anything plans or runs the model: a masked pixel whose background the same shot shows steadily (a "
                          "standard deviation of at most `tol` over at least `min_samples` unmasked frames, `guard` frames away from the mask) is filled "
                          "from the nearest such frame and leaves the mask; what is never revealed stays with the model.  For locked-off shots.  "
                          "Prints one line with what it filled.")
-    ap.add_argument("--plate-align", type=_plate_align_arg, default=None, metavar="on|levels=4,radius=4,min_overlap=25,max_residual=12",
+    ap.add_argument("--plate-align", type=_setting_arg("plate_align"), default=None, metavar=_OPTION["plate_align"].metavar,
                     help="With --plate-fill: track one integer translation per frame first (a coarse-to-fine search over `levels` pyramid levels, "
                          "+-`radius` at the coarsest; a frame whose best match differs by more than `max_residual` levels on average is left out) "
                          "and fill on the canvas in which the background stands still.  For slow pans and tilts.  Prints one line with what it tracked.")
-    ap.add_argument("--deflicker", type=_deflicker_arg, default=None, metavar="on|radius=2,tol=12",
+    ap.add_argument("--deflicker", type=_setting_arg("deflicker"), default=None, metavar=_OPTION["deflicker"].metavar,
                     help="Inpaint deflicker before the seam stages: every pixel of the model's output becomes the mean of those of its neighbours at "
                          "most `radius` frames away (on: 2) that lie within `tol` levels of it (on: 12), so the patch stops shimmering; what changes by "
                          "more (a moving edge) stays as it is.  Prints one line with what it changed.")
-    ap.add_argument("--deflicker-align", type=_deflicker_align_arg, default=None, metavar="on|levels=4,radius=4,min_overlap=25,max_residual=12",
+    ap.add_argument("--deflicker-align", type=_setting_arg("deflicker_align"), default=None, metavar=_OPTION["deflicker_align"].metavar,
                     help="With --deflicker: track one integer translation per frame first (the tracker of --plate-align, per span) and read the "
                          "filter's temporal neighbours along it, so the patch stops shimmering under a pan or tilt too.  A frame the tracker "
                          "loses stays unfiltered; split at cuts with --spans cuts.  Prints one line with what it tracked.")
@@ -623,17 +507,8 @@ def main():
         Hp, Wp = prior_frames[0].shape[:2]
         assert (H0 == Hp and W0 == Wp), "prior and color video are diffrent sizes"
     assert (H0 == Hm and W0 == Wm), "mask and color video are diffrent sizes"
-    kw = {"roi": args.roi} if args.roi is not None else {}      # pass roi= / spans= / cuts= only when asked for: a default call stays the reference's call
-    if args.spans is not None: kw["spans"] = args.spans
-    if args.cuts is not None: kw["cuts"] = args.cuts
-    if args.mask_clean is not None: kw["mask_clean"] = args.mask_clean
-    if args.tone_match is not None: kw["tone_match"] = args.tone_match
-    if args.grain_match is not None: kw["grain_match"] = args.grain_match
-    if args.seam_blend is not None: kw["seam_blend"] = args.seam_blend
-    if args.plate_fill is not None: kw["plate_fill"] = args.plate_fill
-    if args.plate_align is not None: kw["plate_align"] = args.plate_align
-    if args.deflicker is not None: kw["deflicker"] = args.deflicker
-    if args.deflicker_align is not None: kw["deflicker_align"] = args.deflicker_align
+    # pass roi= / spans= / cuts= / a stage only when asked for: a default call stays the reference's call
+    kw = {name: getattr(args, name) for name in [o.name for o in OPTIONS] + ["cuts"] if getattr(args, name) is not None}
     out_frames = run_infill_on_frames(frames, mask_frames, propainer_frames=prior_frames, **kw)
     if args.mask_clean is not None and last_mask_clean is not None:
         r = last_mask_clean

@@ -89,3 +89,42 @@ def test_configure_reference_defaults_is_one_switch():
     finally:
         diffuerase.configure()
     assert diffuerase._run_config is None and diffuerase._prior_stages == {}
+
+
+def test_every_row_of_the_option_table_resolves_argument_then_configure_then_environment(monkeypatch):
+    """diffuerase.OPTIONS: for each row and each value its --help shows (metavar; the module's SPELLINGS for the rows that are a choice), the
+    row's public resolver prefers the argument over configure() over the environment, and "off" wins at each level."""
+    import dataclasses
+    import diffuerase
+    names = ["roi", "spans", "mask_clean", "tone_match", "grain_match", "seam_blend", "plate_fill", "plate_align", "deflicker", "deflicker_align"]
+    assert [o.name for o in diffuerase.OPTIONS] == names
+    for o in diffuerase.OPTIONS:
+        monkeypatch.delenv(o.env, raising=False)
+    try:
+        for o in diffuerase.OPTIONS:
+            assert o.env == "VV_" + o.name.upper()
+            resolve = getattr(diffuerase, o.name + "_config")
+            for text in (o.metavar.split("|") if o.metavar else o.settings.SPELLINGS):
+                cfg = o.settings.as_config(text)
+                mine, yours = dataclasses.replace(cfg), dataclasses.replace(cfg)           # equal settings, told apart by identity
+                diffuerase.configure()
+                assert cfg is not None and resolve() is None
+                monkeypatch.setenv(o.env, text)
+                assert resolve() == cfg                                                    # the environment alone
+                assert resolve(mine) is mine                                               # the argument over the environment
+                assert resolve("off") is None and resolve(False) is None                  # "off" as the argument
+                diffuerase.configure(**{o.name: yours})
+                assert resolve() is yours                                                  # configure() over the environment
+                assert resolve(mine) is mine                                               # the argument over configure()
+                assert resolve("off") is None
+                diffuerase.configure(**{o.name: "off"})
+                assert resolve() is None                                                   # "off" in configure() over the environment
+                assert resolve(mine) is mine
+                monkeypatch.setenv(o.env, "off")
+                diffuerase.configure()
+                assert resolve() is None                                                   # "off" in the environment
+                diffuerase.configure(**{o.name: text})
+                assert resolve() == cfg                                                    # configure() over the environment's "off"
+                monkeypatch.delenv(o.env)
+    finally:
+        diffuerase.configure()

@@ -250,6 +250,28 @@ def test_no_resolution_without_the_option(gpu, clip):
         flicker_hip._lib = kept
 
 
+def test_seam_bindings_stay_unresolved_while_their_stage_is_off(gpu, clip):
+    """The same for the seam stages of infill.finish: a call with no stage leaves fresh tone_hip, grain_hip and blend_hip unresolved, the
+    tone-only call grain_hip and blend_hip."""
+    import diffuerase
+    from videovanish_amd import blend_hip, grain_hip, tone_hip
+    frames, masks, prior = clip
+    mods = (tone_hip, grain_hip, blend_hip)
+    kept = [m._lib for m in mods]
+    diffuerase.configure(RUN)
+    try:
+        for kw, off in ((dict(), mods), (dict(roi=FOLLOW), mods), (dict(tone_match="on", roi=FOLLOW), mods[1:])):
+            for m in mods:
+                m._lib = None
+            diffuerase.run_infill_on_frames(frames, masks, propainer_frames=prior, feather_px=3, **KW, **kw)
+            assert all(m._lib is None for m in off)
+            assert (tone_hip._lib is not None) == ("tone_match" in kw)
+    finally:
+        diffuerase.configure(None)
+        for m, lib in zip(mods, kept):
+            m._lib = lib
+
+
 @pytest.mark.parametrize("kw", PLUMBING, ids=["plain", "seams", "spans-follow"])
 def test_drop_in_radius_0_is_the_call_without_the_option(gpu, clip, run, kw):
     """radius = 0 only materialises the resize that the paste kernels otherwise do on the fly: byte for byte the call without the option, at a

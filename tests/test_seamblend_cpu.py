@@ -458,6 +458,162 @@ def test_finish_two_windows_and_groups_with_stand_ins(monkeypatch):
     assert calls[0][2] == calls[2][2] == M.scratch_bytes(2, 48, 64)                                   # one buffer per window, sized for the first group
 
 
+def _all_stand_ins(monkeypatch, calls, on):
+    """Every device entry point finish can end a window in or measure with, as its restatement on CPU tensors; calls gets (name, frames) per
+    call.  A binding whose stage is not in `on` raises from every entry point and from lib()."""
+    import torch
+    from videovanish_amd import blend_hip, grain_hip, hip, tone_hip
+    n = lambda t: t.numpy()
+    th = lambda a: torch.from_numpy(np.ascontiguousarray(a))
+    ident = lambda T: np.broadcast_to(R.IDENT, (T, 3, 256))
+
+    def into(out, res):
+        out.copy_(th(res))
+        return out
+
+    def said(name, fn):
+        def f(patch, *a, **k):
+            calls.append((name, len(patch)))
+            return fn(patch, *a, **k)
+        return f
+
+    stand = {
+        (tone_hip, "ring_stats"): lambda patch, orig, mask, offs, h, w, ring: th(TR.sums(n(patch), n(orig), n(mask), n(offs), h, w, ring)),
+        (tone_hip, "paste_lut_composite"): lambda patch, orig, mask, offs, lut, h, w, feather, out=None:
+            into(out, TR.composite(n(patch), n(orig), n(mask), n(offs), n(lut), h, w, feather)),
+        (grain_hip, "ring_grain_stats"): lambda patch, orig, mask, offs, lut, h, w, ring, flat:
+            th(GR.sums(n(patch), n(orig), n(mask), n(offs), n(lut), h, w, ring, flat)),
+        (grain_hip, "paste_grain_composite"): lambda patch, orig, mask, offs, lut, amp, ids, seed, mode, h, w, feather, out=None:
+            into(out, GR.composite(n(patch), n(orig), n(mask), n(offs), n(lut), n(amp), n(ids), seed, ("luma", "rgb")[mode], h, w, feather)),
+        (blend_hip, "solve"): lambda patch, orig, mask, offs, lut, h, w, ring, presmooth, sweeps, max_shift, scratch=None:
+            tuple(th(v) for v in R.solve(n(patch), n(orig), n(mask), n(offs), n(lut), h, w, ring, presmooth, sweeps, max_shift)),
+        (blend_hip, "paste_blend_composite"): lambda patch, orig, mask, offs, lut, field, q8, amp, ids, seed, mode, h, w, feather, out=None:
+            into(out, R.composite(n(patch), n(orig), n(mask), n(offs), n(lut), n(field), q8, n(amp), n(ids), seed, ("luma", "rgb")[mode], h, w, feather)),
+        (hip, "roi_paste_composite"): lambda patch, orig, mask, offs, h, w, feather, out=None:
+            into(out, TR.composite(n(patch), n(orig), n(mask), n(offs), ident(len(patch)), h, w, feather)),
+        (hip, "feather_composite"): lambda x, orig, mask, feather:
+            th(TR.composite(n(x), n(orig), n(mask), np.zeros((len(x), 2), np.int32), ident(len(x)), *x.shape[1:3], feather)),
+    }
+    stage_of = {tone_hip: "tone", grain_hip: "grain", blend_hip: "blend"}
+    for (mod, name), fn in stand.items():
+        if stage_of.get(mod, "") in on or mod is hip:
+            monkeypatch.setattr(mod, name, said(name, fn))
+        else:
+            boom = lambda *a, _what=f"{mod.__name__}.{name}", **k: (_ for _ in ()).throw(AssertionError(f"{_what} called with its stage off"))
+            monkeypatch.setattr(mod, name, boom)
+            monkeypatch.setattr(mod, "lib", boom)
+
+
+def _matrix_clip(layout):
+    """(orig [T,H,W,3], mask [T,H,W], windows [(offsets [T,2], (h, w), model frames [T,h,w,3])], plans for finish, the frames this rank holds)."""
+    H, W = 96, 130
+    if layout == "full":            # test_finish_full_frame_with_stand_ins' clip
+        T = 3
+        orig = np.stack([np.clip(TR.smooth_texture(s, H, W).astype(np.float64) + np.random.default_rng(s).normal(0, 3, (H, W, 3)), 0, 255).astype(np.uint8)
+                         for s in range(T)])
+        x = np.clip(np.rint(np.stack([TR.smooth_texture(s, H, W) for s in range(T)]) * 0.95 + 4 + R.shift_field("vignette", H, W)[None]), 0, 255).astype(np.uint8)
+        mask = np.stack([R.box_mask(), R.two_components(), np.zeros((H, W), np.uint8)])
+        return orig, mask, [(np.zeros((T, 2), np.int32), (H, W), x)], [], [0, 1, 2]
+    T = 4                           # test_finish_two_windows_and_groups_with_stand_ins' windows, the originals with grain
+    smooth = np.stack([TR.smooth_texture(10 + s, H, W) for s in range(T)])
+    orig = np.clip(smooth + np.random.default_rng(3).normal(0, 3, smooth.shape), 0, 255).astype(np.uint8)
+    mask = np.zeros((T, H, W), np.uint8)
+    wins = []
+    for (oy, ox), (h, w), (y0, x0, y1, x1), kind in [((0, 0), (48, 64), (12, 15, 30, 40), "ramp"), ((50, 70), (40, 56), (60, 85, 75, 110), "vignette")]:
+        mask[:, y0:y1, x0:x1] = 255
+        offs = np.tile(np.array([[oy, ox]], np.int32), (T, 1))
+        wins.append((offs, (h, w), np.clip(np.rint(smooth[:, oy:oy + h, ox:ox + w] * 0.95 + 4 + R.shift_field(kind, h, w)[None]), 0, 255).astype(np.uint8)))
+    return orig, mask, wins, [types.SimpleNamespace(size=s, offsets=o) for o, s, _ in wins], [0, 1, 3]
+
+
+_MATRIX_WANT = {}
+
+
+def _matrix_want(layout, on, feather):
+    """The chained references over all T frames; the frame another rank holds has no mask pixel there (no ring: zero sums, nothing pooled from
+    it, as finish's zero rows), and its bytes are not compared."""
+    key = (layout, on, feather)
+    if key not in _MATRIX_WANT:
+        orig, mask, wins, _, idx = _matrix_clip(layout)
+        T = len(orig)
+        held = np.zeros(T, bool)
+        held[idx] = True
+        mask = np.where(held[:, None, None], mask, 0).astype(np.uint8)
+        ids = [7 + t for t in range(T)]
+        tone = dict(ring=12) if "tone" in on else None
+        want = orig
+        for offs, (h, w), x in wins:
+            if "blend" in on:
+                want = R.apply(x, want, mask, offs, h, w, feather, frame_ids=ids, strength=0.75, tone=tone,
+                               grain=dict(seed=5, min_count=64) if "grain" in on else None)[0]
+            elif "grain" in on:
+                want = GR.apply(x, want, mask, offs, h, w, feather, ids, tone=tone, seed=5, min_count=64)[0]
+            elif "tone" in on:
+                want = TR.apply(x, want, mask, offs, h, w, feather, ring=12)[0]
+            else:
+                want = TR.composite(x, want, mask, offs, np.broadcast_to(R.IDENT, (T, 3, 256)), h, w, feather)
+        _MATRIX_WANT[key] = want
+    return _MATRIX_WANT[key]
+
+
+@pytest.mark.parametrize("on", [(), ("tone",), ("grain",), ("blend",), ("tone", "grain"), ("tone", "blend"), ("grain", "blend"), ("tone", "grain", "blend")],
+                         ids=lambda on: "+".join(on) or "none")
+@pytest.mark.parametrize("layout", ["full", "windows"])
+def test_finish_stage_matrix_with_stand_ins(monkeypatch, layout, on):
+    """Every subset of {tone, grain, blend} on the full frame and on two windows (one frame held by another rank), the feathered composite and
+    the plain paste: the bytes of the chained restatements, exactly the entry points of that subset (a stage that is off contributes no
+    call and resolves nothing of its binding), and one [K,T,...] report per requested list with zero / identity rows for the frame this rank
+    does not hold."""
+    import torch
+    from videovanish_amd import infill
+    from videovanish_amd.grainmatch import GrainMatchConfig
+    from videovanish_amd.tonematch import ToneMatchConfig
+    calls = []
+    _all_stand_ins(monkeypatch, calls, on)
+    orig, mask, wins, plans, idx = _matrix_clip(layout)
+    T, K, n = len(orig), len(wins), len(idx)
+    groups = [(0, n)] if layout == "full" else [(0, 2), (2, n)]
+    monkeypatch.setattr(M, "groups", lambda T, h, w: groups)
+    cfgs = dict(tone=ToneMatchConfig(), grain=GrainMatchConfig(seed=5, min_count=64), blend=SeamBlendConfig(strength=0.75))
+    for keep in (True, False):
+        del calls[:]
+        outs = [[f if t in idx else None for t, f in enumerate(x)] for _, _, x in wins]
+        kw = {}
+        for s in on:
+            kw.update({s: cfgs[s], s + "_out": []})
+        if "grain" in on or "blend" in on:
+            kw["frame0"] = 7
+        got = infill.finish(outs, list(orig), torch.from_numpy(mask), plans, 3, keep, "cpu", **kw)
+        assert [t for t in range(T) if got[t] is not None] == idx
+        want = _matrix_want(layout, on, 3.0 if keep else -1.0)
+        assert (np.stack([got[t] for t in idx]) == want[idx]).all()
+        assert (want[idx] != orig[idx]).any()
+        per_window = [("ring_stats", n)] * ("tone" in on) + [("ring_grain_stats", n)] * ("grain" in on)
+        if "blend" in on:
+            per_window += [(name, b - a) for a, b in groups for name in ("solve", "paste_blend_composite")]
+        elif "grain" in on:
+            per_window += [("paste_grain_composite", n)]
+        elif "tone" in on:
+            per_window += [("paste_lut_composite", n)]
+        elif plans:
+            per_window += [("roi_paste_composite", n)]
+        elif keep:
+            per_window += [("feather_composite", n)]
+        assert calls == per_window * K
+        away = [t for t in range(T) if t not in idx]
+        for s in on:
+            rows = kw[s + "_out"]
+            assert len(rows) == 1
+            for name, field in rows[0]._asdict().items():
+                assert field.shape[:2] == (K, T)
+                assert (field[:, away] == (1.0 if (s, name) == ("tone", "gain") else 0.0)).all()
+            assert all((rows[0].n[k, idx[0]] > 0).any() for k in range(K))
+        if "tone" in on and "blend" in on:
+            assert (kw["tone_out"][0].gain == 1.0).all()                                            # the offset alone in front of the membrane
+        if on == ("tone",):
+            assert (kw["tone_out"][0].gain != 1.0).any()
+
+
 def test_finish_without_the_option_calls_nothing_of_the_feature(monkeypatch):
     """No blend=: the tone path calls what it called before, nothing of blend_hip; run_clip passes the new keywords only when the stage is on."""
     import torch

@@ -316,6 +316,42 @@ def test_finish_two_windows_take_their_own_shifts(gpu):
     assert err(plain) >= 6 and err(out) <= 2
 
 
+@pytest.mark.parametrize("stages", ["grain", "tone+grain"])
+def test_finish_two_windows_with_the_other_stages(gpu, stages):
+    """The two windows above, on originals with grain, with the membrane and grain (no tone: the identity table in front of both), and with all
+    three stages: byte for byte the restatement chained over the windows, and one [2,T] report per stage."""
+    from videovanish_amd import infill
+    T, H, W = 3, 96, 130
+    smooth = np.stack([TR.smooth_texture(10 + s, H, W) for s in range(T)]).astype(np.float64)
+    orig = np.clip(np.rint(smooth + np.random.default_rng(41).normal(0, 3, smooth.shape)), 0, 255).astype(np.uint8)
+    wins = [((0, 0), (48, 64), (12, 15, 30, 40), "ramp"), ((50, 70), (40, 56), (60, 85, 75, 110), "vignette")]
+    mask = np.zeros((T, H, W), np.uint8)
+    plans, outs = [], []
+    for (oy, ox), (h, w), (y0, x0, y1, x1), kind in wins:
+        mask[:, y0:y1, x0:x1] = 255
+        offs = np.tile(np.array([[oy, ox]], np.int32), (T, 1))
+        plans.append(RoiPlan("static", (h, w), offs, offs.astype(np.float64)))
+        outs.append(list(np.clip(np.rint(smooth[:, oy:oy + h, ox:ox + w] * 0.95 + 4 + R.shift_field(kind, h, w)[None]), 0, 255).astype(np.uint8)))
+    kw, ref = dict(grain=GRAIN, grain_out=[], frame0=7), dict(grain=GRAIN_FIT)
+    if "tone" in stages:
+        kw.update(tone=TONE, tone_out=[])
+        ref.update(tone=dict(ring=12))
+    rows = []
+    out = np.stack(infill.finish(outs, list(orig), _d(mask, gpu), plans, 3, True, gpu, blend=CFG, blend_out=rows, **kw))
+    want = orig
+    assert len(rows) == 1 and rows[0].n.shape == (2, T)
+    for k, (plan, o) in enumerate(zip(plans, outs)):
+        want, field, cls, sums = R.apply(np.stack(o), want, mask, plan.offsets, *plan.size, 3.0, frame_ids=[7, 8, 9], **ref)
+        _report_equals(rows[0], k, sums)
+    assert (out == want).all()
+    assert len(kw["grain_out"]) == 1 and kw["grain_out"][0].n.shape[:2] == (2, T) and kw["grain_out"][0].sigma_added.any()
+    if "tone" in stages:
+        assert len(kw["tone_out"]) == 1 and kw["tone_out"][0].n.shape == (2, T) and (kw["tone_out"][0].gain == 1.0).all()
+        assert kw["tone_out"][0].offset.any()
+        bare = np.stack(infill.finish(outs, list(orig), _d(mask, gpu), plans, 3, True, gpu, blend=CFG, grain=GRAIN, frame0=7))
+        assert (bare != out).any()                                                                   # the table changes the bytes
+
+
 def test_finish_without_a_difference_is_the_plain_call(gpu):
     """A model frame that equals the original on the ring, and strength 0: the bytes of the call without the option."""
     from videovanish_amd import infill

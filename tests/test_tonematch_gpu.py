@@ -250,6 +250,27 @@ def test_finish_two_windows_are_fitted_independently(gpu):
     assert np.abs(plain.astype(int) - orig.astype(int)).max() >= 6
 
 
+def test_finish_two_windows_without_a_stage_is_the_paste_by_hand(gpu):
+    """No stage, K = 2: finish returns the bytes of hip.roi_paste_composite applied window after window, the feathered composite and the plain
+    paste."""
+    from videovanish_amd import hip, infill
+    orig, _, _ = R.restoration_clip(1.0, 0)
+    T, H, W = orig.shape[:3]
+    mask = np.zeros((T, H, W), np.uint8)
+    plans, outs = [], []
+    for (oy, ox), (h, w), (y0, x0, y1, x1), (a, b) in [((0, 0), (48, 64), (12, 15, 30, 40), (0.9, 10)), ((50, 70), (40, 56), (60, 85, 75, 110), (1.2, -25))]:
+        mask[:, y0:y1, x0:x1] = 255
+        offs = np.tile(np.array([[oy, ox]], np.int32), (T, 1))
+        plans.append(RoiPlan("static", (h, w), offs, offs.astype(np.float64)))
+        outs.append(list(np.clip(np.rint(a * orig[:, oy:oy + h, ox:ox + w].astype(np.float64) + b), 0, 255).astype(np.uint8)))
+    for keep, feather in ((True, 3.0), (False, -1.0)):
+        out = np.stack(infill.finish(outs, list(orig), _d(mask, gpu), plans, 3, keep, gpu))
+        want = _d(orig, gpu)
+        for plan, o in zip(plans, outs):
+            want = hip.roi_paste_composite(_d(np.stack(o), gpu), want, _d(mask, gpu), _d(plan.offsets, gpu), *plan.size, feather)
+        assert (out == want.cpu().numpy()).all() and (out != orig).any()
+
+
 # ---- the drop-in --------------------------------------------------------------------------------------------------------------------------
 RUN = RunConfig(steps=2, chunk=4, overlap=2, seed=3, dtype="fp16", unet=TINY_UNET, vae=TINY_VAE)
 KW = dict(mask_dilation_iter=2, max_img_size=960, num_inference_steps=2, scheduler="ddim")

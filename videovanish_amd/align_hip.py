@@ -37,16 +37,7 @@ def lib():
     """hip.lib() with the signatures of vvalign.h applied (once)."""
     global _lib
     if _lib is None:
-        dll = hip.lib()
-        for name, (restype, argtypes) in SIGNATURES.items():
-            if not hasattr(dll, name):
-                raise RuntimeError(f"libvvhip.so does not export {name}")
-            fn = getattr(dll, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        v = dll.vva_abi_version()
-        if v != ABI_VERSION:
-            raise RuntimeError(f"libvvhip.so clean-plate alignment ABI version {v} != {ABI_VERSION}")
-        _lib = dll
+        _lib = hip.bind(hip.lib(), SIGNATURES, "vva_abi_version", ABI_VERSION, "clean-plate alignment")
     return _lib
 
 

@@ -37,22 +37,12 @@ def lib():
     """hip.lib() with the signatures of vvblend.h applied (once)."""
     global _lib
     if _lib is None:
-        dll = hip.lib()
-        for name, (restype, argtypes) in SIGNATURES.items():
-            if not hasattr(dll, name):
-                raise RuntimeError(f"libvvhip.so does not export {name}")
-            fn = getattr(dll, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        v = dll.vvb_abi_version()
-        if v != ABI_VERSION:
-            raise RuntimeError(f"libvvhip.so seam blending ABI version {v} != {ABI_VERSION}")
-        _lib = dll
+        _lib = hip.bind(hip.lib(), SIGNATURES, "vvb_abi_version", ABI_VERSION, "seam blending")
     return _lib
 
 
 def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc}): {lib().vvb_last_error().decode()}")
+    hip.check(rc, what, lib, "vvb_last_error")
 
 
 def scratch_bytes(T, h, w):

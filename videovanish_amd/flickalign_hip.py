@@ -29,22 +29,12 @@ def lib():
     """hip.lib() with the signatures of vvflickalign.h applied (once)."""
     global _lib
     if _lib is None:
-        dll = hip.lib()
-        for name, (restype, argtypes) in SIGNATURES.items():
-            if not hasattr(dll, name):
-                raise RuntimeError(f"libvvhip.so does not export {name}")
-            fn = getattr(dll, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        v = dll.vvc_abi_version()
-        if v != ABI_VERSION:
-            raise RuntimeError(f"libvvhip.so aligned deflicker ABI version {v} != {ABI_VERSION}")
-        _lib = dll
+        _lib = hip.bind(hip.lib(), SIGNATURES, "vvc_abi_version", ABI_VERSION, "aligned deflicker")
     return _lib
 
 
 def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc}): {lib().vvc_last_error().decode()}")
+    hip.check(rc, what, lib, "vvc_last_error")
 
 
 def hold(win, offsets, track, mask2d, radius, tol, out=None):

@@ -30,22 +30,12 @@ def lib():
     """hip.lib() with the signatures of vvflicker.h applied (once)."""
     global _lib
     if _lib is None:
-        dll = hip.lib()
-        for name, (restype, argtypes) in SIGNATURES.items():
-            if not hasattr(dll, name):
-                raise RuntimeError(f"libvvhip.so does not export {name}")
-            fn = getattr(dll, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        v = dll.vvf_abi_version()
-        if v != ABI_VERSION:
-            raise RuntimeError(f"libvvhip.so deflicker ABI version {v} != {ABI_VERSION}")
-        _lib = dll
+        _lib = hip.bind(hip.lib(), SIGNATURES, "vvf_abi_version", ABI_VERSION, "deflicker")
     return _lib
 
 
 def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc}): {lib().vvf_last_error().decode()}")
+    hip.check(rc, what, lib, "vvf_last_error")
 
 
 def _need_clip(what, t):

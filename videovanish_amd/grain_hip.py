@@ -32,22 +32,12 @@ def lib():
     """hip.lib() with the signatures of vvgrain.h applied (once)."""
     global _lib
     if _lib is None:
-        dll = hip.lib()
-        for name, (restype, argtypes) in SIGNATURES.items():
-            if not hasattr(dll, name):
-                raise RuntimeError(f"libvvhip.so does not export {name}")
-            fn = getattr(dll, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        v = dll.vvg_abi_version()
-        if v != ABI_VERSION:
-            raise RuntimeError(f"libvvhip.so grain matching ABI version {v} != {ABI_VERSION}")
-        _lib = dll
+        _lib = hip.bind(hip.lib(), SIGNATURES, "vvg_abi_version", ABI_VERSION, "grain matching")
     return _lib
 
 
 def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc}): {lib().vvg_last_error().decode()}")
+    hip.check(rc, what, lib, "vvg_last_error")
 
 
 def _need_table(what, name, tab, T):

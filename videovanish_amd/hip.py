@@ -202,6 +202,26 @@ SIGNATURES = {
 EXPORTS = list(SIGNATURES)
 
 
+def bind(dll, signatures, version_fn, version, part=""):
+    """dll with a header's `signatures` (name -> (restype, argtypes)) applied.  RuntimeError when an export is missing or `version_fn` does not
+    return `version`; `part` names the header's part of the library in that message.  hip.lib() and every *_hip.lib() go through here."""
+    for name, (restype, argtypes) in signatures.items():
+        if not hasattr(dll, name):
+            raise RuntimeError(f"libvvhip.so does not export {name}")
+        fn = getattr(dll, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    v = getattr(dll, version_fn)()
+    if v != version:
+        raise RuntimeError(f"libvvhip.so {part + ' ' if part else ''}ABI version {v} != {version}")
+    return dll
+
+
+def check(rc, what, lib, last_error):
+    """RuntimeError with the library's message (lib().<last_error>()) when a launcher returned rc != 0."""
+    if rc != 0:
+        raise RuntimeError(f"{what} failed ({rc}): {getattr(lib(), last_error)().decode()}")
+
+
 def lib():
     """Load libvvhip.so (once).  Raises RuntimeError when it has not been built -- never falls back."""
     global _lib
@@ -209,22 +229,12 @@ def lib():
         if not os.path.isfile(_LIB_PATH):
             raise RuntimeError(f"videovanish_amd: HIP extension missing ({_LIB_PATH}); run videovanish_amd/csrc/build.sh "
                                "or __graft_entry__.build() -- there is no CPU fallback")
-        dll = C.CDLL(_LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
-            if not hasattr(dll, name):
-                raise RuntimeError(f"libvvhip.so does not export {name}")
-            fn = getattr(dll, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        v = dll.vv_abi_version()
-        if v != ABI_VERSION:
-            raise RuntimeError(f"libvvhip.so ABI version {v} != {ABI_VERSION}")
-        _lib = dll
+        _lib = bind(C.CDLL(_LIB_PATH), SIGNATURES, "vv_abi_version", ABI_VERSION)
     return _lib
 
 
 def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc}): {lib().vv_last_error().decode()}")
+    check(rc, what, lib, "vv_last_error")
 
 
 def _stream():

@@ -1,11 +1,12 @@
 """The orchestration of one diffuerase.run_infill_on_frames call after the dilation: the mask clean-up (clean_masks), the clean-plate fill
-(plate_fill), the temporal plan (span_plan, run_spans), and for each clip the windows (region_plans, run_clip), ONE crop -> prior -> model sequence (run_windows) and ONE closing step (finish).  The full frame is
-no window, roi= "static" / "follow" one, the "-regions" spellings several.  With tone matching the closing step fits each window's pixels to the
-ring round the mask first (finish, tone_report); with grain matching it gives them the grain the ring's originals have and the model's pixels lack
-(finish, grain_report); with seam blending it adds the membrane that carries the ring's difference original - model into the hole (finish,
-seam_blend_report); with the deflicker each window's model pixels are first filtered along time (finish, deflicker_report), with its alignment along a translation tracked per clip call
-(finish, deflicker_align_report).  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is
-module state.  Rules and reasons: DESIGN.md §10, §11, §12, §13, §14, §15, §16, §17, §18, §19."""
+(plate_fill), the temporal plan (span_plan, run_spans), and for each clip the windows (region_plans, run_clip), ONE crop -> prior -> model
+sequence (run_windows) and ONE closing step (finish).  The full frame is no window, roi= "static" / "follow" one, the "-regions" spellings
+several.  The closing step is one loop over the windows; in it the opt-in seam stages run on each window's pixels before they are pasted: the
+deflicker along time (with its alignment along a translation tracked per clip call), the tone fit to the ring round the mask, the grain the
+ring's originals have and the model's pixels lack, the membrane that carries the ring's difference original - model into the hole.  Each stage
+reports per clip call; tone_report, grain_report, seam_blend_report, deflicker_report and deflicker_align_report assemble a call's report from
+them.  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is module state.  Rules and reasons: DESIGN.md
+§10, §11, §12, §13, §14, §15, §16, §17, §18, §19."""
 import dataclasses
 from typing import Callable, NamedTuple
 
@@ -134,6 +135,38 @@ def _plan_alignment(frames_rgb, d_seg, boxes, pcfg, acfg):
     return track_t, track, cbox, "fallback" if platealign.canvas_bytes(T, cbox) > pcfg.max_bytes else "canvas"
 
 
+def _fill_device(f, d, invalid, pcfg):
+    """The fill itself on resident frames f [T,h,w,3] (written in place) and their masks d [T,h,w]: the tile occupancy, the sample frames from
+    time_bridge_grow(., 0, guard) (and not where `invalid` is set: the canvas places no tracked frame covers), stats, sources, the margin
+    (mask_collapse_dilate of the unfilled remainder), fill -> (d' on the device, counts [T,2] = (filled, left) on the host, steady pixels)."""
+    occ = hip.mask_tile_union(d, plate_hip.TILE)
+    notsample = d if pcfg.guard == 0 else mask_hip.time_bridge_grow(d, 0, pcfg.guard)[0]
+    if invalid is not None:
+        notsample = torch.bitwise_or(notsample, invalid)
+    st, n, s1 = plate_hip.stats(f, notsample, occ, pcfg.min_samples, pcfg.tol)
+    src, r0 = plate_hip.sources(f, d, notsample, occ, st, n, s1, pcfg.tol, pcfg.outlier, pcfg.max_gap)
+    keep = r0 if pcfg.margin == 0 else hip.mask_collapse_dilate(r0[..., None], pcfg.margin)
+    d2, c = plate_hip.fill(f, d, keep, occ, src)
+    return d2, c.cpu().numpy(), int(st.sum().item())
+
+
+def _fill_on_crop(frames_rgb, d, box, pcfg):
+    """One segment filled on the crop `box` of its frames (d = the masks' crop, contiguous): the crop crosses to the device, the crops of the
+    frames that got a fill come back into copies of those frames -> what _fill_on_canvas returns, dil' being the crop's."""
+    y0, x0, y1, x1 = box
+    f = torch.from_numpy(np.stack([fr[y0:y1, x0:x1] for fr in frames_rgb])).to(d.device)
+    d2, c, steady = _fill_device(f, d, None, pcfg)
+    idx = np.nonzero(c[:, 0])[0]
+    new = {}
+    if not len(idx):
+        return new, None, c, steady
+    got = f[torch.from_numpy(idx).to(f.device)].cpu().numpy()
+    for j, i in enumerate(idx):
+        new[int(i)] = np.array(frames_rgb[i], copy=True)
+        new[int(i)][y0:y1, x0:x1] = got[j]
+    return new, d2, c, steady
+
+
 def _fill_on_canvas(frames_rgb, d_seg, track_t, track, box, pcfg):
     """Steps 5 and 7 - 9 of DESIGN.md §17 for one segment: the canvas from per-frame slices, the unchanged vvp_ kernels on it, the filled pixels
     back into copies of their frames -> ({frame index: new frame}, dil' [T,H,W] or None when nothing was filled, counts [T,2], steady)."""
@@ -146,17 +179,11 @@ def _fill_on_canvas(frames_rgb, d_seg, track_t, track, box, pcfg):
             canvas[t][sl[0]] = frames_rgb[t][sl[1]]
     f = torch.from_numpy(canvas).to(d_seg.device)
     d, invalid = align_hip.place_masks(d_seg, track_t, box)
-    occ = hip.mask_tile_union(d, plate_hip.TILE)
-    notsample = torch.bitwise_or(d if pcfg.guard == 0 else mask_hip.time_bridge_grow(d, 0, pcfg.guard)[0], invalid)
-    st, n, s1 = plate_hip.stats(f, notsample, occ, pcfg.min_samples, pcfg.tol)
-    src, r0 = plate_hip.sources(f, d, notsample, occ, st, n, s1, pcfg.tol, pcfg.outlier, pcfg.max_gap)
-    keep = r0 if pcfg.margin == 0 else hip.mask_collapse_dilate(r0[..., None], pcfg.margin)
-    d2, c = plate_hip.fill(f, d, keep, occ, src)
-    c = c.cpu().numpy()
+    d2, c, steady = _fill_device(f, d, invalid, pcfg)
     idx = np.nonzero(c[:, 0])[0]
     new = {}
     if not len(idx):
-        return new, None, c, int(st.sum().item())
+        return new, None, c, steady
     sel = torch.from_numpy(idx).to(f.device)
     got, went = f[sel].cpu().numpy(), ((d[sel] != 0) & (d2[sel] == 0)).cpu().numpy()
     for j, i in enumerate(idx):
@@ -165,14 +192,13 @@ def _fill_on_canvas(frames_rgb, d_seg, track_t, track, box, pcfg):
         m = went[j][cs]
         fr[fs][m] = got[j][cs][m]                                          # only the filled pixels; fr[fs] is a view
         new[int(i)] = fr
-    return new, align_hip.unplace_mask(d2, d_seg, track_t, box), c, int(st.sum().item())
+    return new, align_hip.unplace_mask(d2, d_seg, track_t, box), c, steady
 
 
 def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None):
     """The clean-plate fill (platefill.py; rules: include/vvplate.h): frames_rgb = the T host frames [H,W,3] u8, dil_t = the masks
     [T,H,W] u8 on the device, pcfg = a PlateFillConfig, cuts = frame indices or None (one segment).  Per segment of spans.segments: the crop of
-    the union box of its masks (platefill.crop_box) crosses to the device, the sample frames come from time_bridge_grow(., 0, guard), then
-    stats, sources, the margin (mask_collapse_dilate of the unfilled remainder), fill in place on the uploaded crop; only the crops of frames
+    the union box of its masks (platefill.crop_box) crosses to the device and is filled in place (_fill_device); only the crops of frames
     that got a fill come back, into copies of those frames.  A segment without a mask pixel uploads nothing; one whose crop exceeds max_bytes
     is left as it is and flagged.  Returns (frames', dil', PlateFillReport): a frame with nothing filled is the caller's array itself, dil' is
     dil_t itself when nothing was filled at all, and neither the caller's frames nor dil_t is ever written.  Depends on nothing but its
@@ -191,55 +217,42 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None):
     steady, skipped = [], []
     arep = [[] for _ in range(6)]
     for s, e in segs:
+        # the segment's plan: "crop" / "canvas" fill; "empty" (no mask pixel), "skipped" (the crop is too large), "none" (no tracked frame has a mask pixel) do not
+        plan, d, at = "crop", dil_t[s:e], ()
         if acfg is not None:
-            track_t, track, cbox, path = _plan_alignment(frames_rgb[s:e], dil_t[s:e], boxes[s:e], pcfg, acfg)
+            track_t, track, cbox, path = _plan_alignment(frames_rgb[s:e], d, boxes[s:e], pcfg, acfg)
             for k, v in enumerate((track[:, :2].copy(), track[:, 2].copy(), track[:, 3] == 1, _residual(track), cbox, path)):
                 arep[k].append(v)
             if path in ("none", "canvas"):
-                steady.append(0)
-                skipped.append(False)
-                left[s:e] = (dil_t[s:e] != 0).flatten(1).sum(1).cpu().numpy()
-                if path == "canvas":
-                    new, d2, c, steady[-1] = _fill_on_canvas(frames_rgb[s:e], dil_t[s:e], track_t, track, cbox, pcfg)
-                    filled[s:e] = c[:, 0]
-                    left[s:e] = np.where(track[:, 3] == 1, c[:, 1], left[s:e])
-                    for i, fr in new.items():
-                        frames[s + i] = fr
-                    if d2 is not None:
-                        if dil is dil_t:
-                            dil = dil_t.clone()
-                        dil[s:e] = d2
-                continue
-        box = platefill.crop_box(boxes[s:e], H, W)
+                plan = path
+        if plan == "crop":
+            box = platefill.crop_box(boxes[s:e], H, W)
+            if box is None:
+                plan = "empty"
+            else:
+                if e - s > platefill.MAX_T or platefill.crop_bytes(e - s, box) > pcfg.max_bytes:
+                    plan = "skipped"
+                at = (slice(box[0], box[2]), slice(box[1], box[3]))
+                d = d[(slice(None),) + at].contiguous()
         steady.append(0)
-        skipped.append(box is not None and (e - s > platefill.MAX_T or platefill.crop_bytes(e - s, box) > pcfg.max_bytes))
-        if box is None:
-            continue
-        y0, x0, y1, x1 = box
-        d = dil_t[s:e, y0:y1, x0:x1].contiguous()
-        if skipped[-1]:
+        skipped.append(plan == "skipped")
+        if plan in ("none", "skipped", "canvas"):       # the masked pixels as they are; the canvas fill replaces those of its tracked frames
             left[s:e] = (d != 0).flatten(1).sum(1).cpu().numpy()
+        if plan not in ("crop", "canvas"):
             continue
-        f = torch.from_numpy(np.stack([fr[y0:y1, x0:x1] for fr in frames_rgb[s:e]])).to(dil_t.device)
-        occ = hip.mask_tile_union(d, plate_hip.TILE)
-        notsample = d if pcfg.guard == 0 else mask_hip.time_bridge_grow(d, 0, pcfg.guard)[0]
-        st, n, s1 = plate_hip.stats(f, notsample, occ, pcfg.min_samples, pcfg.tol)
-        src, r0 = plate_hip.sources(f, d, notsample, occ, st, n, s1, pcfg.tol, pcfg.outlier, pcfg.max_gap)
-        keep = r0 if pcfg.margin == 0 else hip.mask_collapse_dilate(r0[..., None], pcfg.margin)
-        d2, c = plate_hip.fill(f, d, keep, occ, src)
-        c = c.cpu().numpy()
-        filled[s:e], left[s:e] = c[:, 0], c[:, 1]
-        steady[-1] = int(st.sum().item())
-        idx = np.nonzero(c[:, 0])[0]
-        if len(idx):
+        if plan == "canvas":
+            new, d2, c, steady[-1] = _fill_on_canvas(frames_rgb[s:e], d, track_t, track, cbox, pcfg)
+            left[s:e] = np.where(track[:, 3] == 1, c[:, 1], left[s:e])
+        else:
+            new, d2, c, steady[-1] = _fill_on_crop(frames_rgb[s:e], d, box, pcfg)
+            left[s:e] = c[:, 1]
+        filled[s:e] = c[:, 0]
+        for i, fr in new.items():
+            frames[s + i] = fr
+        if d2 is not None:
             if dil is dil_t:
                 dil = dil_t.clone()
-            dil[s:e, y0:y1, x0:x1] = d2
-            got = f[torch.from_numpy(idx).to(f.device)].cpu().numpy()
-            for j, i in enumerate(idx):
-                fr = np.array(frames_rgb[s + i], copy=True)
-                fr[y0:y1, x0:x1] = got[j]
-                frames[s + i] = fr
+            dil[(slice(s, e),) + at] = d2
     if acfg is not None and align_out is not None:
         align_out.append(PlateAlignReport(*(tuple(v) for v in arep), segs))
     return frames, dil, PlateFillReport(filled, left, tuple(steady), tuple(skipped), segs, cuts)
@@ -349,11 +362,10 @@ def region_plans(dil_t, H0, W0, feather_px, cfg):
 
 
 def run_clip(frames_rgb, dil_t, propainer_frames, rcfg, stages, prog, dev, feather_px=3, keep_unmasked_original=True,
-             compat_reference_early_return=False, tone=None, tone_out=None, grain=None, grain_out=None, frame0=0, blend=None, blend_out=None, flicker=None, flicker_out=None,
-             flicker_align=None, flicker_align_out=None):
+             compat_reference_early_return=False, **seam):
     """One clip after the dilation: the windows rcfg asks for (none without it, or where the planner falls back to the full frame), run_windows,
-    finish.  The whole call without spans=, and each span's call with it.  tone / tone_out / grain / grain_out / frame0 / blend / blend_out / flicker / flicker_out /
-    flicker_align / flicker_align_out: finish's."""
+    finish.  The whole call without spans=, and each span's call with it.  seam = finish's stage keywords, handed on as they come: a call
+    without them reaches finish with none."""
     H0, W0 = frames_rgb[0].shape[:2]
     if rcfg is None:
         plans = []
@@ -363,14 +375,7 @@ def run_clip(frames_rgb, dil_t, propainer_frames, rcfg, stages, prog, dev, feath
         plan = roi_plan.plan_roi(hip.mask_bbox(dil_t).cpu().numpy(), H0, W0, feather_px, rcfg)
         plans = [] if plan is None else [plan]
     outs = run_windows(frames_rgb, list(dil_t.cpu().numpy()), propainer_frames, plans, stages, prog)
-    more = {} if grain is None else dict(grain=grain, grain_out=grain_out, frame0=frame0)       # passed only when grain matching is on
-    if blend is not None:                                                                        # likewise
-        more.update(blend=blend, blend_out=blend_out)
-    if flicker is not None:                                                                      # likewise
-        more.update(flicker=flicker, flicker_out=flicker_out)
-    if flicker_align is not None:                                                                # likewise
-        more.update(flicker_align=flicker_align, flicker_align_out=flicker_align_out)
-    return finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return, tone, tone_out, **more)
+    return finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return, **seam)
 
 
 def run_windows(frames_rgb, dil, propainer_frames, plans, stages, prog):
@@ -406,6 +411,22 @@ def _on_device(res, n, dev, fn):
     return res
 
 
+def _zeros(*tail, dtype=np.float64):
+    """An "empty" field of a per-window, per-frame report: (K, T) -> zeros [K,T,*tail]."""
+    return lambda K, T: np.zeros((K, T) + tail, dtype)
+
+
+def _merged(report, empty, parts, spans, T, K):
+    """The report of a call over T frames from its clips' reports: parts[i] (what finish appended) covers the frames spans[i] = (a, b); at least
+    K windows; empty = one constructor (K, T) -> array per field, for the frames and windows no part covers."""
+    K = max([len(p.n) for p in parts] + [K])
+    rep = report(*(field(K, T) for field in empty))
+    for part, (a, b) in zip(parts, spans):
+        for whole, piece in zip(rep, part):
+            whole[:len(piece), a:b] = piece
+    return rep
+
+
 class ToneMatchReport(NamedTuple):
     """What seam tone matching applied, per window k and frame t (K = 1 for the full frame): the pixels of the frame's own ring, the gain and offset
     per channel, and the RMS of original - model and of original - (gain model + offset) over that ring (tonematch.ToneFit, stacked).  Frames
@@ -420,12 +441,7 @@ class ToneMatchReport(NamedTuple):
 def tone_report(parts, spans, T, K=1):
     """The report of a call over T frames from its clips' reports: parts[i] (finish's tone_out) covers the frames spans[i] = (a, b); at least K
     windows."""
-    K = max([len(p.n) for p in parts] + [K])
-    rep = ToneMatchReport(np.zeros((K, T), np.int64), np.ones((K, T, 3)), np.zeros((K, T, 3)), np.zeros((K, T, 3)), np.zeros((K, T, 3)))
-    for part, (a, b) in zip(parts, spans):
-        for whole, piece in zip(rep, part):
-            whole[:len(piece), a:b] = piece
-    return rep
+    return _merged(ToneMatchReport, (_zeros(dtype=np.int64), lambda K, T: np.ones((K, T, 3)), _zeros(3), _zeros(3), _zeros(3)), parts, spans, T, K)
 
 
 class GrainMatchReport(NamedTuple):
@@ -442,13 +458,7 @@ class GrainMatchReport(NamedTuple):
 def grain_report(parts, spans, T, K=1):
     """The report of a call over T frames from its clips' reports: parts[i] (finish's grain_out) covers the frames spans[i] = (a, b); at least K
     windows."""
-    K = max([len(p.n) for p in parts] + [K])
-    shape = (K, T, 3, grainmatch.BANDS)
-    rep = GrainMatchReport(np.zeros(shape, np.int64), np.zeros(shape), np.zeros(shape), np.zeros(shape))
-    for part, (a, b) in zip(parts, spans):
-        for whole, piece in zip(rep, part):
-            whole[:len(piece), a:b] = piece
-    return rep
+    return _merged(GrainMatchReport, (_zeros(3, grainmatch.BANDS, dtype=np.int64),) + (_zeros(3, grainmatch.BANDS),) * 3, parts, spans, T, K)
 
 
 class SeamBlendReport(NamedTuple):
@@ -466,12 +476,7 @@ class SeamBlendReport(NamedTuple):
 def seam_blend_report(parts, spans, T, K=1):
     """The report of a call over T frames from its clips' reports: parts[i] (finish's blend_out) covers the frames spans[i] = (a, b); at least K
     windows."""
-    K = max([len(p.n) for p in parts] + [K])
-    rep = SeamBlendReport(np.zeros((K, T), np.int64), np.zeros((K, T, 3)), np.zeros((K, T), np.int64), np.zeros((K, T, 3)), np.zeros((K, T, 3)))
-    for part, (a, b) in zip(parts, spans):
-        for whole, piece in zip(rep, part):
-            whole[:len(piece), a:b] = piece
-    return rep
+    return _merged(SeamBlendReport, (_zeros(dtype=np.int64), _zeros(3), _zeros(dtype=np.int64), _zeros(3), _zeros(3)), parts, spans, T, K)
 
 
 class DeflickerReport(NamedTuple):
@@ -492,13 +497,7 @@ class DeflickerReport(NamedTuple):
 def deflicker_report(parts, spans, T, K=1):
     """The report of a call over T frames from its clips' reports: parts[i] (finish's flicker_out) covers the frames spans[i] = (a, b); at least K
     windows."""
-    K = max([len(p.n) for p in parts] + [K])
-    half = lambda: (np.zeros((K, T), np.int64), np.zeros((K, T), np.int64), np.zeros((K, T)), np.zeros((K, T, 3)))
-    rep = DeflickerReport(*half(), *half())
-    for part, (a, b) in zip(parts, spans):
-        for whole, piece in zip(rep, part):
-            whole[:len(piece), a:b] = piece
-    return rep
+    return _merged(DeflickerReport, (_zeros(dtype=np.int64), _zeros(dtype=np.int64), _zeros(), _zeros(3)) * 2, parts, spans, T, K)
 
 
 class DeflickerAlignReport(NamedTuple):
@@ -525,27 +524,28 @@ def deflicker_align_report(parts, spans):
 
 def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return=False, tone=None, tone_out=None,
            grain=None, grain_out=None, frame0=0, blend=None, blend_out=None, flicker=None, flicker_out=None, flicker_align=None, flicker_align_out=None):
-    """The model's frames into frames of the original size.  No plan (reference :69-112): resize when the model ran at another size, feathered
-    composite with the originals when keep_unmasked_original, in place in outs[0].  The reference returns from inside its loop (:114) so only
-    frame 0 is post-processed; the evident intent (all frames) is the default here, compat_reference_early_return=True reproduces the quirk.
-    With plans: each window's frames into the originals (resize to the window, paste, feathered composite: roi_paste_composite once per window,
-    the output of window k the original of window k + 1: two buffers, one upload, one download).  Exact because the windows are disjoint: inside
-    window k the mask holds only region k's pixels and no other window has touched the bytes.  keep_unmasked_original=False: the plain paste.
-    tone (a tonematch.ToneMatchConfig): per window -- the full frame is the window (0, 0, H0, W0) -- ring_stats of the model's
-    pixels against the running buffer (inside window k still the original bytes), the [T,16] sums to the host, tonematch.fit and tables, the
-    [T,3,256] tables to the device, paste_lut_composite in place of the paste; with keep_unmasked_original=False every pasted pixel goes through
-    the table.  The clip's ToneMatchReport is appended to tone_out.  Without tone nothing here changes.
-    grain (a grainmatch.GrainMatchConfig): per window, after tone's table (the identity table without tone): ring_grain_stats of
-    the looked-up pixels against the running buffer, the [T,36] sums to the host, grainmatch.fit and tables, the [T,3,256] amplitudes to the
-    device, paste_grain_composite in place of the paste, its noise keyed on the frame's index in the call, frame0 + its index in this clip;
-    with keep_unmasked_original=False every pasted pixel gets grain.  The clip's GrainMatchReport is appended to grain_out.  Without grain
-    nothing here changes, and the tone-only path still calls paste_lut_composite.
-    blend (a seamblend.SeamBlendConfig): per window, after tone's table (the identity table without tone; with blend the tone
-    stage fits the offset alone, gain 1, whatever tone.mode says: a shift that varies round the ring misleads a gain): blend_hip.solve of the
-    looked-up pixels against the running buffer gives the membrane, over groups of frames (seamblend.groups) that share one scratch buffer;
-    paste_blend_composite in place of the paste adds it after the table and before the grain (zero amplitudes without grain, whose statistic
-    stays on the tabled pixel without the membrane).  The clip's SeamBlendReport is appended to blend_out.  Without blend nothing here
-    changes and no vvb_ symbol is resolved.
+    """The model's frames into frames of the original size.  No plan and no stage (full_frame; reference :69-112): resize when the model ran
+    at another size, feathered composite with the originals when keep_unmasked_original, in place in outs[0].  The reference returns from
+    inside its loop (:114) so only frame 0 is post-processed; the evident intent (all frames) is the default here,
+    compat_reference_early_return=True reproduces the quirk.
+    Otherwise ONE loop over the windows (pasted) -- with plans theirs, without the full frame as the window (0, 0, H0, W0) -- the output of
+    window k the original of window k + 1: two buffers, one upload, one download.  Exact because the windows are disjoint: inside window k the
+    mask holds only region k's pixels and no other window has touched the bytes.  Per window: its model frames to the device (model_px), the
+    stages that are on, then the ONE fused call that resizes to the window, pastes and composites (keep_unmasked_original=False: the plain
+    paste, and every pasted pixel goes through the stages).  A stage that is off calls nothing and resolves no symbol of its binding; each
+    stage's per-clip report is appended to its *_out list.
+      tone (a tonematch.ToneMatchConfig): ring_stats of the model's pixels against the running buffer (inside window k still
+        the original bytes), the [T,16] sums to the host, tonematch.fit and tables, the [T,3,256] tables to the device.  Without tone the
+        later stages get the identity table.
+      grain (a grainmatch.GrainMatchConfig): ring_grain_stats of the looked-up pixels, the [T,36] sums to the host,
+        grainmatch.fit and tables, the [T,3,256] amplitudes to the device; the noise is keyed on the frame's index in the call, frame0 + its
+        index in this clip.
+      blend (a seamblend.SeamBlendConfig): blend_hip.solve of the looked-up pixels against the running buffer gives the
+        membrane, over groups of frames (seamblend.groups) that share one scratch buffer; it is added after the table and before the grain
+        (zero amplitudes without grain, whose statistic stays on the tabled pixel without the membrane).  In front of it the tone stage fits
+        the offset alone, gain 1, whatever tone.mode says: a shift that varies round the ring misleads a gain.
+    The window ends in hip.roi_paste_composite (no stage), tone_hip.paste_lut_composite (tone alone), grain_hip.paste_grain_composite (grain,
+    with or without tone) or, with blend, blend_hip.paste_blend_composite group by group.
     flicker (a deflicker.DeflickerConfig): per window, where its model frames are uploaded (model_px): the window's pixels
     materialised at the window's size (flicker_hip.window_pixels), filtered along time inside this clip call (flicker_hip.hold; rules:
     include/vvflicker.h); everything above then reads the filtered [n,h,w,3] patch at equal size with the same offsets, so tone, membrane and
@@ -602,127 +602,75 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
             out = hip.feather_composite(out.contiguous(), up(frames_rgb).contiguous(), dil_t[idx].contiguous(), float(feather_px))   # :77-112
         return out
 
-    def windows(idx, up):
-        bufs = [up(frames_rgb).contiguous()]
-        bufs.append(torch.empty_like(bufs[0]))
-        mask = dil_t[idx].contiguous()
-        for k, (plan, o) in enumerate(zip(plans, outs)):
-            offs = torch.from_numpy(np.ascontiguousarray(plan.offsets[idx])).to(dev)
-            hip.roi_paste_composite(model_px(o, idx, up, plan.offsets, plan.size, offs, mask), bufs[k % 2], mask, offs, *plan.size, float(feather_px if keep_unmasked_original else -1.0),
-                                    out=bufs[(k + 1) % 2])
-        return bufs[len(plans) % 2]
+    seam = tone is not None or grain is not None or blend is not None
+    feather = float(feather_px if keep_unmasked_original else -1.0)
 
-    def toned(idx, up):
-        wins = [(p.offsets, p.size) for p in plans] or [(np.zeros((T, 2), np.int32), (H0, W0))]
-        bufs = [up(frames_rgb).contiguous()]
-        bufs.append(torch.empty_like(bufs[0]))
-        mask = dil_t[idx].contiguous()
-        fits = []
-        for k, ((offsets, (h, w)), o) in enumerate(zip(wins, outs)):
-            offs = torch.from_numpy(np.ascontiguousarray(offsets[idx], np.int32)).to(dev)
-            patch = model_px(o, idx, up, offsets, (h, w), offs, mask)
-            sums = np.zeros((T, tonematch.NSUM), np.int64)
-            sums[idx] = tone_hip.ring_stats(patch, bufs[k % 2], mask, offs, h, w, tone.ring).cpu().numpy()
-            fits.append(tonematch.fit(sums, tone))
-            lut = torch.from_numpy(tonematch.tables(fits[-1].gain[idx], fits[-1].offset[idx])).to(dev)
-            tone_hip.paste_lut_composite(patch, bufs[k % 2], mask, offs, lut, h, w, float(feather_px if keep_unmasked_original else -1.0),
-                                         out=bufs[(k + 1) % 2])
-        if tone_out is not None:
-            tone_out.append(ToneMatchReport(*(np.stack(f) for f in zip(*fits))))
-        return bufs[len(wins) % 2]
-
-    def grained(idx, up):
-        wins = [(p.offsets, p.size) for p in plans] or [(np.zeros((T, 2), np.int32), (H0, W0))]
-        bufs = [up(frames_rgb).contiguous()]
-        bufs.append(torch.empty_like(bufs[0]))
-        mask = dil_t[idx].contiguous()
-        ids = torch.from_numpy(np.asarray(idx, np.int32) + np.int32(frame0)).to(dev)
-        ident = np.broadcast_to(np.arange(256, dtype=np.uint8), (len(idx), 3, 256))
-        tfits, gfits = [], []
-        for k, ((offsets, (h, w)), o) in enumerate(zip(wins, outs)):
-            offs = torch.from_numpy(np.ascontiguousarray(offsets[idx], np.int32)).to(dev)
-            patch = model_px(o, idx, up, offsets, (h, w), offs, mask)
-            lut = ident
-            if tone is not None:
-                sums = np.zeros((T, tonematch.NSUM), np.int64)
-                sums[idx] = tone_hip.ring_stats(patch, bufs[k % 2], mask, offs, h, w, tone.ring).cpu().numpy()
-                tfits.append(tonematch.fit(sums, tone))
-                lut = tonematch.tables(tfits[-1].gain[idx], tfits[-1].offset[idx])
-            lut = torch.from_numpy(np.ascontiguousarray(lut)).to(dev)
-            sums = np.zeros((T, grainmatch.NSUM), np.int64)
-            sums[idx] = grain_hip.ring_grain_stats(patch, bufs[k % 2], mask, offs, lut, h, w, grain.ring, grain.flat).cpu().numpy()
-            gfits.append(grainmatch.fit(sums, grain))
-            amp = torch.from_numpy(grainmatch.tables(gfits[-1].sigma_added[idx])).to(dev)
-            grain_hip.paste_grain_composite(patch, bufs[k % 2], mask, offs, lut, amp, ids, grain.seed, grainmatch.MODES.index(grain.mode), h, w,
-                                            float(feather_px if keep_unmasked_original else -1.0), out=bufs[(k + 1) % 2])
-        if tone is not None and tone_out is not None:
-            tone_out.append(ToneMatchReport(*(np.stack(f) for f in zip(*tfits))))
-        if grain_out is not None:
-            grain_out.append(GrainMatchReport(*(np.stack(f) for f in zip(*gfits))))
-        return bufs[len(wins) % 2]
-
-    def blended(idx, up):
-        wins = [(p.offsets, p.size) for p in plans] or [(np.zeros((T, 2), np.int32), (H0, W0))]
-        bufs = [up(frames_rgb).contiguous()]
-        bufs.append(torch.empty_like(bufs[0]))
-        mask = dil_t[idx].contiguous()
+    def pasted(idx, up):
         n = len(idx)
-        ids = torch.from_numpy(np.asarray(idx, np.int32) + np.int32(frame0)).to(dev)
-        ident = np.broadcast_to(np.arange(256, dtype=np.uint8), (n, 3, 256))
-        amp = torch.zeros((n, 3, 256), dtype=torch.uint8, device=dev)
-        seed, mode = (0, 0) if grain is None else (grain.seed, grainmatch.MODES.index(grain.mode))
-        feather = float(feather_px if keep_unmasked_original else -1.0)
-        tfits, gfits, bfits = [], [], []
+        wins = [(p.offsets, p.size) for p in plans] or [(np.zeros((T, 2), np.int32), (H0, W0))]
+        bufs = [up(frames_rgb).contiguous()]
+        bufs.append(torch.empty_like(bufs[0]))
+        mask = dil_t[idx].contiguous()
+        if grain is not None or blend is not None:
+            ids = torch.from_numpy(np.asarray(idx, np.int32) + np.int32(frame0)).to(dev)
+            ident = np.broadcast_to(np.arange(256, dtype=np.uint8), (n, 3, 256))
+            seed, mode = (0, 0) if grain is None else (grain.seed, grainmatch.MODES.index(grain.mode))
+            if grain is None:
+                amp = torch.zeros((n, 3, 256), dtype=torch.uint8, device=dev)
         # a shift that varies round the ring is correlated with the picture there and misleads a fitted gain; what varies is the membrane's to
         # take, so in front of it the tone stage fits the offset alone
-        tone_cfg = None if tone is None else dataclasses.replace(tone, mode="offset")
+        tone_cfg = tone if tone is None or blend is None else dataclasses.replace(tone, mode="offset")
+        tfits, gfits, bfits = [], [], []
+
+        def whole(rows):        # [n,nsum] of this rank's frames -> [T,nsum], zero rows for the others
+            sums = np.zeros((T, rows.shape[1]), np.int64)
+            sums[idx] = rows
+            return sums
+
         for k, ((offsets, (h, w)), o) in enumerate(zip(wins, outs)):
+            src, dst = bufs[k % 2], bufs[(k + 1) % 2]
             offs = torch.from_numpy(np.ascontiguousarray(offsets[idx], np.int32)).to(dev)
             patch = model_px(o, idx, up, offsets, (h, w), offs, mask)
-            lut = ident
             if tone is not None:
-                sums = np.zeros((T, tonematch.NSUM), np.int64)
-                sums[idx] = tone_hip.ring_stats(patch, bufs[k % 2], mask, offs, h, w, tone.ring).cpu().numpy()
-                tfits.append(tonematch.fit(sums, tone_cfg))
-                lut = tonematch.tables(tfits[-1].gain[idx], tfits[-1].offset[idx])
-            lut = torch.from_numpy(np.ascontiguousarray(lut)).to(dev)
+                tfits.append(tonematch.fit(whole(tone_hip.ring_stats(patch, src, mask, offs, h, w, tone.ring).cpu().numpy()), tone_cfg))
+                lut = torch.from_numpy(tonematch.tables(tfits[-1].gain[idx], tfits[-1].offset[idx])).to(dev)
+            elif seam:
+                lut = torch.from_numpy(np.ascontiguousarray(ident)).to(dev)
             if grain is not None:
-                sums = np.zeros((T, grainmatch.NSUM), np.int64)
-                sums[idx] = grain_hip.ring_grain_stats(patch, bufs[k % 2], mask, offs, lut, h, w, grain.ring, grain.flat).cpu().numpy()
-                gfits.append(grainmatch.fit(sums, grain))
+                rows = grain_hip.ring_grain_stats(patch, src, mask, offs, lut, h, w, grain.ring, grain.flat).cpu().numpy()
+                gfits.append(grainmatch.fit(whole(rows), grain))
                 amp = torch.from_numpy(grainmatch.tables(gfits[-1].sigma_added[idx])).to(dev)
-            sums = np.zeros((T, seamblend.NSUM), np.int64)
-            scratch = None
-            for a, b in seamblend.groups(n, h, w):
-                if scratch is None:
-                    scratch = torch.empty((seamblend.scratch_bytes(b - a, h, w),), dtype=torch.uint8, device=dev)
-                field, _, part = blend_hip.solve(patch[a:b], bufs[k % 2][a:b], mask[a:b], offs[a:b], lut[a:b], h, w, blend.ring, blend.presmooth,
-                                                 blend.sweeps, blend.max_shift, scratch=scratch)
-                sums[idx[a:b]] = part.cpu().numpy()
-                blend_hip.paste_blend_composite(patch[a:b], bufs[k % 2][a:b], mask[a:b], offs[a:b], lut[a:b], field, blend.strength_q8, amp[a:b],
-                                                ids[a:b], seed, mode, h, w, feather, out=bufs[(k + 1) % 2][a:b])
-            bfits.append(seamblend.fit(sums))
-        if tone is not None and tone_out is not None:
-            tone_out.append(ToneMatchReport(*(np.stack(f) for f in zip(*tfits))))
-        if grain is not None and grain_out is not None:
-            grain_out.append(GrainMatchReport(*(np.stack(f) for f in zip(*gfits))))
-        if blend_out is not None:
-            blend_out.append(SeamBlendReport(*(np.stack(f) for f in zip(*bfits))))
+            if blend is not None:
+                rows, scratch = [], None
+                for a, b in seamblend.groups(n, h, w):
+                    if scratch is None:
+                        scratch = torch.empty((seamblend.scratch_bytes(b - a, h, w),), dtype=torch.uint8, device=dev)
+                    field, _, part = blend_hip.solve(patch[a:b], src[a:b], mask[a:b], offs[a:b], lut[a:b], h, w, blend.ring, blend.presmooth,
+                                                     blend.sweeps, blend.max_shift, scratch=scratch)
+                    rows.append(part.cpu().numpy())
+                    blend_hip.paste_blend_composite(patch[a:b], src[a:b], mask[a:b], offs[a:b], lut[a:b], field, blend.strength_q8, amp[a:b],
+                                                    ids[a:b], seed, mode, h, w, feather, out=dst[a:b])
+                bfits.append(seamblend.fit(whole(np.concatenate(rows))))
+            elif grain is not None:
+                grain_hip.paste_grain_composite(patch, src, mask, offs, lut, amp, ids, seed, mode, h, w, feather, out=dst)
+            elif tone is not None:
+                tone_hip.paste_lut_composite(patch, src, mask, offs, lut, h, w, feather, out=dst)
+            else:
+                hip.roi_paste_composite(patch, src, mask, offs, h, w, feather, out=dst)
+        for fits, out, report in ((tfits, tone_out, ToneMatchReport), (gfits, grain_out, GrainMatchReport), (bfits, blend_out, SeamBlendReport)):
+            if fits and out is not None:
+                out.append(report(*(np.stack(f) for f in zip(*fits))))
         return bufs[len(wins) % 2]
 
-    if tone is not None or grain is not None or blend is not None:
-        done = [len(o) if o is not None else 0 for o in (tone_out, grain_out, blend_out)]
-        res = _on_device(outs[0] if not plans else list(outs[0]), T, dev, blended if blend is not None else toned if grain is None else grained)
-        if blend is not None and blend_out is not None and len(blend_out) == done[2]:     # this rank holds no frame of the clip: zero rows
-            blend_out.append(seam_blend_report([], [], T, K=max(len(plans), 1)))
-        if tone is not None and tone_out is not None and len(tone_out) == done[0]:        # this rank holds no frame of the clip: identity rows
-            tone_out.append(tone_report([], [], T, K=max(len(plans), 1)))
-        if grain is not None and grain_out is not None and len(grain_out) == done[1]:     # likewise: zero rows
-            grain_out.append(grain_report([], [], T, K=max(len(plans), 1)))
-    elif not plans:
-        res = _on_device(outs[0], 1 if compat_reference_early_return else len(outs[0]), dev, full_frame)
+    if seam or plans:
+        asked = [(out, empty, len(out)) for cfg, out, empty in ((tone, tone_out, tone_report), (grain, grain_out, grain_report),
+                                                                 (blend, blend_out, seam_blend_report)) if cfg is not None and out is not None]
+        res = _on_device(list(outs[0]) if plans else outs[0], T, dev, pasted)
+        for out, empty, before in asked:
+            if len(out) == before:                                                        # this rank holds no frame of the clip: identity / zero rows
+                out.append(empty([], [], T, K=max(len(plans), 1)))
     else:
-        res = _on_device(list(outs[0]), len(outs[0]), dev, windows)
+        res = _on_device(outs[0], 1 if compat_reference_early_return else T, dev, full_frame)
     if flicker is not None and flicker_out is not None:
         if fsums:
             flicker_out.append(DeflickerReport(*(np.stack(f) for f in zip(*(deflicker.fit(s) for s in fsums)))))

@@ -31,22 +31,12 @@ def lib():
     """hip.lib() with the signatures of vvmask.h applied (once)."""
     global _lib
     if _lib is None:
-        dll = hip.lib()
-        for name, (restype, argtypes) in SIGNATURES.items():
-            if not hasattr(dll, name):
-                raise RuntimeError(f"libvvhip.so does not export {name}")
-            fn = getattr(dll, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        v = dll.vvm_abi_version()
-        if v != ABI_VERSION:
-            raise RuntimeError(f"libvvhip.so mask clean-up ABI version {v} != {ABI_VERSION}")
-        _lib = dll
+        _lib = hip.bind(hip.lib(), SIGNATURES, "vvm_abi_version", ABI_VERSION, "mask clean-up")
     return _lib
 
 
 def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc}): {lib().vvm_last_error().decode()}")
+    hip.check(rc, what, lib, "vvm_last_error")
 
 
 def _need_mask(mask2d, what):

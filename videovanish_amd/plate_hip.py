@@ -32,22 +32,12 @@ def lib():
     """hip.lib() with the signatures of vvplate.h applied (once)."""
     global _lib
     if _lib is None:
-        dll = hip.lib()
-        for name, (restype, argtypes) in SIGNATURES.items():
-            if not hasattr(dll, name):
-                raise RuntimeError(f"libvvhip.so does not export {name}")
-            fn = getattr(dll, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        v = dll.vvp_abi_version()
-        if v != ABI_VERSION:
-            raise RuntimeError(f"libvvhip.so clean-plate fill ABI version {v} != {ABI_VERSION}")
-        _lib = dll
+        _lib = hip.bind(hip.lib(), SIGNATURES, "vvp_abi_version", ABI_VERSION, "clean-plate fill")
     return _lib
 
 
 def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc}): {lib().vvp_last_error().decode()}")
+    hip.check(rc, what, lib, "vvp_last_error")
 
 
 def _need_clip(what, frames, *masks, occ=None, tile=TILE):

@@ -29,22 +29,12 @@ def lib():
     """hip.lib() with the signatures of vvtone.h applied (once)."""
     global _lib
     if _lib is None:
-        dll = hip.lib()
-        for name, (restype, argtypes) in SIGNATURES.items():
-            if not hasattr(dll, name):
-                raise RuntimeError(f"libvvhip.so does not export {name}")
-            fn = getattr(dll, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        v = dll.vvt_abi_version()
-        if v != ABI_VERSION:
-            raise RuntimeError(f"libvvhip.so tone matching ABI version {v} != {ABI_VERSION}")
-        _lib = dll
+        _lib = hip.bind(hip.lib(), SIGNATURES, "vvt_abi_version", ABI_VERSION, "tone matching")
     return _lib
 
 
 def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc}): {lib().vvt_last_error().decode()}")
+    hip.check(rc, what, lib, "vvt_last_error")
 
 
 def _need_window(what, patch, orig, mask2d, offsets):
