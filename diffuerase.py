@@ -14,6 +14,8 @@ also configure(seam_blend=...) and $VV_SEAM_BLEND), plate_fill (clean-plate fill
 filled from the nearest such frame and leave the mask before anything plans or runs the model: videovanish_amd/platefill.py; also
 configure(plate_fill=...) and $VV_PLATE_FILL), plate_align (clean-plate alignment: with plate_fill, one integer translation per frame is
 tracked first, so that the fill follows a panning camera: videovanish_amd/platealign.py; also configure(plate_align=...) and $VV_PLATE_ALIGN),
+plate_grain (clean-plate grain: with plate_fill, a filled pixel takes its bytes from a few usable frames in turn, not from the nearest alone, so
+that the grain inside the fill moves: videovanish_amd/plategrain.py; also configure(plate_grain=...) and $VV_PLATE_GRAIN),
 deflicker (inpaint deflicker: the model's pixels are filtered along time before every other seam stage reads them, each the mean of its temporal
 neighbours within a tolerance, so that the patch stops shimmering while moving edges stay as they are: videovanish_amd/deflicker.py; also
 configure(deflicker=...) and $VV_DEFLICKER), deflicker_align (aligned inpaint deflicker: with deflicker, one integer translation per frame is
@@ -33,7 +35,7 @@ import torch
 
 from videovanish_amd import hip, infill
 from videovanish_amd import deflicker as deflicker_settings
-from videovanish_amd import deflickeralign, grainmatch, maskclean, platealign, platefill, seamblend, tonematch
+from videovanish_amd import deflickeralign, grainmatch, maskclean, platealign, platefill, plategrain, seamblend, tonematch
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
 from videovanish_amd.config import RunConfig
@@ -57,6 +59,7 @@ last_grain_match = None # the infill.GrainMatchReport of the last run_infill_on_
 last_seam_blend = None  # the infill.SeamBlendReport of the last run_infill_on_frames call; None when the stage did not run
 last_plate_fill = None  # the infill.PlateFillReport of the last run_infill_on_frames call; None when the stage did not run
 last_plate_align = None # the infill.PlateAlignReport of the last run_infill_on_frames call; None when the tracker did not run
+last_plate_grain = None # the infill.PlateGrainReport of the last run_infill_on_frames call; None when the rotation was not asked for
 last_deflicker = None   # the infill.DeflickerReport of the last run_infill_on_frames call; None when the stage did not run
 last_deflicker_align = None  # the infill.DeflickerAlignReport of the last run_infill_on_frames call; None when the tracker did not run
 
@@ -84,12 +87,17 @@ OPTIONS = (
     Option("deflicker", deflicker_settings, "VV_DEFLICKER", "inpaint deflicker", "on|radius=2,tol=12"),
     Option("deflicker_align", deflickeralign, "VV_DEFLICKER_ALIGN", "aligned inpaint deflicker", "on|levels=4,radius=4,min_overlap=25,max_residual=12"),
 )
-_OPTION = {o.name: o for o in OPTIONS}
+# OPTIONS holds the ten rows tests/test_cli_cpu.py names one by one; a row added since stands here, and everything below walks ALL_OPTIONS
+MORE_OPTIONS = (
+    Option("plate_grain", plategrain, "VV_PLATE_GRAIN", "clean-plate grain", "on|depth=4,reach=8"),
+)
+ALL_OPTIONS = OPTIONS + MORE_OPTIONS
+_OPTION = {o.name: o for o in ALL_OPTIONS}
 _configured = {}        # configure(<option>=...): the value for calls that do not pass that keyword themselves, as given
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
-              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, plate_align=None, plate_fill=None):
+              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, plate_grain=None, plate_align=None, plate_fill=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -118,13 +126,15 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     clean-plate fill for calls that do not pass plate_fill=.
     plate_align = None / "on" / "levels=4,radius=4,min_overlap=25,max_residual=12" (any subset) / a platealign.PlateAlignConfig: clean-plate
     alignment for calls that do not pass plate_align=.
+    plate_grain = None / "on" / "depth=4,reach=8" (any subset) / a plategrain.PlateGrainConfig: clean-plate grain for calls that do not pass
+    plate_grain=.
     deflicker = None / "on" / "radius=2,tol=12" (any subset) / a deflicker.DeflickerConfig: inpaint deflicker for calls that do not pass
     deflicker=.
     deflicker_align = None / "on" / "levels=4,radius=4,min_overlap=25,max_residual=12" (any subset) / a platealign.PlateAlignConfig: aligned
     inpaint deflicker for calls that do not pass deflicker_align=."""
     global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded
     given = locals()
-    for o in reversed(OPTIONS):             # validated now, kept as given: configure(roi="off") means the full frame whatever $VV_ROI says
+    for o in reversed(ALL_OPTIONS):         # validated now, kept as given: configure(roi="off") means the full frame whatever $VV_ROI says
         o.settings.as_config(given[o.name])
     if reference_defaults:
         import dataclasses
@@ -133,7 +143,7 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     _run_config, _dist, _gather, last_ckpt = run, dist, gather, None
     _prior_stages, propainter = dict(prior or {}), None
     _weights, _loaded = weights, None
-    _configured.update({o.name: given[o.name] for o in OPTIONS})
+    _configured.update({o.name: given[o.name] for o in ALL_OPTIONS})
 
 
 def _resolve_weights(ckpt):
@@ -224,6 +234,13 @@ def plate_align_config(plate_align=None):
     return _setting("plate_align", plate_align)
 
 
+def plate_grain_config(plate_grain=None):
+    """The clean-plate grain setting a call runs with: its own plate_grain= argument, else configure(plate_grain=...), else $VV_PLATE_GRAIN
+    (on | off | depth=N,reach=N).  None = every filled pixel takes the nearest usable frame.  plate_grain="off" (or False) asks for that whatever
+    configure() or the environment say."""
+    return _setting("plate_grain", plate_grain)
+
+
 def deflicker_config(deflicker=None):
     """The inpaint deflicker setting a call runs with: its own deflicker= argument, else configure(deflicker=...), else $VV_DEFLICKER (on | off |
     radius=N,tol=N).  None = no deflicker.  deflicker="off" (or False) asks for none whatever configure() or the environment say."""
@@ -240,7 +257,7 @@ def deflicker_align_config(deflicker_align=None):
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
-                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, plate_align=None, plate_fill=None):
+                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, plate_grain=None, plate_align=None, plate_fill=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -288,6 +305,12 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     over a panning shot, is filled from the frames that show its background at another place.  A frame the tracker loses gives no sample
     and keeps its mask; a locked-off clip gives the bytes of the call without it.  What it found is kept in last_plate_align.  Without an
     effective plate_fill it is a ValueError.
+    plate_grain (clean-plate grain, opt-in, needs plate_fill): "on" / "depth=4,reach=8" / a videovanish_amd.plategrain.PlateGrainConfig makes
+    every filled pixel take its bytes from up to `depth` usable frames in turn (the nearest one and the next ones on its side, none more than
+    `reach` frames from it; rule: include/vvplategrain.h), so that the grain inside the fill moves as it does around it.  Every filled byte is
+    still a byte of the clip at that place; the pixels filled, the masks and last_plate_fill are those of plate_fill alone, on the crop and
+    on plate_align's canvas alike, and depth=1 gives its bytes.  What it rotated is kept in last_plate_grain.  Without an effective
+    plate_fill it is a ValueError.
     deflicker (inpaint deflicker, opt-in): "on" / "radius=2,tol=12" / a videovanish_amd.deflicker.DeflickerConfig filters the model's pixels
     along time where they reach the device, for the full frame and for every roi window, inside each span (infill.finish; rules:
     include/vvflicker.h): every pixel becomes the rounded mean of those of its neighbours at most `radius` frames away that lie within `tol`
@@ -302,26 +325,29 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     under a pan or tilt too.  A frame the tracker loses takes no sample and gives none; after a cut inside a clip call every later frame is
     lost and stays unfiltered: spans="cuts" (or "masked-cuts") splits the call there.  A locked-off clip gives the bytes of deflicker alone.
     What it found is kept in last_deflicker_align.  Without an effective deflicker it is a ValueError."""
-    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_deflicker, last_deflicker_align
+    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_plate_grain, last_deflicker, last_deflicker_align
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
     ccfg = mask_clean_config(mask_clean)
     tcfg = tone_match_config(tone_match)
     gcfg = grain_match_config(grain_match)
     fcfg = deflicker_config(deflicker)
-    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_deflicker = last_deflicker_align = None
+    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_plate_grain = last_deflicker = last_deflicker_align = None
     pcfg = plate_fill_config(plate_fill)
     acfg = plate_align_config(plate_align)
     if acfg is not None and pcfg is None:
         raise ValueError("plate_align= (clean-plate alignment) needs plate_fill= (clean-plate fill)")
+    lcfg = plate_grain_config(plate_grain)
+    if lcfg is not None and pcfg is None:
+        raise ValueError("plate_grain= (clean-plate grain) needs plate_fill= (clean-plate fill)")
     facfg = deflicker_align_config(deflicker_align)
     if facfg is not None and fcfg is None:
         raise ValueError("deflicker_align= (aligned inpaint deflicker) needs deflicker= (inpaint deflicker)")
     bcfg = seam_blend_config(seam_blend, feather_px if keep_unmasked_original else None)
     if compat_reference_early_return:
         on = dict(roi=rcfg, spans=scfg, mask_clean=ccfg, tone_match=tcfg, grain_match=gcfg, seam_blend=bcfg, plate_fill=pcfg, plate_align=acfg,
-                  deflicker=fcfg, deflicker_align=facfg)
-        for o in OPTIONS:
+                  plate_grain=lcfg, deflicker=fcfg, deflicker_align=facfg)
+        for o in ALL_OPTIONS:
             if on[o.name] is not None:
                 raise ValueError(f"{o.name}= ({o.phrase}) cannot be combined with compat_reference_early_return=True")
 
@@ -340,12 +366,16 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         if scfg is not None and scfg.cuts == "auto":        # the detector has run: the span plan takes its cuts
             import dataclasses
             scfg = dataclasses.replace(scfg, cuts=tuple(found))
-        if acfg is None:
-            frames_rgb, dil_t, last_plate_fill = infill.plate_fill(frames_rgb, dil_t, pcfg, found)      # downstream these are the originals
-        else:
-            found_align = []
-            frames_rgb, dil_t, last_plate_fill = infill.plate_fill(frames_rgb, dil_t, pcfg, found, acfg=acfg, align_out=found_align)
+        more, found_align, found_grain = {}, [], []
+        if acfg is not None:
+            more.update(acfg=acfg, align_out=found_align)
+        if lcfg is not None:
+            more.update(gcfg=lcfg, grain_out=found_grain)
+        frames_rgb, dil_t, last_plate_fill = infill.plate_fill(frames_rgb, dil_t, pcfg, found, **more)      # downstream these are the originals
+        if acfg is not None:
             last_plate_align = found_align[0]
+        if lcfg is not None:
+            last_plate_grain = found_grain[0]
 
     stages = infill.Stages(lambda: _load_model(dev, ckpt), _load_prior, _run_prior,
                            lambda f, d, prior, p: _run_model(f, d, prior, max_img_size, p, num_inference_steps, scheduler))
@@ -483,6 +513,10 @@ def main():
                     help="With --plate-fill: track one integer translation per frame first (a coarse-to-fine search over `levels` pyramid levels, "
                          "+-`radius` at the coarsest; a frame whose best match differs by more than `max_residual` levels on average is left out) "
                          "and fill on the canvas in which the background stands still.  For slow pans and tilts.  Prints one line with what it tracked.")
+    ap.add_argument("--plate-grain", type=_setting_arg("plate_grain"), default=None, metavar=_OPTION["plate_grain"].metavar,
+                    help="With --plate-fill: a filled pixel takes its bytes from up to `depth` usable frames in turn (the nearest and the next ones on "
+                         "its side, at most `reach` frames from it), not from the nearest alone, so that the grain inside the fill moves as it does "
+                         "around it.  Prints one line with what it rotated.")
     ap.add_argument("--deflicker", type=_setting_arg("deflicker"), default=None, metavar=_OPTION["deflicker"].metavar,
                     help="Inpaint deflicker before the seam stages: every pixel of the model's output becomes the mean of those of its neighbours at "
                          "most `radius` frames away (on: 2) that lie within `tol` levels of it (on: 12), so the patch stops shimmering; what changes by "
@@ -508,7 +542,7 @@ def main():
         assert (H0 == Hp and W0 == Wp), "prior and color video are diffrent sizes"
     assert (H0 == Hm and W0 == Wm), "mask and color video are diffrent sizes"
     # pass roi= / spans= / cuts= / a stage only when asked for: a default call stays the reference's call
-    kw = {name: getattr(args, name) for name in [o.name for o in OPTIONS] + ["cuts"] if getattr(args, name) is not None}
+    kw = {name: getattr(args, name) for name in [o.name for o in ALL_OPTIONS] + ["cuts"] if getattr(args, name) is not None}
     out_frames = run_infill_on_frames(frames, mask_frames, propainer_frames=prior_frames, **kw)
     if args.mask_clean is not None and last_mask_clean is not None:
         r = last_mask_clean
@@ -539,6 +573,10 @@ def main():
         n = len(r.segments)
         print(f"plate align: {int(ok.sum())} of {ok.size} frames tracked, pan extent {max(span[:n])} x {max(span[n:])} px, "
               f"{sum(p == 'canvas' for p in r.path)} of {n} segments filled on a canvas")
+    if args.plate_grain is not None and last_plate_grain is not None:
+        r = last_plate_grain
+        filled, rotated = int(r.filled.sum()), int(r.rotated.sum())
+        print(f"plate grain: {filled} px filled, {100.0 * rotated / max(filled, 1):.1f} % of them from another frame than the nearest")
     if args.deflicker is not None and last_deflicker is not None:
         r = last_deflicker
         touched = (r.changed > 0).any(axis=0)

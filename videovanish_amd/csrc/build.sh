@@ -24,7 +24,7 @@ pids=(); objs=()
 compile() {   # compile <src> <obj> [extra flags]
   local src=$1 obj=$OBJ/$2.o stale=; shift 2
   objs+=($obj)
-  for dep in $src.hip *.h ../../include/vvhip.h ../../include/vvspans.h ../../include/vvmask.h ../../include/vvtone.h ../../include/vvgrain.h ../../include/vvblend.h ../../include/vvplate.h ../../include/vvalign.h ../../include/vvflicker.h ../../include/vvflickalign.h $HERE/build.sh; do
+  for dep in $src.hip *.h ../../include/vvhip.h ../../include/vvspans.h ../../include/vvmask.h ../../include/vvtone.h ../../include/vvgrain.h ../../include/vvblend.h ../../include/vvplate.h ../../include/vvplategrain.h ../../include/vvalign.h ../../include/vvflicker.h ../../include/vvflickalign.h $HERE/build.sh; do
     if [ ! -f $obj ] || [ $dep -nt $obj ]; then stale=1; fi
   done
   if [ -n "$stale" ]; then

@@ -4,6 +4,8 @@
 //   vvp_stats     per pixel along time: n, S1, S2 over the sample frames, the steady flag
 //   vvp_sources   per pixel along time, forward then backward: the nearest usable sample frame of every masked frame, and R0
 //   vvp_fill      per frame: the gather frames[src] -> frames where the pixel left the mask, dil', the counts
+//   vvl_sources   vvp_sources' walk that also keeps the last / next 8 usable frames and writes the live sources (include/vvplategrain.h, DESIGN.md
+//                 section 20): the frame each masked frame takes its bytes from when the sources rotate; vvp_fill is handed that plane
 // A streaming family over [T][H][W][3] u8.  A thread owns P adjacent pixels of one row and walks the frames (VEC: P = 4, one 12-byte image load
 // and one 4-byte mask load per frame, lane after lane contiguous; W % 4 == 0, tile % 4 == 0 and aligned bases, checked by the launcher; else
 // P = 1 with byte loads).  A thread whose pixels lie in a tile without a mask pixel ends before any load: the launcher has set its outputs.
@@ -12,6 +14,8 @@
 // The counts go registers -> wave reduction -> LDS -> one pair of 64-bit global atomics per block, as in vv_tone.hip: integer adds in any order.
 #include "vv_common.h"
 #include "../../include/vvplate.h"
+#include "../../include/vvplategrain.h"
+#include <type_traits>
 
 namespace {
 
@@ -97,17 +101,62 @@ __global__ __launch_bounds__(PB) void stats_kernel(const uint8_t* __restrict__ f
     }
 }
 
-template <bool VEC>
+// vvl_sources' part of the sources walk (include/vvplategrain.h): the last / next 8 usable frames of a pixel, newest first, as 16-bit fields of two
+// 64-bit words (field i of `lo` for i < 4, of `hi` above; NONE = no such frame).  Pushed with shifts and selected with a shift by the field's
+// number, so that nothing is indexed dynamically and nothing goes to scratch.
+struct NoLive {};
+struct LiveArgs { uint16_t* live; int depth, reach; };
+struct Hist { u64 lo, hi; };
+__device__ __forceinline__ void hist_push(Hist& h, unsigned t) {
+    h.hi = (h.hi << 16) | (h.lo >> 48);
+    h.lo = (h.lo << 16) | t;
+}
+__device__ __forceinline__ unsigned hist_at(const Hist& h, unsigned i) { return (unsigned)((i < 4 ? h.lo : h.hi) >> (16 * (i & 3))) & 0xffffu; }
+// t mod 1 .. t mod 8 in the 4-bit fields of one word: t is the same for every lane, so these are scalar operations
+__device__ __forceinline__ unsigned mods_of(unsigned t) {
+    unsigned w = 0;
+#pragma unroll
+    for (unsigned m = 2; m <= 8; ++m) w |= (t % m) << (4 * (m - 1));
+    return w;
+}
+// the live source of frame t from the candidates of one side: m = the kept prefix, field t mod m.  A candidate c is kept when
+// base <= c <= base + span (one unsigned compare); NONE lies above every such range.  gap = max_gap, or 65535 for "any".
+__device__ __forceinline__ unsigned live_pick(const Hist& h, int base, int span, unsigned mods, int depth) {
+    unsigned m = 1;
+#pragma unroll
+    for (int i = 1; i < VVL_MAX_DEPTH; ++i)
+        m += (i < depth && (unsigned)((int)hist_at(h, i) - base) <= (unsigned)span) ? 1u : 0u;      // holds for a prefix, so the sum is its length
+    return hist_at(h, (mods >> (4 * (m - 1))) & 15u);
+}
+// before t: the candidates descend from c_0; within reach of it and within gap of t is c >= max(c_0 - reach, t - gap)
+__device__ __forceinline__ unsigned live_before(const Hist& h, int t, unsigned mods, int depth, int reach, int gap) {
+    const int c0 = (int)hist_at(h, 0);
+    const int lo = max(max(c0 - reach, t - gap), 0);
+    return live_pick(h, lo, c0 - lo, mods, depth);
+}
+// after t: they ascend from c_0, up to min(c_0 + reach, t + gap), and never reach NONE
+__device__ __forceinline__ unsigned live_after(const Hist& h, int t, unsigned mods, int depth, int reach, int gap) {
+    const int c0 = (int)hist_at(h, 0);
+    const int hi = min(min(c0 + reach, t + gap), (int)NONE - 1);
+    return live_pick(h, c0, hi - c0, mods, depth);
+}
+
+// L = NoLive: vvp_sources.  L = LiveArgs: vvl_sources, the same walk that also keeps the candidates and writes the live sources.
+template <bool VEC, class L>
 __global__ __launch_bounds__(PB) void sources_kernel(const uint8_t* __restrict__ frames, const uint8_t* __restrict__ dil, const uint8_t* __restrict__ ns,
                                                      const uint8_t* __restrict__ occ, const uint8_t* __restrict__ steady, const int* __restrict__ n_in,
                                                      const int* __restrict__ s1_in, int T, int64_t N, int64_t units, int W, int tile, int tw, int tol,
-                                                     int outlier, int max_gap, uint16_t* src, uint8_t* __restrict__ r0) {
+                                                     int outlier, int max_gap, uint16_t* src, uint8_t* __restrict__ r0, L lv) {
     constexpr int P = VEC ? 4 : 1;
+    constexpr bool LIVE = std::is_same<L, LiveArgs>::value;
     const int64_t u = (int64_t)blockIdx.x * PB + threadIdx.x;
     if (u >= units || !occupied(occ, u * P, W, tile, tw)) return;
     const int64_t i0 = u * P;
     int n[P], s1[3 * P], lim[P];
     unsigned prev[P];
+    Hist hist[LIVE ? P : 1];
+    int gap = 0;
+    if constexpr (LIVE) gap = max_gap > 0 ? max_gap : VVP_MAX_T;
 #pragma unroll
     for (int p = 0; p < P; ++p) {
         n[p] = steady[i0 + p] ? n_in[i0 + p] : 0;                            // n = 0: not steady, no frame is usable
@@ -115,6 +164,7 @@ __global__ __launch_bounds__(PB) void sources_kernel(const uint8_t* __restrict__
 #pragma unroll
         for (int c = 0; c < 3; ++c) s1[3 * p + c] = s1_in[(i0 + p) * 3 + c];
         prev[p] = NONE;
+        if constexpr (LIVE) hist[p].lo = hist[p].hi = ~0ull;
     }
     // forward: src[t] = the last usable frame before a masked frame t; at an unmasked frame t itself where it is usable
     for (int t = 0; t < T; ++t) {
@@ -138,14 +188,29 @@ __global__ __launch_bounds__(PB) void sources_kernel(const uint8_t* __restrict__
             }
             if (us) prev[p] = (unsigned)t;
             o[p] = ((md >> (8 * p)) & 255u) ? prev[p] : (us ? (unsigned)t : NONE);
+            if constexpr (LIVE)
+                if (us) hist_push(hist[p], (unsigned)t);
         }
         if constexpr (VEC) *reinterpret_cast<uint2*>(src + at) = make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));
         else src[at] = (uint16_t)o[0];
+        if constexpr (LIVE) {
+            if (md) {                                                       // the before side's pick; an unmasked frame keeps the launcher's NONE
+                const unsigned mods = mods_of((unsigned)t);
+                unsigned ol[P];
+#pragma unroll
+                for (int p = 0; p < P; ++p) ol[p] = ((md >> (8 * p)) & 255u) ? live_before(hist[p], t, mods, lv.depth, lv.reach, gap) : NONE;
+                if constexpr (VEC) *reinterpret_cast<uint2*>(lv.live + at) = make_uint2(ol[0] | (ol[1] << 16), ol[2] | (ol[3] << 16));
+                else lv.live[at] = (uint16_t)ol[0];
+            }
+        }
     }
-    // backward: the first usable frame after t against the one before it; this thread wrote every src it reads
+    // backward: the first usable frame after t against the one before it; this thread wrote every src (and live) it reads
     int next[P];
 #pragma unroll
-    for (int p = 0; p < P; ++p) next[p] = -1;
+    for (int p = 0; p < P; ++p) {
+        next[p] = -1;
+        if constexpr (LIVE) hist[p].lo = hist[p].hi = ~0ull;
+    }
     for (int t = T - 1; t >= 0; --t) {
         const int64_t at = (int64_t)t * N + i0;
         const unsigned md = load_mask<VEC>(dil + at);
@@ -156,16 +221,20 @@ __global__ __launch_bounds__(PB) void sources_kernel(const uint8_t* __restrict__
         } else {
             sv[0] = src[at];
         }
-        unsigned o[P], r = 0;
+        unsigned o[P], r = 0, after = 0;                                    // after: bit p = the after side wins at pixel p
 #pragma unroll
         for (int p = 0; p < P; ++p) {
             if (((md >> (8 * p)) & 255u) == 0) {
-                if (sv[p] == (unsigned)t) next[p] = t;
+                if (sv[p] == (unsigned)t) {
+                    next[p] = t;
+                    if constexpr (LIVE) hist_push(hist[p], (unsigned)t);
+                }
                 o[p] = NONE;
             } else {
                 const int pv = sv[p] == NONE ? -1 : (int)sv[p];
                 int best = pv;
                 if (next[p] >= 0 && (pv < 0 || next[p] - t < t - pv)) best = next[p];      // a tie goes to the earlier frame
+                if (best != pv) after |= 1u << p;
                 if (best >= 0 && max_gap > 0 && (best > t ? best - t : t - best) > max_gap) best = -1;
                 o[p] = best < 0 ? NONE : (unsigned)best;
                 if (best < 0) r |= 255u << (8 * p);
@@ -177,6 +246,25 @@ __global__ __launch_bounds__(PB) void sources_kernel(const uint8_t* __restrict__
         } else {
             src[at] = (uint16_t)o[0];
             r0[at] = (uint8_t)r;
+        }
+        if constexpr (LIVE) {
+            if (after | r) {                                                // else the forward walk's picks stand
+                const unsigned mods = mods_of((unsigned)t);
+                unsigned ol[P];
+                if constexpr (VEC) {
+                    const uint2 q = *reinterpret_cast<const uint2*>(lv.live + at);
+                    ol[0] = q.x & 0xffffu; ol[1] = q.x >> 16; ol[2] = q.y & 0xffffu; ol[3] = q.y >> 16;
+                } else {
+                    ol[0] = lv.live[at];
+                }
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    if ((r >> (8 * p)) & 255u) ol[p] = NONE;
+                    else if ((after >> p) & 1u) ol[p] = live_after(hist[p], t, mods, lv.depth, lv.reach, gap);
+                }
+                if constexpr (VEC) *reinterpret_cast<uint2*>(lv.live + at) = make_uint2(ol[0] | (ol[1] << 16), ol[2] | (ol[3] << 16));
+                else lv.live[at] = (uint16_t)ol[0];
+            }
         }
     }
 }
@@ -263,29 +351,58 @@ extern "C" int vvp_stats(const uint8_t* frames, const uint8_t* notsample, const 
     return VV_OK;
 }
 
-extern "C" int vvp_sources(const uint8_t* frames, const uint8_t* dil, const uint8_t* notsample, const uint8_t* occ, const uint8_t* steady, const int32_t* n,
-                           const int32_t* s1, int T, int H, int W, int tile, int tol, int outlier, int max_gap, uint16_t* src, uint8_t* r0, void* stream) {
+// vvp_sources and, with lv, vvl_sources: one set of checks and one launch
+template <class L>
+int launch_sources(const char* who, const uint8_t* frames, const uint8_t* dil, const uint8_t* notsample, const uint8_t* occ, const uint8_t* steady,
+                   const int32_t* n, const int32_t* s1, int T, int H, int W, int tile, int tol, int outlier, int max_gap, uint16_t* src, uint8_t* r0, L lv,
+                   void* stream) {
+    constexpr bool LIVE = std::is_same<L, LiveArgs>::value;
     if (!frames || !dil || !notsample || !steady || !n || !s1 || !src || !r0 || tol < 0 || outlier < 0 || max_gap < 0)
-        VV_FAIL(VV_E_ARG, "vvp_sources: bad args (no null pointer but occ, tol >= 0, outlier >= 0, max_gap >= 0)");
-    const int rc = bad_clip("vvp_sources", T, H, W, occ, tile);
+        VV_FAIL(VV_E_ARG, "%s: bad args (no null pointer but occ, tol >= 0, outlier >= 0, max_gap >= 0)", who);
+    if constexpr (LIVE)
+        if (!lv.live || lv.depth < 1 || lv.reach < 1) VV_FAIL(VV_E_ARG, "%s: bad args (live is not null, depth >= 1, reach >= 1)", who);
+    const int rc = bad_clip(who, T, H, W, occ, tile);
     if (rc != VV_OK) return rc;
     if (tol > VVP_MAX_TOL || outlier > VVP_MAX_OUTLIER || max_gap > VVP_MAX_GAP)
-        VV_FAIL(VV_E_UNSUPPORTED, "vvp_sources: tol <= %d, outlier <= %d and max_gap <= %d are supported, not tol %d, outlier %d, max_gap %d", VVP_MAX_TOL,
+        VV_FAIL(VV_E_UNSUPPORTED, "%s: tol <= %d, outlier <= %d and max_gap <= %d are supported, not tol %d, outlier %d, max_gap %d", who, VVP_MAX_TOL,
                 VVP_MAX_OUTLIER, VVP_MAX_GAP, tol, outlier, max_gap);
+    if constexpr (LIVE)
+        if (lv.depth > VVL_MAX_DEPTH || lv.reach > VVL_MAX_REACH)
+            VV_FAIL(VV_E_UNSUPPORTED, "%s: depth <= %d and reach <= %d are supported, not depth %d, reach %d", who, VVL_MAX_DEPTH, VVL_MAX_REACH, lv.depth,
+                    lv.reach);
     hipStream_t st = (hipStream_t)stream;
     const int64_t N = (int64_t)H * W;
     if (occ && (hipMemsetAsync(src, 0xff, (size_t)T * N * 2, st) != hipSuccess || hipMemsetAsync(r0, 0, (size_t)T * N, st) != hipSuccess))
-        VV_FAIL(VV_E_LAUNCH, "vvp_sources: memset failed");
+        VV_FAIL(VV_E_LAUNCH, "%s: memset failed", who);
+    bool vec = vec_ok(W, occ, tile) && aligned(frames, 4) && aligned(dil, 4) && aligned(notsample, 4) && aligned(src, 8) && aligned(r0, 4);
+    if constexpr (LIVE) {
+        if (hipMemsetAsync(lv.live, 0xff, (size_t)T * N * 2, st) != hipSuccess) VV_FAIL(VV_E_LAUNCH, "%s: memset failed", who);      // the kernel writes masked frames only
+        vec = vec && aligned(lv.live, 8);
+    }
     const int tw = occ ? (W + tile - 1) / tile : 0;
-    const bool vec = vec_ok(W, occ, tile) && aligned(frames, 4) && aligned(dil, 4) && aligned(notsample, 4) && aligned(src, 8) && aligned(r0, 4);
     const int64_t units = vec ? N / 4 : N;
     const dim3 grid((unsigned)((units + PB - 1) / PB));
-    if (vec) hipLaunchKernelGGL(sources_kernel<true>, grid, dim3(PB), 0, st, frames, dil, notsample, occ, steady, n, s1, T, N, units, W, tile, tw, tol, outlier,
-                                max_gap, src, r0);
-    else hipLaunchKernelGGL(sources_kernel<false>, grid, dim3(PB), 0, st, frames, dil, notsample, occ, steady, n, s1, T, N, units, W, tile, tw, tol, outlier,
-                            max_gap, src, r0);
-    VV_CHECK_LAUNCH("vvp_sources");
+    if (vec) hipLaunchKernelGGL((sources_kernel<true, L>), grid, dim3(PB), 0, st, frames, dil, notsample, occ, steady, n, s1, T, N, units, W, tile, tw, tol,
+                                outlier, max_gap, src, r0, lv);
+    else hipLaunchKernelGGL((sources_kernel<false, L>), grid, dim3(PB), 0, st, frames, dil, notsample, occ, steady, n, s1, T, N, units, W, tile, tw, tol,
+                            outlier, max_gap, src, r0, lv);
+    VV_CHECK_LAUNCH(who);
     return VV_OK;
+}
+
+extern "C" int vvp_sources(const uint8_t* frames, const uint8_t* dil, const uint8_t* notsample, const uint8_t* occ, const uint8_t* steady, const int32_t* n,
+                           const int32_t* s1, int T, int H, int W, int tile, int tol, int outlier, int max_gap, uint16_t* src, uint8_t* r0, void* stream) {
+    return launch_sources("vvp_sources", frames, dil, notsample, occ, steady, n, s1, T, H, W, tile, tol, outlier, max_gap, src, r0, NoLive{}, stream);
+}
+
+extern "C" int vvl_abi_version(void) { return VVL_ABI_VERSION; }
+extern "C" const char* vvl_last_error(void) { return vv_last_error(); }
+
+extern "C" int vvl_sources(const uint8_t* frames, const uint8_t* dil, const uint8_t* notsample, const uint8_t* occ, const uint8_t* steady, const int32_t* n,
+                           const int32_t* s1, int T, int H, int W, int tile, int tol, int outlier, int max_gap, int depth, int reach, uint16_t* src,
+                           uint16_t* live, uint8_t* r0, void* stream) {
+    return launch_sources("vvl_sources", frames, dil, notsample, occ, steady, n, s1, T, H, W, tile, tol, outlier, max_gap, src, r0,
+                          LiveArgs{live, depth, reach}, stream);
 }
 
 extern "C" int vvp_fill(uint8_t* frames, const uint8_t* dil, const uint8_t* keep, const uint8_t* occ, const uint16_t* src, int T, int H, int W, int tile,

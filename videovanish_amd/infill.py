@@ -13,7 +13,7 @@ from typing import Callable, NamedTuple
 import numpy as np
 import torch
 
-from . import align_hip, blend_hip, deflicker, deflickeralign, flickalign_hip, flicker_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platealign, platefill, seamblend, spans_hip, tone_hip, tonematch
+from . import align_hip, blend_hip, deflicker, deflickeralign, flickalign_hip, flicker_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platealign, platefill, plategrain_hip, seamblend, spans_hip, tone_hip, tonematch
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -85,6 +85,14 @@ class PlateFillReport(NamedTuple):
     cuts: tuple
 
 
+class PlateGrainReport(NamedTuple):
+    """What plate_fill(gcfg=) rotated: per frame (int64 [T] each) the filled pixels whose bytes come from another frame than the nearest usable
+    one, and the pixels filled (PlateFillReport.filled); the segments."""
+    rotated: np.ndarray
+    filled: np.ndarray
+    segments: tuple
+
+
 class PlateAlignReport(NamedTuple):
     """What the tracker of plate_fill(acfg=) found, per segment of `segments` (a tuple each): off [T,2] int32 = the frame's (x, y) on the canvas,
     key [T] = the key frame it was tracked against, tracked [T] bool, residual [T] = the mean absolute luma difference of its level-0 best
@@ -135,27 +143,34 @@ def _plan_alignment(frames_rgb, d_seg, boxes, pcfg, acfg):
     return track_t, track, cbox, "fallback" if platealign.canvas_bytes(T, cbox) > pcfg.max_bytes else "canvas"
 
 
-def _fill_device(f, d, invalid, pcfg):
+def _fill_device(f, d, invalid, pcfg, gcfg=None):
     """The fill itself on resident frames f [T,h,w,3] (written in place) and their masks d [T,h,w]: the tile occupancy, the sample frames from
     time_bridge_grow(., 0, guard) (and not where `invalid` is set: the canvas places no tracked frame covers), stats, sources, the margin
-    (mask_collapse_dilate of the unfilled remainder), fill -> (d' on the device, counts [T,2] = (filled, left) on the host, steady pixels)."""
+    (mask_collapse_dilate of the unfilled remainder), fill -> (d' on the device, counts [T,3] = (filled, left, rotated) on the host, steady
+    pixels).  gcfg = a plategrain.PlateGrainConfig with depth > 1: vvl_sources in place of vvp_sources, and the fill gathers from its live
+    sources (include/vvplategrain.h); rotated = the filled pixels whose live source is not the nearest one, 0 otherwise."""
     occ = hip.mask_tile_union(d, plate_hip.TILE)
     notsample = d if pcfg.guard == 0 else mask_hip.time_bridge_grow(d, 0, pcfg.guard)[0]
     if invalid is not None:
         notsample = torch.bitwise_or(notsample, invalid)
     st, n, s1 = plate_hip.stats(f, notsample, occ, pcfg.min_samples, pcfg.tol)
-    src, r0 = plate_hip.sources(f, d, notsample, occ, st, n, s1, pcfg.tol, pcfg.outlier, pcfg.max_gap)
+    rotate = gcfg is not None and gcfg.depth > 1
+    if rotate:
+        near, src, r0 = plategrain_hip.sources(f, d, notsample, occ, st, n, s1, pcfg.tol, pcfg.outlier, pcfg.max_gap, gcfg.depth, gcfg.reach)
+    else:
+        src, r0 = plate_hip.sources(f, d, notsample, occ, st, n, s1, pcfg.tol, pcfg.outlier, pcfg.max_gap)
     keep = r0 if pcfg.margin == 0 else hip.mask_collapse_dilate(r0[..., None], pcfg.margin)
     d2, c = plate_hip.fill(f, d, keep, occ, src)
-    return d2, c.cpu().numpy(), int(st.sum().item())
+    rotated = ((d != 0) & (d2 == 0) & (src != near)).flatten(1).sum(1, keepdim=True) if rotate else torch.zeros_like(c[:, :1])
+    return d2, torch.cat([c, rotated.to(c.dtype)], 1).cpu().numpy(), int(st.sum().item())
 
 
-def _fill_on_crop(frames_rgb, d, box, pcfg):
+def _fill_on_crop(frames_rgb, d, box, pcfg, gcfg=None):
     """One segment filled on the crop `box` of its frames (d = the masks' crop, contiguous): the crop crosses to the device, the crops of the
     frames that got a fill come back into copies of those frames -> what _fill_on_canvas returns, dil' being the crop's."""
     y0, x0, y1, x1 = box
     f = torch.from_numpy(np.stack([fr[y0:y1, x0:x1] for fr in frames_rgb])).to(d.device)
-    d2, c, steady = _fill_device(f, d, None, pcfg)
+    d2, c, steady = _fill_device(f, d, None, pcfg, gcfg)
     idx = np.nonzero(c[:, 0])[0]
     new = {}
     if not len(idx):
@@ -167,9 +182,9 @@ def _fill_on_crop(frames_rgb, d, box, pcfg):
     return new, d2, c, steady
 
 
-def _fill_on_canvas(frames_rgb, d_seg, track_t, track, box, pcfg):
+def _fill_on_canvas(frames_rgb, d_seg, track_t, track, box, pcfg, gcfg=None):
     """Steps 5 and 7 - 9 of DESIGN.md §17 for one segment: the canvas from per-frame slices, the unchanged vvp_ kernels on it, the filled pixels
-    back into copies of their frames -> ({frame index: new frame}, dil' [T,H,W] or None when nothing was filled, counts [T,2], steady)."""
+    back into copies of their frames -> ({frame index: new frame}, dil' [T,H,W] or None when nothing was filled, counts [T,3] as _fill_device's, steady)."""
     T, H, W = d_seg.shape
     y0, x0, y1, x1 = box
     canvas = np.zeros((T, y1 - y0, x1 - x0, 3), np.uint8)
@@ -179,7 +194,7 @@ def _fill_on_canvas(frames_rgb, d_seg, track_t, track, box, pcfg):
             canvas[t][sl[0]] = frames_rgb[t][sl[1]]
     f = torch.from_numpy(canvas).to(d_seg.device)
     d, invalid = align_hip.place_masks(d_seg, track_t, box)
-    d2, c, steady = _fill_device(f, d, invalid, pcfg)
+    d2, c, steady = _fill_device(f, d, invalid, pcfg, gcfg)
     idx = np.nonzero(c[:, 0])[0]
     new = {}
     if not len(idx):
@@ -195,7 +210,7 @@ def _fill_on_canvas(frames_rgb, d_seg, track_t, track, box, pcfg):
     return new, align_hip.unplace_mask(d2, d_seg, track_t, box), c, steady
 
 
-def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None):
+def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None, gcfg=None, grain_out=None):
     """The clean-plate fill (platefill.py; rules: include/vvplate.h): frames_rgb = the T host frames [H,W,3] u8, dil_t = the masks
     [T,H,W] u8 on the device, pcfg = a PlateFillConfig, cuts = frame indices or None (one segment).  Per segment of spans.segments: the crop of
     the union box of its masks (platefill.crop_box) crosses to the device and is filled in place (_fill_device); only the crops of frames
@@ -207,13 +222,17 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None):
     (one integer translation per frame against a held key); a segment whose frames all sit at offset zero takes the path above as it is, any
     other is filled on the canvas in which its background stands still (the same vvp_ kernels; the places no tracked frame covers are no
     samples), unless the canvas exceeds max_bytes: then the path above runs and the segment is flagged "fallback".  An untracked frame gives
-    no sample, gets no fill and keeps its mask.  align_out = a list that receives the call's PlateAlignReport."""
+    no sample, gets no fill and keeps its mask.  align_out = a list that receives the call's PlateAlignReport.
+    gcfg = a plategrain.PlateGrainConfig (rule: include/vvplategrain.h), opt-in: wherever a segment is filled, on the crop or on
+    the canvas, every masked frame takes its bytes from up to `depth` usable frames in turn, not from the nearest alone, so that the grain inside
+    the fill moves; the pixels filled, dil' and the PlateFillReport are those without it, and depth = 1 is the call without it.  grain_out = a
+    list that receives the call's PlateGrainReport."""
     T, H, W = dil_t.shape
     cuts = tuple(int(c) for c in (cuts or ()))
     segs = tuple(span_planner.segments(T, cuts))
     boxes = hip.mask_bbox(dil_t).cpu().numpy()
     frames, dil = list(frames_rgb), dil_t
-    filled, left = np.zeros(T, np.int64), np.zeros(T, np.int64)
+    filled, left, rotated = np.zeros(T, np.int64), np.zeros(T, np.int64), np.zeros(T, np.int64)
     steady, skipped = [], []
     arep = [[] for _ in range(6)]
     for s, e in segs:
@@ -241,12 +260,12 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None):
         if plan not in ("crop", "canvas"):
             continue
         if plan == "canvas":
-            new, d2, c, steady[-1] = _fill_on_canvas(frames_rgb[s:e], d, track_t, track, cbox, pcfg)
+            new, d2, c, steady[-1] = _fill_on_canvas(frames_rgb[s:e], d, track_t, track, cbox, pcfg, gcfg)
             left[s:e] = np.where(track[:, 3] == 1, c[:, 1], left[s:e])
         else:
-            new, d2, c, steady[-1] = _fill_on_crop(frames_rgb[s:e], d, box, pcfg)
+            new, d2, c, steady[-1] = _fill_on_crop(frames_rgb[s:e], d, box, pcfg, gcfg)
             left[s:e] = c[:, 1]
-        filled[s:e] = c[:, 0]
+        filled[s:e], rotated[s:e] = c[:, 0], c[:, 2]
         for i, fr in new.items():
             frames[s + i] = fr
         if d2 is not None:
@@ -255,6 +274,8 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None):
             dil[(slice(s, e),) + at] = d2
     if acfg is not None and align_out is not None:
         align_out.append(PlateAlignReport(*(tuple(v) for v in arep), segs))
+    if gcfg is not None and grain_out is not None:
+        grain_out.append(PlateGrainReport(rotated, filled.copy(), segs))
     return frames, dil, PlateFillReport(filled, left, tuple(steady), tuple(skipped), segs, cuts)
 
 
