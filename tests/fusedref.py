@@ -91,13 +91,14 @@ def _ln(t, g, b, merged_without_between=False):
 def gn_affine(gn, x, Fr, HW, pool):
     """(a, b) [Fr, C] float64 of the GroupNorm gn = (gamma, beta, groups, eps) over x [Fr * HW, C]: statistics per frame, or pooled over the clip"""
     gamma, beta, groups, eps = gn
-    xd = x.double().view(Fr, HW, groups, C // groups)
+    Cc = x.shape[-1]          # (any width: tests/modref.py shares this)
+    xd = x.double().view(Fr, HW, groups, Cc // groups)
     dims = (0, 1, 3) if pool else (1, 3)
     mean = xd.mean(dim=dims, keepdim=True).expand(Fr, 1, groups, 1)
     var = xd.var(dim=dims, unbiased=False, keepdim=True).expand(Fr, 1, groups, 1)
     rstd = torch.rsqrt(var + eps)
-    a = rstd.expand(Fr, 1, groups, C // groups).reshape(Fr, C) * gamma.double()
-    b = beta.double() - mean.expand(Fr, 1, groups, C // groups).reshape(Fr, C) * a
+    a = rstd.expand(Fr, 1, groups, Cc // groups).reshape(Fr, Cc) * gamma.double()
+    b = beta.double() - mean.expand(Fr, 1, groups, Cc // groups).reshape(Fr, Cc) * a
     return a, b
 
 
