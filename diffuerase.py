@@ -16,6 +16,8 @@ configure(plate_fill=...) and $VV_PLATE_FILL), plate_align (clean-plate alignmen
 tracked first, so that the fill follows a panning camera: videovanish_amd/platealign.py; also configure(plate_align=...) and $VV_PLATE_ALIGN),
 plate_grain (clean-plate grain: with plate_fill, a filled pixel takes its bytes from a few usable frames in turn, not from the nearest alone, so
 that the grain inside the fill moves: videovanish_amd/plategrain.py; also configure(plate_grain=...) and $VV_PLATE_GRAIN),
+shadow_mask (shadow masking: unmasked pixels that look like the shot's clean background uniformly darkened and hang on to the mask join it,
+between the mask clean-up and the clean-plate fill: videovanish_amd/shadowmask.py; also configure(shadow_mask=...) and $VV_SHADOW_MASK),
 deflicker (inpaint deflicker: the model's pixels are filtered along time before every other seam stage reads them, each the mean of its temporal
 neighbours within a tolerance, so that the patch stops shimmering while moving edges stay as they are: videovanish_amd/deflicker.py; also
 configure(deflicker=...) and $VV_DEFLICKER), deflicker_align (aligned inpaint deflicker: with deflicker, one integer translation per frame is
@@ -35,7 +37,7 @@ import torch
 
 from videovanish_amd import hip, infill
 from videovanish_amd import deflicker as deflicker_settings
-from videovanish_amd import deflickeralign, grainmatch, maskclean, platealign, platefill, plategrain, seamblend, tonematch
+from videovanish_amd import deflickeralign, grainmatch, maskclean, platealign, platefill, plategrain, seamblend, shadowmask, tonematch
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
 from videovanish_amd.config import RunConfig
@@ -60,6 +62,7 @@ last_seam_blend = None  # the infill.SeamBlendReport of the last run_infill_on_f
 last_plate_fill = None  # the infill.PlateFillReport of the last run_infill_on_frames call; None when the stage did not run
 last_plate_align = None # the infill.PlateAlignReport of the last run_infill_on_frames call; None when the tracker did not run
 last_plate_grain = None # the infill.PlateGrainReport of the last run_infill_on_frames call; None when the rotation was not asked for
+last_shadow_mask = None # the infill.ShadowMaskReport of the last run_infill_on_frames call; None when the stage did not run
 last_deflicker = None   # the infill.DeflickerReport of the last run_infill_on_frames call; None when the stage did not run
 last_deflicker_align = None  # the infill.DeflickerAlignReport of the last run_infill_on_frames call; None when the tracker did not run
 
@@ -90,6 +93,7 @@ OPTIONS = (
 # OPTIONS holds the ten rows tests/test_cli_cpu.py names one by one; a row added since stands here, and everything below walks ALL_OPTIONS
 MORE_OPTIONS = (
     Option("plate_grain", plategrain, "VV_PLATE_GRAIN", "clean-plate grain", "on|depth=4,reach=8"),
+    Option("shadow_mask", shadowmask, "VV_SHADOW_MASK", "shadow masking", "on|guard=1,min_samples=4,tol=6,lo=30,hi=90,drop=12,chroma=20,floor=16,reach=32,min_area=16,grow=1"),
 )
 ALL_OPTIONS = OPTIONS + MORE_OPTIONS
 _OPTION = {o.name: o for o in ALL_OPTIONS}
@@ -97,7 +101,7 @@ _configured = {}        # configure(<option>=...): the value for calls that do n
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
-              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, plate_grain=None, plate_align=None, plate_fill=None):
+              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_grain=None, plate_align=None, plate_fill=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -128,6 +132,8 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     alignment for calls that do not pass plate_align=.
     plate_grain = None / "on" / "depth=4,reach=8" (any subset) / a plategrain.PlateGrainConfig: clean-plate grain for calls that do not pass
     plate_grain=.
+    shadow_mask = None / "on" / "guard=1,min_samples=4,tol=6,lo=30,hi=90,drop=12,chroma=20,floor=16,reach=32,min_area=16,grow=1,max_bytes=N" (any
+    subset) / a shadowmask.ShadowMaskConfig: shadow masking for calls that do not pass shadow_mask=.
     deflicker = None / "on" / "radius=2,tol=12" (any subset) / a deflicker.DeflickerConfig: inpaint deflicker for calls that do not pass
     deflicker=.
     deflicker_align = None / "on" / "levels=4,radius=4,min_overlap=25,max_residual=12" (any subset) / a platealign.PlateAlignConfig: aligned
@@ -241,6 +247,13 @@ def plate_grain_config(plate_grain=None):
     return _setting("plate_grain", plate_grain)
 
 
+def shadow_mask_config(shadow_mask=None):
+    """The shadow masking setting a call runs with: its own shadow_mask= argument, else configure(shadow_mask=...), else $VV_SHADOW_MASK (on | off |
+    guard=N,min_samples=N,tol=N,lo=N,hi=N,drop=N,chroma=N,floor=N,reach=N,min_area=N,grow=N,max_bytes=N).  None = the masks as they are.
+    shadow_mask="off" (or False) asks for that whatever configure() or the environment say."""
+    return _setting("shadow_mask", shadow_mask)
+
+
 def deflicker_config(deflicker=None):
     """The inpaint deflicker setting a call runs with: its own deflicker= argument, else configure(deflicker=...), else $VV_DEFLICKER (on | off |
     radius=N,tol=N).  None = no deflicker.  deflicker="off" (or False) asks for none whatever configure() or the environment say."""
@@ -257,7 +270,7 @@ def deflicker_align_config(deflicker_align=None):
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
-                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, plate_grain=None, plate_align=None, plate_fill=None):
+                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_grain=None, plate_align=None, plate_fill=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -311,6 +324,14 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     still a byte of the clip at that place; the pixels filled, the masks and last_plate_fill are those of plate_fill alone, on the crop and
     on plate_align's canvas alike, and depth=1 gives its bytes.  What it rotated is kept in last_plate_grain.  Without an effective
     plate_fill it is a ValueError.
+    shadow_mask (shadow masking, opt-in): "on" / "guard=1,min_samples=4,tol=6,lo=30,hi=90,drop=12,chroma=20,floor=16,reach=32,min_area=16,grow=1,
+    max_bytes=N" / a videovanish_amd.shadowmask.ShadowMaskConfig extends, after the mask clean-up and before the clean-plate fill, every frame's
+    mask over the cast shadow of what it covers (infill.shadow_mask; rules: include/vvshadow.h): per segment between the cuts of spans= / cuts=
+    and per pixel a clean background is taken from the unmasked frames that are not themselves darkened, the unmasked pixels that look like it
+    uniformly darkened are marked, and those that hang on to the frame's mask within `reach` steps join it, grown by `grow`.  Masks change,
+    never a frame byte; the larger masks replace the dilated ones for the clean-plate fill, the planners, the prior, the model and the
+    composite.  It needs neither plate_fill nor a locked-off camera: where the shot shows no steady background (a pan) nothing is added, and
+    the call's bytes are those of the call without it.  What it added is kept in last_shadow_mask.
     deflicker (inpaint deflicker, opt-in): "on" / "radius=2,tol=12" / a videovanish_amd.deflicker.DeflickerConfig filters the model's pixels
     along time where they reach the device, for the full frame and for every roi window, inside each span (infill.finish; rules:
     include/vvflicker.h): every pixel becomes the rounded mean of those of its neighbours at most `radius` frames away that lie within `tol`
@@ -325,14 +346,14 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     under a pan or tilt too.  A frame the tracker loses takes no sample and gives none; after a cut inside a clip call every later frame is
     lost and stays unfiltered: spans="cuts" (or "masked-cuts") splits the call there.  A locked-off clip gives the bytes of deflicker alone.
     What it found is kept in last_deflicker_align.  Without an effective deflicker it is a ValueError."""
-    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_plate_grain, last_deflicker, last_deflicker_align
+    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_plate_grain, last_shadow_mask, last_deflicker, last_deflicker_align
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
     ccfg = mask_clean_config(mask_clean)
     tcfg = tone_match_config(tone_match)
     gcfg = grain_match_config(grain_match)
     fcfg = deflicker_config(deflicker)
-    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_plate_grain = last_deflicker = last_deflicker_align = None
+    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_plate_grain = last_shadow_mask = last_deflicker = last_deflicker_align = None
     pcfg = plate_fill_config(plate_fill)
     acfg = plate_align_config(plate_align)
     if acfg is not None and pcfg is None:
@@ -340,13 +361,14 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     lcfg = plate_grain_config(plate_grain)
     if lcfg is not None and pcfg is None:
         raise ValueError("plate_grain= (clean-plate grain) needs plate_fill= (clean-plate fill)")
+    hcfg = shadow_mask_config(shadow_mask)
     facfg = deflicker_align_config(deflicker_align)
     if facfg is not None and fcfg is None:
         raise ValueError("deflicker_align= (aligned inpaint deflicker) needs deflicker= (inpaint deflicker)")
     bcfg = seam_blend_config(seam_blend, feather_px if keep_unmasked_original else None)
     if compat_reference_early_return:
         on = dict(roi=rcfg, spans=scfg, mask_clean=ccfg, tone_match=tcfg, grain_match=gcfg, seam_blend=bcfg, plate_fill=pcfg, plate_align=acfg,
-                  plate_grain=lcfg, deflicker=fcfg, deflicker_align=facfg)
+                  plate_grain=lcfg, shadow_mask=hcfg, deflicker=fcfg, deflicker_align=facfg)
         for o in ALL_OPTIONS:
             if on[o.name] is not None:
                 raise ValueError(f"{o.name}= ({o.phrase}) cannot be combined with compat_reference_early_return=True")
@@ -361,11 +383,14 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         if scfg is not None and scfg.cuts == "auto":        # the detector has run, on the despeckled masks: the span plan takes its cuts
             import dataclasses
             scfg = dataclasses.replace(scfg, cuts=last_mask_clean.cuts)
-    if pcfg is not None:
+    if hcfg is not None or pcfg is not None:
         found = None if scfg is None else infill.clip_cuts(frames_rgb, dil_t, scfg)
-        if scfg is not None and scfg.cuts == "auto":        # the detector has run: the span plan takes its cuts
+        if scfg is not None and scfg.cuts == "auto":        # the detector has run, once for both stages: the span plan takes its cuts
             import dataclasses
             scfg = dataclasses.replace(scfg, cuts=tuple(found))
+    if hcfg is not None:
+        dil_t, last_shadow_mask = infill.shadow_mask(frames_rgb, dil_t, hcfg, found)
+    if pcfg is not None:
         more, found_align, found_grain = {}, [], []
         if acfg is not None:
             more.update(acfg=acfg, align_out=found_align)
@@ -517,6 +542,11 @@ def main():
                     help="With --plate-fill: a filled pixel takes its bytes from up to `depth` usable frames in turn (the nearest and the next ones on "
                          "its side, at most `reach` frames from it), not from the nearest alone, so that the grain inside the fill moves as it does "
                          "around it.  Prints one line with what it rotated.")
+    ap.add_argument("--shadow-mask", type=_setting_arg("shadow_mask"), default=None, metavar=_OPTION["shadow_mask"].metavar,
+                    help="Shadow masking before the clean-plate fill: extend every frame's mask over the cast shadow of what it covers.  Unmasked "
+                         "pixels at `lo` .. `hi` percent of the shot's clean background (at least `drop` levels darker, the three channels within "
+                         "`chroma` points of each other) that hang on to the mask within `reach` steps join it, grown by `grow`; parts under "
+                         "`min_area` pixels are dropped.  Changes masks only.  Prints one line with what it added.")
     ap.add_argument("--deflicker", type=_setting_arg("deflicker"), default=None, metavar=_OPTION["deflicker"].metavar,
                     help="Inpaint deflicker before the seam stages: every pixel of the model's output becomes the mean of those of its neighbours at "
                          "most `radius` frames away (on: 2) that lie within `tol` levels of it (on: 12), so the patch stops shimmering; what changes by "
@@ -577,6 +607,10 @@ def main():
         r = last_plate_grain
         filled, rotated = int(r.filled.sum()), int(r.rotated.sum())
         print(f"plate grain: {filled} px filled, {100.0 * rotated / max(filled, 1):.1f} % of them from another frame than the nearest")
+    if args.shadow_mask is not None and last_shadow_mask is not None:
+        r = last_shadow_mask
+        print(f"shadow mask: {int(r.added.sum())} px added in {int((r.added > 0).sum())} of {r.added.size} frames from {int(r.candidates.sum())} candidate px, "
+              f"{sum(r.skipped)} of {len(r.segments)} segments skipped")
     if args.deflicker is not None and last_deflicker is not None:
         r = last_deflicker
         touched = (r.changed > 0).any(axis=0)

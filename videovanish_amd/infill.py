@@ -1,19 +1,19 @@
-"""The orchestration of one diffuerase.run_infill_on_frames call after the dilation: the mask clean-up (clean_masks), the clean-plate fill
-(plate_fill), the temporal plan (span_plan, run_spans), and for each clip the windows (region_plans, run_clip), ONE crop -> prior -> model
+"""The orchestration of one diffuerase.run_infill_on_frames call after the dilation: the mask clean-up (clean_masks), the shadow masking
+(shadow_mask), the clean-plate fill (plate_fill), the temporal plan (span_plan, run_spans), and for each clip the windows (region_plans, run_clip), ONE crop -> prior -> model
 sequence (run_windows) and ONE closing step (finish).  The full frame is no window, roi= "static" / "follow" one, the "-regions" spellings
 several.  The closing step is one loop over the windows; in it the opt-in seam stages run on each window's pixels before they are pasted: the
 deflicker along time (with its alignment along a translation tracked per clip call), the tone fit to the ring round the mask, the grain the
 ring's originals have and the model's pixels lack, the membrane that carries the ring's difference original - model into the hole.  Each stage
 reports per clip call; tone_report, grain_report, seam_blend_report, deflicker_report and deflicker_align_report assemble a call's report from
 them.  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is module state.  Rules and reasons: DESIGN.md
-§10, §11, §12, §13, §14, §15, §16, §17, §18, §19."""
+§10, §11, §12, §13, §14, §15, §16, §17, §18, §19, §21."""
 import dataclasses
 from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
 
-from . import align_hip, blend_hip, deflicker, deflickeralign, flickalign_hip, flicker_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platealign, platefill, plategrain_hip, seamblend, spans_hip, tone_hip, tonematch
+from . import align_hip, blend_hip, deflicker, deflickeralign, flickalign_hip, flicker_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platealign, platefill, plategrain_hip, seamblend, shadow_hip, shadowmask, spans_hip, tone_hip, tonematch
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -70,6 +70,71 @@ def clean_masks(m, dil_t, ccfg, cuts=None):
         dil_t = out
         counts[:, 2:] = c.cpu().numpy()
     return dil_t, MaskCleanReport(*(counts[:, k].copy() for k in range(4)), cuts)
+
+
+# ---- shadows: what the object casts beside the mask --------------------------------------------------------------------------------------------
+class ShadowMaskReport(NamedTuple):
+    """What shadow_mask changed: per frame (int64 [T] each) the candidate pixels of rule 4 inside the segment's crop and the pixels added to the
+    mask; per segment of `segments` the pixels of its crop that have a plate and whether it was skipped (its crop exceeded max_bytes or 65535
+    frames: nothing added); the cuts the segments come from."""
+    candidates: np.ndarray
+    added: np.ndarray
+    plate: tuple
+    skipped: tuple
+    segments: tuple
+    cuts: tuple
+
+
+def _shadow_device(f, d, hcfg):
+    """The stage itself on resident frames f [T,h,w,3] and their masks d [T,h,w] (include/vvshadow.h): the sample frames from
+    time_bridge_grow(., 0, guard), the plate, the candidates, the growth from the frame's mask, the despeckle of what was added, its penumbra
+    (mask_collapse_dilate), the union -> (d' on the device, counts [T,2] = (candidates, added) on the host, plate pixels).  A step that is
+    switched off launches nothing; nothing is read back before the end."""
+    notsample = d if hcfg.guard == 0 else mask_hip.time_bridge_grow(d, 0, hcfg.guard)[0]
+    ok, n2, t1 = shadow_hip.plate(f, notsample, hcfg.min_samples, hcfg.tol)
+    cand, counts = shadow_hip.candidates(f, d, ok, n2, t1, hcfg.lo, hcfg.hi, hcfg.drop, hcfg.chroma, hcfg.floor)
+    s = shadow_hip.grow(d, cand, hcfg.reach)
+    if hcfg.min_area > 1:
+        s = mask_hip.despeckle(s, s, hcfg.min_area)[0]
+    if hcfg.grow:
+        s = hip.mask_collapse_dilate(s[..., None], hcfg.grow)
+    d2 = shadow_hip.merge(d, s, counts)
+    return d2, counts.cpu().numpy(), int(ok.sum().item())
+
+
+def shadow_mask(frames_rgb, dil_t, hcfg, cuts=None):
+    """The shadow masking (shadowmask.py; rules: include/vvshadow.h): frames_rgb = the T host frames [H,W,3] u8, dil_t = the masks
+    [T,H,W] u8 on the device, hcfg = a ShadowMaskConfig, cuts = frame indices or None (one segment).  Per segment of spans.segments: the crop of
+    the union box of its masks (platefill.crop_box) widened by reach + grow (shadowmask.widen_box) crosses to the device, and the masks of that
+    crop are replaced (_shadow_device).  A segment without a mask pixel uploads nothing; one whose crop exceeds max_bytes, or that is longer
+    than 65535 frames, is left as it is and flagged.  Returns (dil', ShadowMaskReport): dil' is dil_t itself when nothing was added at all,
+    and neither the frames nor dil_t is ever written.  Depends on nothing but its arguments: every rank gets the same masks."""
+    T, H, W = dil_t.shape
+    cuts = tuple(int(c) for c in (cuts or ()))
+    segs = tuple(span_planner.segments(T, cuts))
+    boxes = hip.mask_bbox(dil_t).cpu().numpy()
+    dil = dil_t
+    cand, added = np.zeros(T, np.int64), np.zeros(T, np.int64)
+    plate, skipped = [], []
+    for s, e in segs:
+        plate.append(0)
+        skipped.append(False)
+        box = platefill.crop_box(boxes[s:e], H, W)
+        if box is None:
+            continue
+        box = shadowmask.widen_box(box, H, W, hcfg.widen)
+        if e - s > shadowmask.MAX_T or platefill.crop_bytes(e - s, box) > hcfg.max_bytes:
+            skipped[-1] = True
+            continue
+        y0, x0, y1, x1 = box
+        f = torch.from_numpy(np.stack([fr[y0:y1, x0:x1] for fr in frames_rgb[s:e]])).to(dil_t.device)
+        d2, c, plate[-1] = _shadow_device(f, dil_t[s:e, y0:y1, x0:x1].contiguous(), hcfg)
+        cand[s:e], added[s:e] = c[:, 0], c[:, 1]
+        if c[:, 1].any():
+            if dil is dil_t:
+                dil = dil_t.clone()
+            dil[s:e, y0:y1, x0:x1] = d2
+    return dil, ShadowMaskReport(cand, added, tuple(plate), tuple(skipped), segs, cuts)
 
 
 # ---- clean plate: what the clip itself shows behind the mask -------------------------------------------------------------------------------
