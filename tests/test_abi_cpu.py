@@ -2,8 +2,12 @@
 import ctypes
 import os
 import re
+import sys
 
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abiref  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "videovanish_amd", "csrc", "libvvhip.so")
@@ -32,38 +36,40 @@ def test_every_declared_symbol_is_exported(lib):
 
 def _header():
     """include/vvhip.h without its comments"""
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vvhip.h")).read(), flags=re.S)
-
-
-CTYPE_OF = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
-
-
-def _prototypes():
-    """every prototype of include/vvhip.h -> {name: (restype, [argtypes])}: any pointer -> c_void_p, scalars by CTYPE_OF, `const char*` returned -> c_char_p"""
-    protos = {}
-    for ret, name, args in re.findall(r"^\s*(int|const char\*)\s+(vv_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _header(), flags=re.M):
-        args = [" ".join(a.split()) for a in args.split(",")]
-        args = [] if args in (["void"], [""]) else args
-        # a parameter is `type name`; a pointer of any pointee is an address
-        protos[name] = (ctypes.c_int if ret == "int" else ctypes.c_char_p, [ctypes.c_void_p if "*" in a else CTYPE_OF[a.rsplit(" ", 1)[0]] for a in args])
-    return protos
+    return abiref.code(open(os.path.join(ROOT, "include", "vvhip.h")).read())
 
 
 def test_binding_lists_match_header(lib):
     """hip.SIGNATURES declares every function of include/vvhip.h with the header's return and parameter types, and hip.lib() has applied it: an int64_t
     or float parameter passed without its declaration would be truncated / passed as garbage silently."""
     from videovanish_amd import hip
-    protos = _prototypes()
+    protos = abiref.prototypes("vvhip.h", "vv_")[1]
     assert sorted(protos) == _declared() and len(protos) == 88
     assert sorted(hip.EXPORTS) == _declared()
-    assert sorted(hip.SIGNATURES) == sorted(protos)
-    loaded = hip.lib()
-    for name, (restype, argtypes) in protos.items():
-        fn = getattr(loaded, name)
-        assert fn.restype is restype, (name, fn.restype, restype)
-        assert fn.argtypes is not None and list(fn.argtypes) == argtypes, (name, fn.argtypes, argtypes)
+    abiref.check_binding(hip, 88)
     assert sum(ctypes.c_int64 in a for _, a in protos.values()) == 34 and sum(ctypes.c_float in a for _, a in protos.values()) == 16
     assert lib.vv_abi_version() == hip.ABI_VERSION == 10
+
+
+def test_parts_of_the_library_share_no_name():
+    """The parts of libvvhip.so (abiref.PARTS) are hip and every videovanish_amd/*_hip.py, their headers every include/vv*.h but the codec's; the
+    prefixes differ pairwise, every name of a part carries its own prefix, and no name is declared by two parts."""
+    import glob
+    found = ["hip"] + [os.path.basename(f)[:-3] for f in glob.glob(os.path.join(ROOT, "videovanish_amd", "*_hip.py"))]
+    assert sorted(abiref.PARTS) == sorted(found) and len(set(abiref.PARTS)) == len(abiref.PARTS)
+    parts = abiref.parts()
+    headers = {os.path.basename(f) for f in glob.glob(os.path.join(ROOT, "include", "vv*.h"))} - {"vvio.h"}
+    assert sorted(p.header for _, p in parts) == sorted(headers)
+    prefixes = [p.prefix for _, p in parts]
+    assert len(set(prefixes)) == len(prefixes) and all(re.fullmatch(r"vv[a-z]?_", x) for x in prefixes) and parts[0][1].prefix == "vv_"
+    seen = {}
+    for mod, part in parts:
+        assert part.signatures is mod.SIGNATURES and list(mod.SIGNATURES) == mod.EXPORTS, mod.__name__
+        for name in mod.SIGNATURES:
+            assert name.startswith(part.prefix), (mod.__name__, name)
+            assert seen.setdefault(name, mod.__name__) == mod.__name__, (name, seen[name], mod.__name__)
+        for other in prefixes:      # a name of one part cannot be taken for another's either: no other prefix starts it
+            assert other == part.prefix or not any(name.startswith(other) for name in mod.SIGNATURES), (mod.__name__, other)
 
 
 def test_wrong_kind_of_argument_is_refused_at_the_call():

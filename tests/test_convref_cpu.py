@@ -339,10 +339,10 @@ def _params(**kw):
         def vv_conv_gemm_route(self, pp, dt):
             seen["p"] = hip.ConvParams.from_buffer_copy(pp._obj)
             return orig(pp, dt)
-    saved = hip._lib
-    hip._lib = Spy()
+    saved = hip.CORE.dll
+    hip.CORE.dll = Spy()
     try:
         _route(**kw)
     finally:
-        hip._lib = saved
+        hip.CORE.dll = saved
     return seen["p"]

@@ -2,7 +2,6 @@
 restatement (tests/deflicker_ref.py), the rule on synthetic clips, the report, configuration and CLI."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 import types
@@ -11,6 +10,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abiref  # noqa: E402
 import deflicker_ref as R  # noqa: E402
 
 from videovanish_amd import deflicker as D  # noqa: E402
@@ -42,38 +42,13 @@ def test_spellings_and_config():
 
 
 # ---- binding ------------------------------------------------------------------------------------------------------------------------------
-CTYPE_OF = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64}
-RET_OF = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char*": ctypes.c_char_p}
-
-
 def test_binding_matches_vvflicker_header():
     """flicker_hip.SIGNATURES declares every function of include/vvflicker.h with the header's types, flicker_hip.lib() has applied it, the version
-    and the limits agree in the header, the binding and the settings, no name could be taken for another unit's, and arguments are refused
-    before anything touches a device."""
-    from videovanish_amd import align_hip, blend_hip, flicker_hip, grain_hip, hip, mask_hip, plate_hip, spans_hip, tone_hip
-    if not os.path.isfile(os.path.join(ROOT, "videovanish_amd", "csrc", "libvvhip.so")):
-        import __graft_entry__
-        __graft_entry__.build()
-    raw = open(os.path.join(ROOT, "include", "vvflicker.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = re.findall(r"\b(vvf_[a-z0-9_]+)\s*\(", src)
-    protos = {}
-    for ret, name, args in re.findall(r"^\s*(int|int64_t|const char\*)\s+(vvf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        args = [" ".join(a.split()) for a in args.split(",")]
-        args = [] if args in (["void"], [""]) else args
-        protos[name] = (RET_OF[ret], [ctypes.c_void_p if "*" in a else CTYPE_OF[a.rsplit(" ", 1)[0]] for a in args])
-    assert list(protos) == declared == list(flicker_hip.SIGNATURES) == flicker_hip.EXPORTS and len(protos) == 4      # in the header's order
-    assert not re.findall(r"\bvv[a-eg-z]?_[a-z0-9_]+\s*\(", src)
-    others = set()
-    for unit in (hip, spans_hip, mask_hip, tone_hip, grain_hip, blend_hip, plate_hip, align_hip):
-        others |= set(unit.SIGNATURES)
-    assert not set(flicker_hip.SIGNATURES) & others
-    loaded = flicker_hip.lib()
-    for name, (restype, argtypes) in protos.items():
-        fn = getattr(loaded, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, (name, fn.restype, fn.argtypes)
-    define = lambda name: eval(re.search(rf"#define {name} (\S+)", raw).group(1))
-    assert loaded.vvf_abi_version() == define("VVF_ABI_VERSION") == flicker_hip.ABI_VERSION == 1
+    and the limits agree in the header, the binding and the settings (abiref.check_binding; test_abi_cpu.py: no name could be taken for
+    another part's), and arguments are refused before anything touches a device."""
+    from videovanish_amd import flicker_hip
+    loaded, define = abiref.check_binding(flicker_hip, 4)
+    assert define("VVF_ABI_VERSION") == 1
     limits = (define("VVF_MAX_RADIUS"), define("VVF_MAX_T"), define("VVF_SLAB"))
     assert limits == (flicker_hip.MAX_RADIUS, flicker_hip.MAX_T, flicker_hip.SLAB) == (4, 65535, 16)
     assert (D.MAX_RADIUS, D.MAX_T, D.MAX_TOL, D.NSUM) == (4, 65535, 255, 12) == (flicker_hip.MAX_RADIUS, flicker_hip.MAX_T, 255, flicker_hip.NSUM)
@@ -107,13 +82,8 @@ def test_binding_matches_vvflicker_header():
 def test_product_sources_of_the_feature():
     """vv_flicker is in the one build recipe with its header among the dependencies and reads no environment; the settings import no torch and no
     oracle; importing the drop-in resolves no vvf_ symbol."""
-    csrc = os.path.join(ROOT, "videovanish_amd", "csrc")
-    recipe = open(os.path.join(csrc, "build.sh")).read()
-    assert re.search(r"\bvv_flicker\b", recipe) and "include/vvflicker.h" in recipe
-    assert "getenv" not in open(os.path.join(csrc, "vv_flicker.hip")).read()
-    txt = open(os.path.join(ROOT, "videovanish_amd", "deflicker.py")).read()
-    assert "import torch" not in txt and "from torch" not in txt and "oracle" not in txt
-    code = ("import sys, diffuerase; from videovanish_amd import flicker_hip, hip, infill; assert flicker_hip._lib is None and hip._lib is None; "
+    abiref.check_sources("vv_flicker", "vvflicker.h", "deflicker")
+    code = ("import sys, diffuerase; from videovanish_amd import flicker_hip, hip, infill; assert flicker_hip.PART.dll is None and hip.CORE.dll is None; "
             "assert diffuerase.deflicker_config() is None and diffuerase.last_deflicker is None")
     env = {k: v for k, v in os.environ.items() if k != "VV_DEFLICKER"}
     subprocess.check_call([sys.executable, "-c", code], cwd=ROOT, env=env)

@@ -221,7 +221,7 @@ def run(gpu, clip):
                 flicker_hip.window_pixels, flicker_hip.hold = R.hip_window_pixels, R.hip_hold
             try:
                 out = diffuerase.run_infill_on_frames(frames, masks, propainer_frames=prior, feather_px=3, **KW, **kw)
-                seen[key] = (np.stack(out), diffuerase.last_deflicker, flicker_hip._lib is not None)
+                seen[key] = (np.stack(out), diffuerase.last_deflicker, flicker_hip.PART.dll is not None)
             finally:
                 flicker_hip.window_pixels, flicker_hip.hold = device
                 diffuerase.configure(None)
@@ -239,15 +239,15 @@ def test_no_resolution_without_the_option(gpu, clip):
     import diffuerase
     from videovanish_amd import flicker_hip
     frames, masks, prior = clip
-    kept, flicker_hip._lib = flicker_hip._lib, None
+    kept, flicker_hip.PART.dll = flicker_hip.PART.dll, None
     diffuerase.configure(RUN)
     try:
         for kw in (dict(), dict(deflicker="off", tone_match="on"), dict(roi=FOLLOW, spans=SPANS)):
             diffuerase.run_infill_on_frames(frames, masks, propainer_frames=prior, feather_px=3, **KW, **kw)
-            assert flicker_hip._lib is None and diffuerase.last_deflicker is None
+            assert flicker_hip.PART.dll is None and diffuerase.last_deflicker is None
     finally:
         diffuerase.configure(None)
-        flicker_hip._lib = kept
+        flicker_hip.PART.dll = kept
 
 
 def test_seam_bindings_stay_unresolved_while_their_stage_is_off(gpu, clip):
@@ -257,19 +257,19 @@ def test_seam_bindings_stay_unresolved_while_their_stage_is_off(gpu, clip):
     from videovanish_amd import blend_hip, grain_hip, tone_hip
     frames, masks, prior = clip
     mods = (tone_hip, grain_hip, blend_hip)
-    kept = [m._lib for m in mods]
+    kept = [m.PART.dll for m in mods]
     diffuerase.configure(RUN)
     try:
         for kw, off in ((dict(), mods), (dict(roi=FOLLOW), mods), (dict(tone_match="on", roi=FOLLOW), mods[1:])):
             for m in mods:
-                m._lib = None
+                m.PART.dll = None
             diffuerase.run_infill_on_frames(frames, masks, propainer_frames=prior, feather_px=3, **KW, **kw)
-            assert all(m._lib is None for m in off)
-            assert (tone_hip._lib is not None) == ("tone_match" in kw)
+            assert all(m.PART.dll is None for m in off)
+            assert (tone_hip.PART.dll is not None) == ("tone_match" in kw)
     finally:
         diffuerase.configure(None)
         for m, lib in zip(mods, kept):
-            m._lib = lib
+            m.PART.dll = lib
 
 
 @pytest.mark.parametrize("kw", PLUMBING, ids=["plain", "seams", "spans-follow"])

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abiref  # noqa: E402
 import deflicker_ref as R0  # noqa: E402
 import deflickeralign_ref as R  # noqa: E402
 import platealign_ref as A  # noqa: E402
@@ -47,39 +48,14 @@ def test_settings_are_the_trackers():
 
 
 # ---- binding ------------------------------------------------------------------------------------------------------------------------------
-CTYPE_OF = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64}
-RET_OF = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char*": ctypes.c_char_p}
-
-
 def test_binding_matches_vvflickalign_header():
     """flickalign_hip.SIGNATURES declares every function of include/vvflickalign.h with the header's types, flickalign_hip.lib() has applied it,
-    the version and the limits agree in the header, the binding and vvflicker.h, no name could be taken for another unit's, and arguments are
-    refused before anything touches a device."""
-    from videovanish_amd import align_hip, blend_hip, flickalign_hip, flicker_hip, grain_hip, hip, mask_hip, plate_hip, spans_hip, tone_hip
-    if not os.path.isfile(os.path.join(ROOT, "videovanish_amd", "csrc", "libvvhip.so")):
-        import __graft_entry__
-        __graft_entry__.build()
-    raw = open(os.path.join(ROOT, "include", "vvflickalign.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = re.findall(r"\b(vvc_[a-z0-9_]+)\s*\(", src)
-    protos = {}
-    for ret, name, args in re.findall(r"^\s*(int|int64_t|const char\*)\s+(vvc_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        args = [" ".join(a.split()) for a in args.split(",")]
-        args = [] if args in (["void"], [""]) else args
-        protos[name] = (RET_OF[ret], [ctypes.c_void_p if "*" in a else CTYPE_OF[a.rsplit(" ", 1)[0]] for a in args])
-    assert list(protos) == declared == list(flickalign_hip.SIGNATURES) == flickalign_hip.EXPORTS == ["vvc_abi_version", "vvc_last_error", "vvc_hold"]
-    assert not re.findall(r"\bvv[abd-z]?_[a-z0-9_]+\s*\(", src)
-    others = set()
-    for unit in (hip, spans_hip, mask_hip, tone_hip, grain_hip, blend_hip, plate_hip, align_hip, flicker_hip):
-        others |= set(unit.SIGNATURES)
-    assert not set(flickalign_hip.SIGNATURES) & others
-    loaded = flickalign_hip.lib()
-    for name, (restype, argtypes) in protos.items():
-        fn = getattr(loaded, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, (name, fn.restype, fn.argtypes)
-    define = lambda text, name: eval(re.search(rf"#define {name} (\S+)", text).group(1))
-    assert loaded.vvc_abi_version() == define(raw, "VVC_ABI_VERSION") == flickalign_hip.ABI_VERSION == 1
-    limits = (define(raw, "VVC_MAX_RADIUS"), define(raw, "VVC_MAX_T"), define(raw, "VVC_TRACK_INTS"))
+    the version and the limits agree in the header, the binding and vvflicker.h (abiref.check_binding; test_abi_cpu.py: no name could be taken
+    for another part's), and arguments are refused before anything touches a device."""
+    from videovanish_amd import align_hip, flickalign_hip, flicker_hip
+    loaded, define = abiref.check_binding(flickalign_hip, 3)
+    assert flickalign_hip.EXPORTS == ["vvc_abi_version", "vvc_last_error", "vvc_hold"] and define("VVC_ABI_VERSION") == 1
+    limits = (define("VVC_MAX_RADIUS"), define("VVC_MAX_T"), define("VVC_TRACK_INTS"))
     assert limits == (flickalign_hip.MAX_RADIUS, flickalign_hip.MAX_T, flickalign_hip.TRACK_INTS) == (4, 65535, 8)
     assert limits == (flicker_hip.MAX_RADIUS, flicker_hip.MAX_T, align_hip.TRACK_INTS) and flickalign_hip.NSUM == flicker_hip.NSUM == R.NSUM == 12
     # refusals: nothing is launched, the message names the function
@@ -105,18 +81,14 @@ def test_binding_matches_vvflickalign_header():
 def test_product_sources_of_the_feature():
     """The kernel lives in vv_flicker.hip beside the gather form, as one body; the header is among the recipe's dependencies; the settings
     import no torch and no oracle; importing the drop-in resolves no vvc_ symbol; vvflicker.h keeps its four functions."""
-    csrc = os.path.join(ROOT, "videovanish_amd", "csrc")
-    recipe = open(os.path.join(csrc, "build.sh")).read()
-    assert "include/vvflickalign.h" in recipe and "include/vvflicker.h" in recipe
-    hipsrc = open(os.path.join(csrc, "vv_flicker.hip")).read()
-    assert "getenv" not in hipsrc and "vvflickalign.h" in hipsrc
+    hipsrc, txt = abiref.check_sources("vv_flicker", "vvflickalign.h", "deflickeralign")
+    assert "include/vvflicker.h" in open(os.path.join(abiref.CSRC, "build.sh")).read()
     assert len(re.findall(r"void hold_gather_kernel\(", hipsrc)) == 1 and "hold_gather_kernel<true>" in hipsrc and "hold_gather_kernel<false>" in hipsrc
     assert len(re.findall(r'extern "C" [^(]*\bvvc_', hipsrc)) == 3
     assert "vvc_" not in open(os.path.join(ROOT, "include", "vvflicker.h")).read()
-    txt = open(os.path.join(ROOT, "videovanish_amd", "deflickeralign.py")).read()
-    assert "import torch" not in txt and "from torch" not in txt and "oracle" not in txt and "class " not in txt
+    assert "class " not in txt
     code = ("import sys, diffuerase; from videovanish_amd import flickalign_hip, flicker_hip, align_hip, hip; "
-            "assert flickalign_hip._lib is None and flicker_hip._lib is None and align_hip._lib is None and hip._lib is None; "
+            "assert flickalign_hip.PART.dll is None and flicker_hip.PART.dll is None and align_hip.PART.dll is None and hip.CORE.dll is None; "
             "assert diffuerase.deflicker_align_config() is None and diffuerase.last_deflicker_align is None")
     env = {k: v for k, v in os.environ.items() if k not in ("VV_DEFLICKER", "VV_DEFLICKER_ALIGN")}
     subprocess.check_call([sys.executable, "-c", code], cwd=ROOT, env=env)

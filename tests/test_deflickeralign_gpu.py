@@ -260,14 +260,14 @@ def _call(clip, host=False, **kw):
 
 def test_drop_in_locked_off_is_deflicker_alone_and_resolves_nothing_without_the_option(gpu, still_clip):
     from videovanish_amd import flickalign_hip
-    kept, flickalign_hip._lib = flickalign_hip._lib, None
+    kept, flickalign_hip.PART.dll = flickalign_hip.PART.dll, None
     try:
         base, rep, none = _call(still_clip, deflicker="on")
-        assert none is None and rep is not None and flickalign_hip._lib is None                     # a full call without the option
+        assert none is None and rep is not None and flickalign_hip.PART.dll is None                 # a full call without the option
         out, arep_rep, arep = _call(still_clip, deflicker="on", deflicker_align="on")
-        assert flickalign_hip._lib is None                                                          # "static": vvf_hold as it is
+        assert flickalign_hip.PART.dll is None                                                      # "static": vvf_hold as it is
     finally:
-        flickalign_hip._lib = kept
+        flickalign_hip.PART.dll = kept
     assert (out == base).all() and (out != np.stack(still_clip[0])).any()
     for a, b in zip(rep, arep_rep):
         assert (a == b).all()

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abiref  # noqa: E402
 import grainmatch_ref as R  # noqa: E402
 
 from videovanish_amd import grainmatch as M  # noqa: E402
@@ -56,37 +57,14 @@ def test_spellings_and_config():
 
 
 # ---- binding ------------------------------------------------------------------------------------------------------------------------------
-CTYPE_OF = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
-
-
 def test_binding_matches_vvgrain_header():
     """grain_hip.SIGNATURES declares every function of include/vvgrain.h with the header's types and in its order, grain_hip.lib() has applied it,
-    the version and the limits agree, no name of the header could be taken for one of the other headers', and the arguments are validated before
-    any device work."""
-    from videovanish_amd import grain_hip, hip, mask_hip, spans_hip, tone_hip
-    if not os.path.isfile(os.path.join(ROOT, "videovanish_amd", "csrc", "libvvhip.so")):
-        import __graft_entry__
-        __graft_entry__.build()
+    the version and the limits agree (abiref.check_binding; test_abi_cpu.py: no name could be taken for another part's), and the arguments are
+    validated before any device work."""
+    from videovanish_amd import grain_hip
+    loaded, define = abiref.check_binding(grain_hip, 4)
     raw = open(os.path.join(ROOT, "include", "vvgrain.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = sorted(set(re.findall(r"\b(vvg_[a-z0-9_]+)\s*\(", src)))
-    protos = {}
-    for ret, name, args in re.findall(r"^\s*(int|const char\*)\s+(vvg_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        args = [" ".join(a.split()) for a in args.split(",")]
-        args = [] if args in (["void"], [""]) else args
-        protos[name] = (ctypes.c_int if ret == "int" else ctypes.c_char_p, [ctypes.c_void_p if "*" in a else CTYPE_OF[a.rsplit(" ", 1)[0]] for a in args])
-    assert sorted(protos) == declared == sorted(grain_hip.SIGNATURES) == sorted(grain_hip.EXPORTS) and len(protos) == 4
-    assert list(grain_hip.SIGNATURES) == re.findall(r"\b(vvg_[a-z0-9_]+)\s*\(", src)                  # in the header's order
-    for prefix in ("vv", "vvs", "vvm", "vvt"):
-        assert not re.findall(rf"\b{prefix}_[a-z0-9_]+\s*\(", src), prefix
-    assert not set(grain_hip.SIGNATURES) & (set(hip.SIGNATURES) | set(spans_hip.SIGNATURES) | set(mask_hip.SIGNATURES) | set(tone_hip.SIGNATURES))
-    loaded = grain_hip.lib()
-    for name, (restype, argtypes) in protos.items():
-        fn = getattr(loaded, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, (name, fn.restype, fn.argtypes)
-        assert (restype, tuple(argtypes)) == (grain_hip.SIGNATURES[name][0], tuple(grain_hip.SIGNATURES[name][1]))
-    define = lambda name: int(re.search(rf"#define {name} (\d+)", raw).group(1))
-    assert loaded.vvg_abi_version() == define("VVG_ABI_VERSION") == grain_hip.ABI_VERSION == 1
+    assert define("VVG_ABI_VERSION") == 1
     assert define("VVG_MAX_RING") == grain_hip.MAX_RING == M.MAX_RING == 32
     assert define("VVG_BANDS") == grain_hip.BANDS == M.BANDS == 4 and define("VVG_NSUM") == grain_hip.NSUM == M.NSUM == 36
     for formula in ("0x9E3779B97F4A7C15", "0xBF58476D1CE4E5B9", "0x94D049BB133111EB", "* 5017 + (1 << 23)) >> 24", "- 1020"):
@@ -125,18 +103,14 @@ def test_binding_matches_vvgrain_header():
 def test_product_sources_of_the_feature():
     """vv_grain is in the one build recipe with its header among the dependencies and reads no environment; the ring has one statement, which
     both users include; the settings import no torch; importing the drop-in resolves no symbol of the feature."""
-    csrc = os.path.join(ROOT, "videovanish_amd", "csrc")
-    recipe = open(os.path.join(csrc, "build.sh")).read()
-    assert re.search(r"\bvv_grain\b", recipe) and "include/vvgrain.h" in recipe
-    grain, tone, shared = (open(os.path.join(csrc, f)).read() for f in ("vv_grain.hip", "vv_tone.hip", "vv_ring_bits.h"))
-    assert "getenv" not in grain and "getenv" not in shared
+    grain, _ = abiref.check_sources("vv_grain", "vvgrain.h", "grainmatch")
+    tone, shared = (open(os.path.join(abiref.CSRC, f)).read() for f in ("vv_tone.hip", "vv_ring_bits.h"))
+    assert "getenv" not in shared
     for user in (grain, tone):
         assert '#include "vv_ring_bits.h"' in user and "vvring::ring_bits<" in user and "__ballot" not in user
     assert shared.count("__ballot(") == 2
-    txt = open(os.path.join(ROOT, "videovanish_amd", "grainmatch.py")).read()
-    assert "import torch" not in txt and "from torch" not in txt and "oracle" not in txt
     code = ("import diffuerase; from videovanish_amd import grain_hip, tone_hip, hip, grainmatch; "
-            "assert grain_hip._lib is None and tone_hip._lib is None and hip._lib is None; assert diffuerase.last_grain_match is None")
+            "assert grain_hip.PART.dll is None and tone_hip.PART.dll is None and hip.CORE.dll is None; assert diffuerase.last_grain_match is None")
     subprocess.check_call([sys.executable, "-c", code], cwd=ROOT)
 
 

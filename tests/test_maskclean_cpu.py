@@ -3,7 +3,6 @@ over seeded draws, the planners on noisy masks with and without the clean-up, th
 reference, configuration and CLI."""
 import ctypes
 import os
-import re
 import sys
 import types
 
@@ -12,6 +11,7 @@ import pytest
 from scipy import ndimage
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abiref  # noqa: E402
 import maskclean_ref as R  # noqa: E402
 
 from videovanish_amd import maskclean as M  # noqa: E402
@@ -46,35 +46,12 @@ def test_spellings_and_config():
 
 
 # ---- binding ------------------------------------------------------------------------------------------------------------------------------
-CTYPE_OF = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
-
-
 def test_binding_matches_vvmask_header():
     """mask_hip.SIGNATURES declares every function of include/vvmask.h with the header's types, mask_hip.lib() has applied it, the versions and
-    limits agree, and no name of the header could be taken for one of vvhip.h's or vvspans.h's."""
-    from videovanish_amd import hip, mask_hip, spans_hip
-    if not os.path.isfile(os.path.join(ROOT, "videovanish_amd", "csrc", "libvvhip.so")):
-        import __graft_entry__
-        __graft_entry__.build()
-    raw = open(os.path.join(ROOT, "include", "vvmask.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = sorted(set(re.findall(r"\b(vvm_[a-z0-9_]+)\s*\(", src)))
-    protos = {}
-    for ret, name, args in re.findall(r"^\s*(int|const char\*)\s+(vvm_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        args = [" ".join(a.split()) for a in args.split(",")]
-        args = [] if args in (["void"], [""]) else args
-        protos[name] = (ctypes.c_int if ret == "int" else ctypes.c_char_p, [ctypes.c_void_p if "*" in a else CTYPE_OF[a.rsplit(" ", 1)[0]] for a in args])
-    assert sorted(protos) == declared == sorted(mask_hip.SIGNATURES) == sorted(mask_hip.EXPORTS) and len(protos) == 5
-    assert list(mask_hip.SIGNATURES) == re.findall(r"\b(vvm_[a-z0-9_]+)\s*\(", src)                   # in the header's order
-    assert not re.findall(r"\bvv_[a-z0-9_]+\s*\(", src) and not re.findall(r"\bvvs_[a-z0-9_]+\s*\(", src)
-    assert not set(mask_hip.SIGNATURES) & (set(hip.SIGNATURES) | set(spans_hip.SIGNATURES))
-    loaded = mask_hip.lib()
-    for name, (restype, argtypes) in protos.items():
-        fn = getattr(loaded, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, (name, fn.restype, fn.argtypes)
-        assert (restype, tuple(argtypes)) == (mask_hip.SIGNATURES[name][0], tuple(mask_hip.SIGNATURES[name][1]))
-    define = lambda name: int(re.search(rf"#define {name} (\d+)", raw).group(1))
-    assert loaded.vvm_abi_version() == define("VVM_ABI_VERSION") == mask_hip.ABI_VERSION == 1
+    limits agree (abiref.check_binding; test_abi_cpu.py: no name could be taken for another part's)."""
+    from videovanish_amd import mask_hip
+    loaded, define = abiref.check_binding(mask_hip, 5)
+    assert define("VVM_ABI_VERSION") == 1
     assert (define("VVM_MAX_BRIDGE"), define("VVM_MAX_GROW"), define("VVM_MAX_T")) == (mask_hip.MAX_BRIDGE, mask_hip.MAX_GROW, mask_hip.MAX_T) == (16, 8, 65535)
     assert (M.MAX_BRIDGE, M.MAX_GROW) == (mask_hip.MAX_BRIDGE, mask_hip.MAX_GROW)
     # arguments are validated before anything touches a device
@@ -98,13 +75,8 @@ def test_binding_matches_vvmask_header():
 def test_product_sources_of_the_feature():
     """vv_mask is in the one build recipe with its header among the dependencies and reads no environment; the settings import no torch; importing
     the drop-in resolves no symbol of the feature."""
-    csrc = os.path.join(ROOT, "videovanish_amd", "csrc")
-    recipe = open(os.path.join(csrc, "build.sh")).read()
-    assert re.search(r"\bvv_mask\b", recipe) and "include/vvmask.h" in recipe
-    assert "getenv" not in open(os.path.join(csrc, "vv_mask.hip")).read()
-    txt = open(os.path.join(ROOT, "videovanish_amd", "maskclean.py")).read()
-    assert "import torch" not in txt and "from torch" not in txt and "oracle" not in txt
-    code = "import diffuerase; from videovanish_amd import mask_hip, hip; assert mask_hip._lib is None and hip._lib is None"
+    abiref.check_sources("vv_mask", "vvmask.h", "maskclean")
+    code = "import diffuerase; from videovanish_amd import mask_hip, hip; assert mask_hip.PART.dll is None and hip.CORE.dll is None"
     import subprocess
     subprocess.check_call([sys.executable, "-c", code], cwd=ROOT)
 

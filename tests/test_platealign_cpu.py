@@ -2,7 +2,6 @@
 the ground truth of synthetic pans, the orchestration with the device functions replaced by the reference, configuration and CLI."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 import types
@@ -11,6 +10,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abiref  # noqa: E402
 import platealign_ref as A  # noqa: E402
 import platefill_ref as R  # noqa: E402
 from test_platefill_cpu import host_kernels  # noqa: E402,F401  (the fixture: plate_fill's device calls replaced by the reference)
@@ -79,36 +79,13 @@ def test_canvas_box_and_slices():
 
 
 # ---- binding ------------------------------------------------------------------------------------------------------------------------------
-CTYPE_OF = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64}
-RET_OF = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char*": ctypes.c_char_p}
-
-
 def test_binding_matches_vvalign_header():
     """align_hip.SIGNATURES declares every function of include/vvalign.h with the header's types, align_hip.lib() has applied it, the version and
-    the limits agree in the header, the binding and the settings, no name could be taken for another unit's, and arguments are refused before
-    anything touches a device."""
-    from videovanish_amd import align_hip, blend_hip, hip, mask_hip, plate_hip, spans_hip
-    if not os.path.isfile(os.path.join(ROOT, "videovanish_amd", "csrc", "libvvhip.so")):
-        import __graft_entry__
-        __graft_entry__.build()
-    raw = open(os.path.join(ROOT, "include", "vvalign.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = re.findall(r"\b(vva_[a-z0-9_]+)\s*\(", src)
-    protos = {}
-    for ret, name, args in re.findall(r"^\s*(int|int64_t|const char\*)\s+(vva_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        args = [" ".join(a.split()) for a in args.split(",")]
-        args = [] if args in (["void"], [""]) else args
-        protos[name] = (RET_OF[ret], [ctypes.c_void_p if "*" in a else CTYPE_OF[a.rsplit(" ", 1)[0]] for a in args])
-    assert list(protos) == declared == list(align_hip.SIGNATURES) == align_hip.EXPORTS and len(protos) == 10      # in the header's order
-    assert not re.findall(r"\bvv[b-z]?_[a-z0-9_]+\s*\(", src)
-    others = set(hip.SIGNATURES) | set(spans_hip.SIGNATURES) | set(mask_hip.SIGNATURES) | set(blend_hip.SIGNATURES) | set(plate_hip.SIGNATURES)
-    assert not set(align_hip.SIGNATURES) & others
-    loaded = align_hip.lib()
-    for name, (restype, argtypes) in protos.items():
-        fn = getattr(loaded, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, (name, fn.restype, fn.argtypes)
-    define = lambda name: eval(re.search(rf"#define {name} (.+)", raw).group(1))
-    assert loaded.vva_abi_version() == define("VVA_ABI_VERSION") == align_hip.ABI_VERSION == 1
+    the limits agree in the header, the binding and the settings (abiref.check_binding; test_abi_cpu.py: no name could be taken for another
+    part's), and arguments are refused before anything touches a device."""
+    from videovanish_amd import align_hip
+    loaded, define = abiref.check_binding(align_hip, 10)
+    assert define("VVA_ABI_VERSION") == 1
     limits = (define("VVA_MAX_LEVELS"), define("VVA_MAX_RADIUS"), define("VVA_MAX_PIXELS"), define("VVA_MAX_T"))
     assert limits == (align_hip.MAX_LEVELS, align_hip.MAX_RADIUS, align_hip.MAX_PIXELS, align_hip.MAX_T) == (6, 8, 1 << 24, 65535)
     assert limits == (PA.MAX_LEVELS, PA.MAX_RADIUS, PA.MAX_PIXELS, PA.MAX_T)
@@ -149,13 +126,9 @@ def test_binding_matches_vvalign_header():
 def test_product_sources_of_the_feature():
     """vv_align is in the one build recipe with its header among the dependencies and reads no environment; the settings import no torch; importing
     the drop-in resolves no vva_ symbol, and neither does a call's set-up without the option."""
-    csrc = os.path.join(ROOT, "videovanish_amd", "csrc")
-    recipe = open(os.path.join(csrc, "build.sh")).read()
-    assert re.search(r"\bvv_align\b", recipe) and "include/vvalign.h" in recipe
-    assert "getenv" not in open(os.path.join(csrc, "vv_align.hip")).read()
-    txt = open(os.path.join(ROOT, "videovanish_amd", "platealign.py")).read()
-    assert "import torch" not in txt and "from torch" not in txt and "oracle" not in txt
-    code = ("import diffuerase; from videovanish_amd import align_hip, plate_hip, hip; assert align_hip._lib is None and plate_hip._lib is None and hip._lib is None; "
+    abiref.check_sources("vv_align", "vvalign.h", "platealign")
+    code = ("import diffuerase; from videovanish_amd import align_hip, plate_hip, hip; "
+            "assert align_hip.PART.dll is None and plate_hip.PART.dll is None and hip.CORE.dll is None; "
             "assert diffuerase.plate_align_config() is None and diffuerase.last_plate_align is None")
     env = {k: v for k, v in os.environ.items() if k not in ("VV_PLATE_FILL", "VV_PLATE_ALIGN")}
     subprocess.check_call([sys.executable, "-c", code], cwd=ROOT, env=env)

@@ -2,7 +2,6 @@
 prototype's clips, the orchestration with the device functions replaced by the reference, configuration and CLI."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 import types
@@ -11,6 +10,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abiref  # noqa: E402
 import platefill_ref as R  # noqa: E402
 
 from videovanish_amd import platefill as PF  # noqa: E402
@@ -55,35 +55,13 @@ def test_crop_box():
 
 
 # ---- binding ------------------------------------------------------------------------------------------------------------------------------
-CTYPE_OF = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
-
-
 def test_binding_matches_vvplate_header():
     """plate_hip.SIGNATURES declares every function of include/vvplate.h with the header's types, plate_hip.lib() has applied it, the version and
-    the range constants agree, no name could be taken for another unit's, and arguments are refused before anything touches a device."""
-    from videovanish_amd import blend_hip, hip, mask_hip, plate_hip, spans_hip
-    if not os.path.isfile(os.path.join(ROOT, "videovanish_amd", "csrc", "libvvhip.so")):
-        import __graft_entry__
-        __graft_entry__.build()
-    raw = open(os.path.join(ROOT, "include", "vvplate.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = sorted(set(re.findall(r"\b(vvp_[a-z0-9_]+)\s*\(", src)))
-    protos = {}
-    for ret, name, args in re.findall(r"^\s*(int|const char\*)\s+(vvp_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        args = [" ".join(a.split()) for a in args.split(",")]
-        args = [] if args in (["void"], [""]) else args
-        protos[name] = (ctypes.c_int if ret == "int" else ctypes.c_char_p, [ctypes.c_void_p if "*" in a else CTYPE_OF[a.rsplit(" ", 1)[0]] for a in args])
-    assert sorted(protos) == declared == sorted(plate_hip.SIGNATURES) == sorted(plate_hip.EXPORTS) and len(protos) == 5
-    assert list(plate_hip.SIGNATURES) == re.findall(r"\b(vvp_[a-z0-9_]+)\s*\(", src)                   # in the header's order
-    assert not re.findall(r"\bvv[a-oq-z]?_[a-z0-9_]+\s*\(", src)
-    assert not set(plate_hip.SIGNATURES) & (set(hip.SIGNATURES) | set(spans_hip.SIGNATURES) | set(mask_hip.SIGNATURES) | set(blend_hip.SIGNATURES))
-    loaded = plate_hip.lib()
-    for name, (restype, argtypes) in protos.items():
-        fn = getattr(loaded, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, (name, fn.restype, fn.argtypes)
-        assert (restype, tuple(argtypes)) == (plate_hip.SIGNATURES[name][0], tuple(plate_hip.SIGNATURES[name][1]))
-    define = lambda name: int(re.search(rf"#define {name} (\d+)", raw).group(1))
-    assert loaded.vvp_abi_version() == define("VVP_ABI_VERSION") == plate_hip.ABI_VERSION == 1
+    the range constants agree (abiref.check_binding; test_abi_cpu.py: no name could be taken for another part's), and arguments are refused
+    before anything touches a device."""
+    from videovanish_amd import mask_hip, plate_hip
+    loaded, define = abiref.check_binding(plate_hip, 5)
+    assert define("VVP_ABI_VERSION") == 1
     limits = (define("VVP_MAX_T"), define("VVP_NO_SOURCE"), define("VVP_MAX_GUARD"), define("VVP_MAX_TOL"), define("VVP_MAX_OUTLIER"), define("VVP_MAX_GAP"))
     assert limits == (plate_hip.MAX_T, plate_hip.NO_SOURCE, plate_hip.MAX_GUARD, plate_hip.MAX_TOL, plate_hip.MAX_OUTLIER, plate_hip.MAX_GAP)
     assert limits == (65535, R.NONE, 8, 255, 64, 65535)
@@ -115,13 +93,8 @@ def test_binding_matches_vvplate_header():
 def test_product_sources_of_the_feature():
     """vv_plate is in the one build recipe with its header among the dependencies and reads no environment; the settings import no torch; importing
     the drop-in resolves no symbol of the feature, and neither does a call's set-up without the option."""
-    csrc = os.path.join(ROOT, "videovanish_amd", "csrc")
-    recipe = open(os.path.join(csrc, "build.sh")).read()
-    assert re.search(r"\bvv_plate\b", recipe) and "include/vvplate.h" in recipe
-    assert "getenv" not in open(os.path.join(csrc, "vv_plate.hip")).read()
-    txt = open(os.path.join(ROOT, "videovanish_amd", "platefill.py")).read()
-    assert "import torch" not in txt and "from torch" not in txt and "oracle" not in txt
-    code = ("import diffuerase; from videovanish_amd import plate_hip, hip; assert plate_hip._lib is None and hip._lib is None; "
+    abiref.check_sources("vv_plate", "vvplate.h", "platefill")
+    code = ("import diffuerase; from videovanish_amd import plate_hip, hip; assert plate_hip.PART.dll is None and hip.CORE.dll is None; "
             "assert diffuerase.plate_fill_config() is None and diffuerase.last_plate_fill is None")
     env = {k: v for k, v in os.environ.items() if k != "VV_PLATE_FILL"}
     subprocess.check_call([sys.executable, "-c", code], cwd=ROOT, env=env)

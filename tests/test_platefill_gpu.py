@@ -250,7 +250,7 @@ def test_plate_fill_alone_and_with_cuts(gpu, cuts, H, W):
     plist = list(pf)
     out, dil, rep = infill.plate_fill(plist, pd, PlateFillConfig(), cuts)
     assert dil is pd and all(a is b for a, b in zip(out, plist)) and not rep.filled.any()
-    assert plate_hip._lib is not None
+    assert plate_hip.PART.dll is not None
 
 
 # ---- the drop-in --------------------------------------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abiref  # noqa: E402
 import platefill_ref as R  # noqa: E402
 import plategrain_ref as G  # noqa: E402
 
@@ -45,43 +46,14 @@ def test_spellings_and_config():
 
 
 # ---- binding ------------------------------------------------------------------------------------------------------------------------------
-CTYPE_OF = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
-
-
-def _lib_built():
-    if not os.path.isfile(os.path.join(ROOT, "videovanish_amd", "csrc", "libvvhip.so")):
-        import __graft_entry__
-        __graft_entry__.build()
-
-
 def test_binding_matches_vvplategrain_header():
     """plategrain_hip.SIGNATURES declares every function of include/vvplategrain.h with the header's types and in its order, plategrain_hip.lib()
-    has applied it, the version and the limits agree, and the vvl_ prefix belongs to no other unit."""
-    from videovanish_amd import align_hip, blend_hip, flickalign_hip, flicker_hip, grain_hip, hip, mask_hip, plate_hip, plategrain_hip, spans_hip, tone_hip
-    _lib_built()
-    raw = open(os.path.join(ROOT, "include", "vvplategrain.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = re.findall(r"\b(vvl_[a-z0-9_]+)\s*\(", src)
-    protos = {}
-    for ret, name, args in re.findall(r"^\s*(int|const char\*)\s+(vvl_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        args = [" ".join(a.split()) for a in args.split(",")]
-        args = [] if args in (["void"], [""]) else args
-        protos[name] = (ctypes.c_int if ret == "int" else ctypes.c_char_p, [ctypes.c_void_p if "*" in a else CTYPE_OF[a.rsplit(" ", 1)[0]] for a in args])
-    assert list(protos) == declared == list(plategrain_hip.SIGNATURES) == plategrain_hip.EXPORTS == ["vvl_abi_version", "vvl_last_error", "vvl_sources"]
-    assert not re.findall(r"\bvv[a-km-z]?_[a-z0-9_]+\s*\(", src)                                      # no other unit's function is declared here
-    others = (hip, spans_hip, mask_hip, tone_hip, grain_hip, blend_hip, plate_hip, align_hip, flicker_hip, flickalign_hip)
-    for unit in others:
-        assert not any(name.startswith("vvl_") for name in unit.SIGNATURES), unit.__name__
-        assert not set(unit.SIGNATURES) & set(plategrain_hip.SIGNATURES)
-    loaded = plategrain_hip.lib()
-    for name, (restype, argtypes) in protos.items():
-        fn = getattr(loaded, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, (name, fn.restype, fn.argtypes)
-        assert (restype, tuple(argtypes)) == (plategrain_hip.SIGNATURES[name][0], tuple(plategrain_hip.SIGNATURES[name][1]))
+    has applied it, the version and the limits agree (abiref.check_binding; test_abi_cpu.py: the vvl_ prefix belongs to no other part)."""
+    from videovanish_amd import plate_hip, plategrain_hip
+    loaded, define = abiref.check_binding(plategrain_hip, 3)
+    assert plategrain_hip.EXPORTS == ["vvl_abi_version", "vvl_last_error", "vvl_sources"] and define("VVL_ABI_VERSION") == 1
     # vvp_sources' arguments, then depth and reach, and one more output plane
-    assert protos["vvl_sources"][1] == list(plate_hip.lib().vvp_sources.argtypes[:14]) + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 4
-    define = lambda name: int(re.search(rf"#define {name} (\d+)", raw).group(1))
-    assert loaded.vvl_abi_version() == define("VVL_ABI_VERSION") == plategrain_hip.ABI_VERSION == 1
+    assert list(loaded.vvl_sources.argtypes) == list(plate_hip.lib().vvp_sources.argtypes[:14]) + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 4
     assert (define("VVL_MAX_DEPTH"), define("VVL_MAX_REACH")) == (plategrain_hip.MAX_DEPTH, plategrain_hip.MAX_REACH) == (PG.MAX_DEPTH, PG.MAX_REACH) == (8, 65535)
 
 
@@ -96,7 +68,7 @@ def test_refusals_through_the_library():
     """Every refusal of vvl_sources: vvp_sources' own, then depth, reach and a null live; each names vvl_sources.  Nothing can be launched here:
     every pointer is host memory and every call is refused before the first device call."""
     from videovanish_amd import plategrain_hip
-    _lib_built()
+    abiref.built()
     loaded = plategrain_hip.lib()
     buf = (ctypes.c_char * 64)()
     a = ctypes.addressof(buf)
@@ -126,16 +98,12 @@ def test_refusals_through_the_library():
 def test_product_sources_of_the_feature():
     """The kernel lives in vv_plate.hip with the new header among the recipe's dependencies and reads no environment; the settings import no
     torch; importing the drop-in resolves no vvl_ symbol."""
-    csrc = os.path.join(ROOT, "videovanish_amd", "csrc")
-    recipe = open(os.path.join(csrc, "build.sh")).read()
-    assert re.search(r"\bvv_plate\b", recipe) and "include/vvplategrain.h" in recipe and "include/vvplate.h" in recipe
-    kernel = open(os.path.join(csrc, "vv_plate.hip")).read()
-    assert "getenv" not in kernel and "vvplategrain.h" in kernel and 'extern "C" int vvl_sources(' in kernel
+    kernel, txt = abiref.check_sources("vv_plate", "vvplategrain.h", "plategrain")
+    assert "include/vvplate.h" in open(os.path.join(abiref.CSRC, "build.sh")).read() and 'extern "C" int vvl_sources(' in kernel
     assert kernel.count("void sources_kernel(") == 1                                                 # one body for vvp_sources and vvl_sources
-    txt = open(os.path.join(ROOT, "videovanish_amd", "plategrain.py")).read()
-    assert "import torch" not in txt and "from torch" not in txt and "numpy" not in txt and "oracle" not in txt
+    assert "numpy" not in txt
     code = ("import diffuerase; from videovanish_amd import plategrain_hip, plate_hip, hip; "
-            "assert plategrain_hip._lib is None and plate_hip._lib is None and hip._lib is None; "
+            "assert plategrain_hip.PART.dll is None and plate_hip.PART.dll is None and hip.CORE.dll is None; "
             "assert diffuerase.plate_grain_config() is None and diffuerase.last_plate_grain is None")
     env = {k: v for k, v in os.environ.items() if k not in ("VV_PLATE_GRAIN", "VV_PLATE_FILL")}
     subprocess.check_call([sys.executable, "-c", code], cwd=ROOT, env=env)

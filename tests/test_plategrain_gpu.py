@@ -329,9 +329,9 @@ def test_drop_in_equals_the_call_on_the_restatement(gpu, still_clip, monkeypatch
     else:
         # depth = 1: the bytes of plate_fill alone, and plategrain_hip stays unresolved
         from videovanish_amd import plategrain_hip
-        monkeypatch.setattr(plategrain_hip, "_lib", None)
+        monkeypatch.setattr(plategrain_hip.PART, "dll", None)
         one, rep1, grep1 = _run(frames, masks, prior, plate_fill="on", plate_grain="depth=1")
-        assert plategrain_hip._lib is None and not grep1.rotated.any() and (grep1.filled == rep1.filled).all()
+        assert plategrain_hip.PART.dll is None and not grep1.rotated.any() and (grep1.filled == rep1.filled).all()
         alone, rep0, none = _run(frames, masks, prior, plate_fill="on")
         assert none is None and _same(one, alone) and not _same(out, alone)
         assert all((a == b).all() if isinstance(a, np.ndarray) else a == b for a, b in zip(rep0, rep1))

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abiref  # noqa: E402
 import grainmatch_ref as GR  # noqa: E402
 import seamblend_ref as R  # noqa: E402
 import tonematch_ref as TR  # noqa: E402
@@ -59,39 +60,14 @@ def test_spellings_and_config():
 
 
 # ---- binding ------------------------------------------------------------------------------------------------------------------------------
-CTYPE_OF = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
-RET_OF = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char*": ctypes.c_char_p}
-
-
 def test_binding_matches_vvblend_header():
     """blend_hip.SIGNATURES declares every function of include/vvblend.h with the header's types and in its order, blend_hip.lib() has applied it,
-    the version and the limits agree, no name of the header could be taken for one of the other headers', the formulas of the field stand in
-    the header, and the arguments are validated before any device work, each refusal naming its function."""
-    from videovanish_amd import blend_hip, grain_hip, hip, mask_hip, spans_hip, tone_hip
-    if not os.path.isfile(os.path.join(ROOT, "videovanish_amd", "csrc", "libvvhip.so")):
-        import __graft_entry__
-        __graft_entry__.build()
+    the version and the limits agree (abiref.check_binding; test_abi_cpu.py: no name could be taken for another part's), the formulas of the
+    field stand in the header, and the arguments are validated before any device work, each refusal naming its function."""
+    from videovanish_amd import blend_hip
+    loaded, define = abiref.check_binding(blend_hip, 9)
     raw = open(os.path.join(ROOT, "include", "vvblend.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = sorted(set(re.findall(r"\b(vvb_[a-z0-9_]+)\s*\(", src)))
-    protos = {}
-    for ret, name, args in re.findall(r"^\s*(int|int64_t|const char\*)\s+(vvb_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        args = [" ".join(a.split()) for a in args.split(",")]
-        args = [] if args in (["void"], [""]) else args
-        protos[name] = (RET_OF[ret], [ctypes.c_void_p if "*" in a else CTYPE_OF[a.rsplit(" ", 1)[0]] for a in args])
-    assert sorted(protos) == declared == sorted(blend_hip.SIGNATURES) == sorted(blend_hip.EXPORTS) and len(protos) == 9
-    assert list(blend_hip.SIGNATURES) == re.findall(r"\b(vvb_[a-z0-9_]+)\s*\(", src)                  # in the header's order
-    for prefix in ("vv", "vvs", "vvm", "vvt", "vvg"):
-        assert not re.findall(rf"\b{prefix}_[a-z0-9_]+\s*\(", src), prefix
-    others = set(hip.SIGNATURES) | set(spans_hip.SIGNATURES) | set(mask_hip.SIGNATURES) | set(tone_hip.SIGNATURES) | set(grain_hip.SIGNATURES)
-    assert not set(blend_hip.SIGNATURES) & others
-    loaded = blend_hip.lib()
-    for name, (restype, argtypes) in protos.items():
-        fn = getattr(loaded, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, (name, fn.restype, fn.argtypes)
-        assert (restype, tuple(argtypes)) == (blend_hip.SIGNATURES[name][0], tuple(blend_hip.SIGNATURES[name][1]))
-    define = lambda name: int(re.search(rf"#define {name} (\d+)", raw).group(1))
-    assert loaded.vvb_abi_version() == define("VVB_ABI_VERSION") == blend_hip.ABI_VERSION == 1
+    assert define("VVB_ABI_VERSION") == 1
     assert define("VVB_MAX_RING") == M.MAX_RING == 32 and define("VVB_MAX_PRESMOOTH") == M.MAX_PRESMOOTH == 4
     assert define("VVB_MAX_SWEEPS") == M.MAX_SWEEPS == 16 and define("VVB_MAX_SHIFT") == M.MAX_SHIFT == 255
     assert define("VVB_NSUM") == blend_hip.NSUM == M.NSUM == 11 and define("VVB_MAX_STRENGTH_Q8") == SeamBlendConfig(strength=2).strength_q8
@@ -158,19 +134,15 @@ def test_binding_matches_vvblend_header():
 def test_product_sources_of_the_feature():
     """vv_blend is in the one build recipe with its header among the dependencies and reads no environment; the ring and the noise have one
     statement each, which their users include; the settings import no torch; importing the drop-in resolves no symbol of the feature."""
-    csrc = os.path.join(ROOT, "videovanish_amd", "csrc")
-    recipe = open(os.path.join(csrc, "build.sh")).read()
-    assert re.search(r"\bvv_blend\b", recipe) and "include/vvblend.h" in recipe
-    blend, grain, paste = (open(os.path.join(csrc, f)).read() for f in ("vv_blend.hip", "vv_grain.hip", "vv_paste_px.h"))
-    assert "getenv" not in blend and "getenv" not in paste
+    blend, _ = abiref.check_sources("vv_blend", "vvblend.h", "seamblend")
+    grain, paste = (open(os.path.join(abiref.CSRC, f)).read() for f in ("vv_grain.hip", "vv_paste_px.h"))
+    assert "getenv" not in paste
     assert '#include "vv_ring_bits.h"' in blend and "vvring::ring_bits<" in blend and "__ballot" not in blend
     for user in (blend, grain):
         assert '#include "vv_paste_px.h"' in user and "vvpaste::grain_px(" in user and "0x9E3779B97F4A7C15" not in user and "5017" not in user
     assert paste.count("0x9E3779B97F4A7C15") == 1 and paste.count("5017 + (1 << 23)) >> 24") == 1
-    txt = open(os.path.join(ROOT, "videovanish_amd", "seamblend.py")).read()
-    assert "import torch" not in txt and "from torch" not in txt and "oracle" not in txt
     code = ("import diffuerase; from videovanish_amd import blend_hip, grain_hip, tone_hip, hip, seamblend; "
-            "assert blend_hip._lib is None and grain_hip._lib is None and tone_hip._lib is None and hip._lib is None; "
+            "assert blend_hip.PART.dll is None and grain_hip.PART.dll is None and tone_hip.PART.dll is None and hip.CORE.dll is None; "
             "assert diffuerase.last_seam_blend is None")
     subprocess.check_call([sys.executable, "-c", code], cwd=ROOT)
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abiref  # noqa: E402
 import platefill_ref as P  # noqa: E402
 import shadowmask_ref as R  # noqa: E402
 
@@ -57,36 +58,13 @@ def test_widen_box():
 
 
 # ---- binding ------------------------------------------------------------------------------------------------------------------------------
-CTYPE_OF = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
-
-
 def test_binding_matches_vvshadow_header():
     """shadow_hip.SIGNATURES declares every function of include/vvshadow.h with the header's types, shadow_hip.lib() has applied it, the version
-    and the range constants agree, no name could be taken for another unit's, and arguments are refused before anything touches a device."""
-    from videovanish_amd import blend_hip, hip, mask_hip, plate_hip, shadow_hip, spans_hip
-    if not os.path.isfile(os.path.join(ROOT, "videovanish_amd", "csrc", "libvvhip.so")):
-        import __graft_entry__
-        __graft_entry__.build()
-    raw = open(os.path.join(ROOT, "include", "vvshadow.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = sorted(set(re.findall(r"\b(vvh_[a-z0-9_]+)\s*\(", src)))
-    protos = {}
-    for ret, name, args in re.findall(r"^\s*(int|const char\*)\s+(vvh_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        args = [" ".join(a.split()) for a in args.split(",")]
-        args = [] if args in (["void"], [""]) else args
-        protos[name] = (ctypes.c_int if ret == "int" else ctypes.c_char_p, [ctypes.c_void_p if "*" in a else CTYPE_OF[a.rsplit(" ", 1)[0]] for a in args])
-    assert sorted(protos) == declared == sorted(shadow_hip.SIGNATURES) == sorted(shadow_hip.EXPORTS) and len(protos) == 6
-    assert list(shadow_hip.SIGNATURES) == re.findall(r"\b(vvh_[a-z0-9_]+)\s*\(", src)                 # in the header's order
-    assert not re.findall(r"\bvv[a-gi-z]?_[a-z0-9_]+\s*\(", src)
-    others = set(hip.SIGNATURES) | set(spans_hip.SIGNATURES) | set(mask_hip.SIGNATURES) | set(blend_hip.SIGNATURES) | set(plate_hip.SIGNATURES)
-    assert not set(shadow_hip.SIGNATURES) & others and not [n for n in others if n.startswith("vvh_")]
-    loaded = shadow_hip.lib()
-    for name, (restype, argtypes) in protos.items():
-        fn = getattr(loaded, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, (name, fn.restype, fn.argtypes)
-        assert (restype, tuple(argtypes)) == (shadow_hip.SIGNATURES[name][0], tuple(shadow_hip.SIGNATURES[name][1]))
-    define = lambda name: int(re.search(rf"#define {name} (\d+)", raw).group(1))
-    assert loaded.vvh_abi_version() == define("VVH_ABI_VERSION") == shadow_hip.ABI_VERSION == 1
+    and the range constants agree (abiref.check_binding; test_abi_cpu.py: no name could be taken for another part's), and arguments are refused
+    before anything touches a device."""
+    from videovanish_amd import mask_hip, shadow_hip
+    loaded, define = abiref.check_binding(shadow_hip, 6)
+    assert define("VVH_ABI_VERSION") == 1
     limits = tuple(define("VVH_MAX_" + k) for k in ("T", "GUARD", "TOL", "DROP", "CHROMA", "FLOOR", "REACH", "GROW"))
     assert limits == (shadow_hip.MAX_T, shadow_hip.MAX_GUARD, shadow_hip.MAX_TOL, shadow_hip.MAX_DROP, shadow_hip.MAX_CHROMA, shadow_hip.MAX_FLOOR,
                       shadow_hip.MAX_REACH, shadow_hip.MAX_GROW) == (65535, 8, 255, 255, 100, 255, 64, 16)
@@ -125,14 +103,9 @@ def test_binding_matches_vvshadow_header():
 def test_product_sources_of_the_feature():
     """vv_shadow is in the one build recipe with its header among the dependencies and reads no environment; the settings import neither torch nor
     numpy; importing the drop-in resolves no symbol of the feature, and neither does a call's set-up without the option."""
-    csrc = os.path.join(ROOT, "videovanish_amd", "csrc")
-    recipe = open(os.path.join(csrc, "build.sh")).read()
-    assert re.search(r"\bvv_shadow\b", recipe) and "include/vvshadow.h" in recipe
-    kernel = open(os.path.join(csrc, "vv_shadow.hip")).read()
-    assert "getenv" not in kernel and "vvshadow.h" in kernel
-    txt = open(os.path.join(ROOT, "videovanish_amd", "shadowmask.py")).read()
+    _, txt = abiref.check_sources("vv_shadow", "vvshadow.h", "shadowmask")
     assert not re.search(r"^\s*(import|from)\s+(torch|numpy|oracle)\b", txt, flags=re.M)
-    code = ("import sys, diffuerase; from videovanish_amd import shadow_hip, hip; assert shadow_hip._lib is None and hip._lib is None; "
+    code = ("import sys, diffuerase; from videovanish_amd import shadow_hip, hip; assert shadow_hip.PART.dll is None and hip.CORE.dll is None; "
             "assert diffuerase.shadow_mask_config() is None and diffuerase.last_shadow_mask is None; "
             "import videovanish_amd.shadowmask")
     env = {k: v for k, v in os.environ.items() if k != "VV_SHADOW_MASK"}

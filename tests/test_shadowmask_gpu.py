@@ -109,7 +109,7 @@ def test_shadow_mask_alone_and_with_cuts(gpu, cuts):
     pd = _d(pm, gpu)
     got, rep = infill.shadow_mask(list(pf), pd, ShadowMaskConfig(), cuts)
     assert got is pd and not rep.added.any()
-    assert shadow_hip._lib is not None
+    assert shadow_hip.PART.dll is not None
 
 
 # ---- vvh_grow at its edges ----------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,6 @@ restatement of the device statistics: tests/spans_ref.py), the drop-in's orchest
 binding of include/vvspans.h."""
 import ctypes
 import os
-import re
 import sys
 import types
 
@@ -11,6 +10,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abiref  # noqa: E402
 import spans_ref as R  # noqa: E402
 
 from videovanish_amd import spans as S  # noqa: E402
@@ -351,36 +351,12 @@ def test_cli_spans_and_cuts_reach_the_call(cli):
         d.main()
 
 
-CTYPE_OF = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
-
-
 def test_binding_matches_vvspans_header():
-    """spans_hip.SIGNATURES declares every function of include/vvspans.h with the header's types, spans_hip.lib() has applied it, the versions agree,
-    and no name of the header could be taken for one of vvhip.h's (its scan is vv_[a-z0-9_]+ followed by a parenthesis)."""
-    from videovanish_amd import hip, spans_hip
-    lib_path = os.path.join(ROOT, "videovanish_amd", "csrc", "libvvhip.so")
-    if not os.path.isfile(lib_path):
-        import __graft_entry__
-        __graft_entry__.build()
-    raw = open(os.path.join(ROOT, "include", "vvspans.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = sorted(set(re.findall(r"\b(vvs_[a-z0-9_]+)\s*\(", src)))
-    protos = {}
-    for ret, name, args in re.findall(r"^\s*(int|const char\*)\s+(vvs_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        args = [" ".join(a.split()) for a in args.split(",")]
-        args = [] if args in (["void"], [""]) else args
-        protos[name] = (ctypes.c_int if ret == "int" else ctypes.c_char_p, [ctypes.c_void_p if "*" in a else CTYPE_OF[a.rsplit(" ", 1)[0]] for a in args])
-    assert sorted(protos) == declared == sorted(spans_hip.SIGNATURES) == sorted(spans_hip.EXPORTS) and len(protos) == 3
-    assert not re.findall(r"\bvv_[a-z0-9_]+\s*\(", src)
-    assert not set(spans_hip.SIGNATURES) & set(hip.SIGNATURES)
-    loaded = spans_hip.lib()
-    for name, (restype, argtypes) in protos.items():
-        fn = getattr(loaded, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, (name, fn.restype, fn.argtypes)
-        assert (restype, tuple(argtypes)) == (spans_hip.SIGNATURES[name][0], tuple(spans_hip.SIGNATURES[name][1]))
-    ver = int(re.search(r"#define VVS_ABI_VERSION (\d+)", raw).group(1))
-    assert loaded.vvs_abi_version() == ver == spans_hip.ABI_VERSION
-    assert int(re.search(r"#define VVS_HIST_BINS (\d+)", raw).group(1)) == spans_hip.HIST_BINS == R.BINS
+    """spans_hip.SIGNATURES declares every function of include/vvspans.h with the header's types, spans_hip.lib() has applied it, the versions agree
+    (abiref.check_binding; test_abi_cpu.py: no name could be taken for another part's), and arguments are refused before anything touches a device."""
+    from videovanish_amd import spans_hip
+    loaded, define = abiref.check_binding(spans_hip, 3)
+    assert define("VVS_HIST_BINS") == spans_hip.HIST_BINS == R.BINS
     # arguments are validated before anything touches a device
     assert loaded.vvs_frame_pair_stats(None, None, 4, 8, 8, None, None, None) == -1 and b"vvs_frame_pair_stats" in loaded.vvs_last_error()
     buf = (ctypes.c_char * 64)()
@@ -395,8 +371,4 @@ def test_binding_matches_vvspans_header():
 
 def test_product_sources_of_the_feature():
     """vv_spans is in the one build recipe and reads no environment; the planner imports no torch."""
-    csrc = os.path.join(ROOT, "videovanish_amd", "csrc")
-    assert re.search(r"\bvv_spans\b", open(os.path.join(csrc, "build.sh")).read())
-    assert "getenv" not in open(os.path.join(csrc, "vv_spans.hip")).read()
-    txt = open(os.path.join(ROOT, "videovanish_amd", "spans.py")).read()
-    assert "import torch" not in txt and "from torch" not in txt and "oracle" not in txt
+    abiref.check_sources("vv_spans", "vvspans.h", "spans")

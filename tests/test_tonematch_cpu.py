@@ -3,7 +3,6 @@ host code against the restatement of tests/tonematch_ref.py, bit for bit in the 
 alone, configuration and CLI."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 import types
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abiref  # noqa: E402
 import tonematch_ref as R  # noqa: E402
 
 from videovanish_amd import tonematch as M  # noqa: E402
@@ -51,36 +51,13 @@ def test_spellings_and_config():
 
 
 # ---- binding ------------------------------------------------------------------------------------------------------------------------------
-CTYPE_OF = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
-
-
 def test_binding_matches_vvtone_header():
     """tone_hip.SIGNATURES declares every function of include/vvtone.h with the header's types, tone_hip.lib() has applied it, the version and the
-    limit agree, no name of the header could be taken for one of the other headers', and the arguments are validated before any device work."""
-    from videovanish_amd import hip, mask_hip, spans_hip, tone_hip
-    if not os.path.isfile(os.path.join(ROOT, "videovanish_amd", "csrc", "libvvhip.so")):
-        import __graft_entry__
-        __graft_entry__.build()
-    raw = open(os.path.join(ROOT, "include", "vvtone.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    declared = sorted(set(re.findall(r"\b(vvt_[a-z0-9_]+)\s*\(", src)))
-    protos = {}
-    for ret, name, args in re.findall(r"^\s*(int|const char\*)\s+(vvt_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src, flags=re.M):
-        args = [" ".join(a.split()) for a in args.split(",")]
-        args = [] if args in (["void"], [""]) else args
-        protos[name] = (ctypes.c_int if ret == "int" else ctypes.c_char_p, [ctypes.c_void_p if "*" in a else CTYPE_OF[a.rsplit(" ", 1)[0]] for a in args])
-    assert sorted(protos) == declared == sorted(tone_hip.SIGNATURES) == sorted(tone_hip.EXPORTS) and len(protos) == 4
-    assert list(tone_hip.SIGNATURES) == re.findall(r"\b(vvt_[a-z0-9_]+)\s*\(", src)                   # in the header's order
-    for prefix in ("vv", "vvs", "vvm"):
-        assert not re.findall(rf"\b{prefix}_[a-z0-9_]+\s*\(", src), prefix
-    assert not set(tone_hip.SIGNATURES) & (set(hip.SIGNATURES) | set(spans_hip.SIGNATURES) | set(mask_hip.SIGNATURES))
-    loaded = tone_hip.lib()
-    for name, (restype, argtypes) in protos.items():
-        fn = getattr(loaded, name)
-        assert fn.restype is restype and list(fn.argtypes) == argtypes, (name, fn.restype, fn.argtypes)
-        assert (restype, tuple(argtypes)) == (tone_hip.SIGNATURES[name][0], tuple(tone_hip.SIGNATURES[name][1]))
-    define = lambda name: int(re.search(rf"#define {name} (\d+)", raw).group(1))
-    assert loaded.vvt_abi_version() == define("VVT_ABI_VERSION") == tone_hip.ABI_VERSION == 1
+    limit agree (abiref.check_binding; test_abi_cpu.py: no name could be taken for another part's), and the arguments are validated before any
+    device work."""
+    from videovanish_amd import tone_hip
+    loaded, define = abiref.check_binding(tone_hip, 4)
+    assert define("VVT_ABI_VERSION") == 1
     assert define("VVT_MAX_RING") == tone_hip.MAX_RING == M.MAX_RING == 32
     # arguments are validated before anything touches a device: -1 null pointers and sizes, -2 the ring and the feather
     buf = (ctypes.c_char * 64)()
@@ -113,13 +90,8 @@ def test_binding_matches_vvtone_header():
 def test_product_sources_of_the_feature():
     """vv_tone is in the one build recipe with its header among the dependencies and reads no environment; the settings import no torch; importing
     the drop-in resolves no symbol of the feature."""
-    csrc = os.path.join(ROOT, "videovanish_amd", "csrc")
-    recipe = open(os.path.join(csrc, "build.sh")).read()
-    assert re.search(r"\bvv_tone\b", recipe) and "include/vvtone.h" in recipe
-    assert "getenv" not in open(os.path.join(csrc, "vv_tone.hip")).read()
-    txt = open(os.path.join(ROOT, "videovanish_amd", "tonematch.py")).read()
-    assert "import torch" not in txt and "from torch" not in txt and "oracle" not in txt
-    code = ("import diffuerase; from videovanish_amd import tone_hip, hip, tonematch; assert tone_hip._lib is None and hip._lib is None; "
+    abiref.check_sources("vv_tone", "vvtone.h", "tonematch")
+    code = ("import diffuerase; from videovanish_amd import tone_hip, hip, tonematch; assert tone_hip.PART.dll is None and hip.CORE.dll is None; "
             "assert diffuerase.last_tone_match is None")
     subprocess.check_call([sys.executable, "-c", code], cwd=ROOT)
 

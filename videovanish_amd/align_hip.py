@@ -1,8 +1,8 @@
 """ctypes binding of the clean-plate alignment entry points of libvvhip.so (include/vvalign.h; kernels: csrc/vv_align.hip).
 
-Built on hip.py, as plate_hip.py is: the same library handle, device / contiguity checks and stream; the ABI of vvalign.h is declared once, in
-SIGNATURES, and applied when the library is first used through this module.  tests/test_platealign_cpu.py holds the table against the header.
-No fallback: a missing symbol or a launcher's error raises RuntimeError.
+Built on hip.py: PART (a hip.Part) declares vvalign.h's part of the library once, SIGNATURES is applied when the library is first used through this
+module, and the handle, the device / contiguity checks and the stream are hip's.  tests/test_platealign_cpu.py checks the table against the header
+(tests/abiref.py).  No fallback: a missing symbol or a launcher's error raises RuntimeError.
 """
 import ctypes as C
 
@@ -30,18 +30,11 @@ SIGNATURES = {
     "vva_unplace_mask": (I, (P, P, P, I, I, I, I, I, I, I, P, P)),
 }
 EXPORTS = list(SIGNATURES)
-_lib = None
+PART = hip.Part("vvalign.h", "vva_", ABI_VERSION, "clean-plate alignment", SIGNATURES)
+lib = PART.lib
 
 
-def lib():
-    """hip.lib() with the signatures of vvalign.h applied (once)."""
-    global _lib
-    if _lib is None:
-        _lib = hip.bind(hip.lib(), SIGNATURES, "vva_abi_version", ABI_VERSION, "clean-plate alignment")
-    return _lib
-
-
-def _check(rc, what):
+def _check(rc, what):      # not PART.check: vva_frame_bytes and vva_track_launches answer with a count, so only rc < 0 is an error and rc is handed on
     if rc < 0:
         raise RuntimeError(f"{what} failed ({rc}): {lib().vva_last_error().decode()}")
     return rc

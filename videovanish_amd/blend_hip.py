@@ -1,17 +1,15 @@
 """ctypes binding of the seam membrane blending entry points of libvvhip.so (include/vvblend.h; kernels: csrc/vv_blend.hip).
 
-Built on hip.py, as tone_hip.py and grain_hip.py are: the same library handle, device / contiguity checks and stream; the ABI of vvblend.h is
-declared once, in SIGNATURES, and applied when the library is first used through this module.  tests/test_seamblend_cpu.py holds the table
-against the header.  No fallback: a missing symbol or a launcher's error raises RuntimeError.
+Built on hip.py: PART (a hip.Part) declares vvblend.h's part of the library once, SIGNATURES is applied when the library is first used through this
+module, and the handle, the device / contiguity checks and the stream are hip's.  tests/test_seamblend_cpu.py checks the table against the header
+(tests/abiref.py).  No fallback: a missing symbol or a launcher's error raises RuntimeError.
 """
 import ctypes as C
 
 import torch
 
 from . import hip, seamblend
-from .grain_hip import _need_table
 from .hip import I, P      # the ctypes shorthands of hip.SIGNATURES
-from .tone_hip import _need_window
 
 ABI_VERSION = 1
 NSUM = 11
@@ -30,19 +28,8 @@ SIGNATURES = {
     "vvb_paste_blend_composite": (I, (P, I, I, P, P, P, P, P, I, P, P, I, I, I, I, I, I, I, C.c_float, P, P)),
 }
 EXPORTS = list(SIGNATURES)
-_lib = None
-
-
-def lib():
-    """hip.lib() with the signatures of vvblend.h applied (once)."""
-    global _lib
-    if _lib is None:
-        _lib = hip.bind(hip.lib(), SIGNATURES, "vvb_abi_version", ABI_VERSION, "seam blending")
-    return _lib
-
-
-def _check(rc, what):
-    hip.check(rc, what, lib, "vvb_last_error")
+PART = hip.Part("vvblend.h", "vvb_", ABI_VERSION, "seam blending", SIGNATURES)
+lib, _check = PART.lib, PART.check
 
 
 def scratch_bytes(T, h, w):
@@ -63,8 +50,8 @@ def ring_diff(patch, orig, mask2d, offsets, lut, h, w, ring, presmooth, max_shif
     if mask2d is None:
         raise RuntimeError("ring_diff: the ring needs mask2d")
     hip._need_cuda(lut)
-    T, Hm, Wm, H0, W0 = _need_window("ring_diff", patch, orig, mask2d, offsets)
-    _need_table("ring_diff", "lut", lut, T)
+    T, Hm, Wm, H0, W0 = hip._need_window("ring_diff", patch, orig, mask2d, offsets)
+    hip._need_table("ring_diff", "lut", lut, T)
     h, w = int(h), int(w)
     if h < 1 or w < 1:
         raise RuntimeError("ring_diff: the window must hold a pixel")
@@ -113,8 +100,8 @@ def solve(patch, orig, mask2d, offsets, lut, h, w, ring, presmooth, sweeps, max_
     if mask2d is None:
         raise RuntimeError("solve: the ring needs mask2d")
     hip._need_cuda(lut, scratch)
-    T, Hm, Wm, H0, W0 = _need_window("solve", patch, orig, mask2d, offsets)
-    _need_table("solve", "lut", lut, T)
+    T, Hm, Wm, H0, W0 = hip._need_window("solve", patch, orig, mask2d, offsets)
+    hip._need_table("solve", "lut", lut, T)
     h, w = int(h), int(w)
     if h < 1 or w < 1:
         raise RuntimeError("solve: the window must hold a pixel")
@@ -135,17 +122,14 @@ def paste_blend_composite(patch, orig, mask2d, offsets, lut, field, strength_q8,
     """grain_hip.paste_grain_composite with the membrane: after lut and before the grain, channel c of a pixel of the window gets
     (field * strength_q8 + 2^13) >> 14 added (field [T,h,w,3] int16, Q6).  A zero field gives paste_grain_composite's bytes."""
     hip._need_cuda(lut, field, amp, frame_ids, out)
-    T, Hm, Wm, H0, W0 = _need_window("paste_blend_composite", patch, orig, mask2d, offsets)
-    _need_table("paste_blend_composite", "lut", lut, T)
-    _need_table("paste_blend_composite", "amp", amp, T)
+    T, Hm, Wm, H0, W0 = hip._need_window("paste_blend_composite", patch, orig, mask2d, offsets)
+    hip._need_table("paste_blend_composite", "lut", lut, T)
+    hip._need_table("paste_blend_composite", "amp", amp, T)
     if field.dtype != torch.int16 or tuple(field.shape) != (T, int(h), int(w), 3):
         raise RuntimeError("paste_blend_composite: field must be a [T, h, w, 3] int16 tensor")
     if frame_ids.dtype != torch.int32 or tuple(frame_ids.shape) != (T,):
         raise RuntimeError("paste_blend_composite: frame_ids must be a [T] int32 tensor")
-    if out is None:
-        out = torch.empty_like(orig)
-    elif out.shape != orig.shape or out.dtype != torch.uint8 or out.data_ptr() == orig.data_ptr():
-        raise RuntimeError("paste_blend_composite: out must be a contiguous u8 buffer of orig's shape, not orig itself")
+    out = hip._out_like("paste_blend_composite", out, orig, "orig")
     with hip._Prof("blend_paste_composite", 0.0, T * H0 * W0 * (3 + 1 + 3) + patch.numel() + field.numel() * 2):
         _check(lib().vvb_paste_blend_composite(hip._p(patch), Hm, Wm, hip._p(orig), hip._p(mask2d), hip._p(offsets), hip._p(lut), hip._p(field),
                                                int(strength_q8), hip._p(amp), hip._p(frame_ids), int(seed), int(mode), T, H0, W0, int(h), int(w),

@@ -11,10 +11,14 @@
 //   vva_place_masks    frame masks -> canvas masks and the canvas' invalid plane
 //   vva_unplace_mask   canvas masks -> frame masks
 #include "vv_common.h"
+#include "vv_wave_bytes.h"
 #include "../../include/vvalign.h"
 
 namespace {
 
+using vvwave::U3;
+using vvwave::luma;
+using vvwave::wave_sum;
 constexpr int PB = 256;                      // threads per block of the streaming kernels
 constexpr int TW = 64, TH = 16;              // vva_sad: the tile of frame t's plane a block owns; 256 threads x 4 adjacent pixels
 constexpr int MAXR = VVA_MAX_RADIUS;
@@ -26,14 +30,10 @@ typedef unsigned long long u64;
 static_assert(TW * TH == PB * 4, "4 pixels per thread");
 static_assert(TW * TH * 255 < (1 << 20) && TW * TH < (1 << 11), "a block's sad and n share 32 bits");
 
-struct __attribute__((aligned(4))) U3 { unsigned a, b, c; };
-
 struct Geo {
     int Hl[VVA_MAX_LEVELS + 1], Wl[VVA_MAX_LEVELS + 1];
     int64_t o[VVA_MAX_LEVELS + 1], S;
 };
-
-__device__ __forceinline__ unsigned luma(unsigned r, unsigned g, unsigned b) { return (77u * r + 150u * g + 29u * b + 128u) >> 8; }
 
 // grid (ceil(units / PB), B): frame = blockIdx.y
 template <bool VEC>
@@ -76,12 +76,6 @@ __global__ __launch_bounds__(PB) void down_kernel(uint8_t* pyr, int64_t S, int64
     const unsigned s = (unsigned)py[0] + py[1] + py[Wp] + py[Wp + 1] + 2u;
     rec[ol + i] = (uint8_t)(s >> 2);
     rec[ol + (int64_t)Hl * Wl + i] = (pv[0] & pv[1] & pv[Wp] & pv[Wp + 1]) ? 1 : 0;
-}
-
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // grid (ceil(Wl / TW), ceil(Hl / TH)).  o = the level's place in a frame's record.

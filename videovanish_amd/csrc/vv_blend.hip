@@ -9,11 +9,14 @@
 // The sums go registers -> wave reduction -> 64-bit LDS atomics -> one set of 64-bit global integer atomics per block, as in vv_tone.hip.
 #include "vv_paste_px.h"
 #include "vv_ring_bits.h"
+#include "vv_wave_bytes.h"
 #include "../../include/vvblend.h"
 #pragma clang fp contract(off)
 
 namespace {
 
+using vvwave::wave_max;
+using vvwave::wave_sum;
 using vvring::TB;
 using vvring::TW;
 using vvring::TH;
@@ -27,16 +30,6 @@ static_assert(VVB_MAX_RING == vvring::MAX_RING, "the ring of vv_ring_bits.h");
 static_assert(64ull * (TH / 4) * 255ull * 255ull < (1ull << 32) && 64ull * (TH / 4) * 64ull * VVB_MAX_SHIFT < (1ull << 32), "32-bit sums up to the wave");
 static_assert(64 * VVB_MAX_SHIFT <= 32767, "the field is int16");
 
-__device__ __forceinline__ unsigned wave_sum32(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned wave_max32(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor(v, o, 64));
-    return v;
-}
 // (2 s + n) // (2 n), the floor division, n > 0
 __device__ __forceinline__ int round_div(int s, int n) {
     const int num = 2 * s + n, den = 2 * n;
@@ -143,7 +136,7 @@ __global__ __launch_bounds__(TB) void ring_diff_kernel(const uint8_t* __restrict
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const unsigned s = wave_sum32(acc[i]);
+        const unsigned s = wave_sum(acc[i]);
         if (lane == 0 && s) atomicAdd(&tot[i], (u64)s);
     }
     __syncthreads();
@@ -276,11 +269,11 @@ __global__ __launch_bounds__(TB) void relax_kernel(const uint8_t* __restrict__ c
         }
     if (!sums) return;                                                         // block-uniform
     {
-        const unsigned c = wave_sum32(cnt);
+        const unsigned c = wave_sum(cnt);
         if (lane == 0 && c) atomicAdd(&tot[0], (u64)c);
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
-            const unsigned sm = wave_sum32(sa[ch]), m = wave_max32(mx[ch]);
+            const unsigned sm = wave_sum(sa[ch]), m = wave_max(mx[ch]);
             if (lane == 0 && sm) { atomicAdd(&tot[1 + ch], (u64)sm); atomicMax(&tot[4 + ch], (u64)m); }
         }
     }

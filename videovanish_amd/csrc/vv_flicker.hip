@@ -14,19 +14,20 @@
 // The sums go registers (packed in 16-bit halves) -> wave reduction -> LDS -> one group of 64-bit global atomics per block, as in vv_tone.hip:
 // integer adds in any order.  out_c = (2 S_c + n) / (2 n) is a multiplication by a 20-bit reciprocal, exact for every S_c <= 255 n, n <= 9.
 #include "vv_paste_px.h"
+#include "vv_wave_bytes.h"
 #include "../../include/vvflicker.h"
 #include "../../include/vvflickalign.h"
 
 namespace {
 
+using vvwave::U3;
+using vvwave::wave_sum;
 constexpr int FB = 256;                     // threads per block
 constexpr int NSUM = 12;
 typedef unsigned long long u64;
 static_assert(VVF_MAX_RADIUS == 4 && 2 * VVF_MAX_RADIUS + 1 <= 9, "n <= 9: the reciprocals, the packed sums");
 static_assert(VVC_MAX_RADIUS == VVF_MAX_RADIUS && VVC_MAX_T == VVF_MAX_T, "vvc_hold shares vvf_hold's limits");
 static_assert(64 * 4 * 255 < (1 << 16) && 64 * 4 * 9 < (1 << 16), "a wave's sums of 4 pixels per lane fit the 16-bit halves");
-
-struct __attribute__((aligned(4))) U3 { unsigned a, b, c; };
 
 // x / (2 n) == (x * recip(n)) >> 20 for every x <= 2 * 255 * n + n
 constexpr unsigned recip(unsigned n) { return (1u << 20) / (2u * n) + 1u; }
@@ -38,11 +39,6 @@ constexpr bool recip_exact() {
 }
 static_assert(recip_exact(), "the rounded mean by multiplication");
 
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ unsigned byte_of(const U3& q, int j) {       // byte j of the 12, j a constant
     const unsigned w = (j >> 2) == 0 ? q.a : (j >> 2) == 1 ? q.b : q.c;
     return (w >> ((j & 3) * 8)) & 255u;

@@ -11,11 +11,13 @@
 // vv_image_px.h, the window's pixel and the noise vv_paste_px.h (shared with vv_blend.hip), so a zero amplitude gives vvt_paste_lut_composite's bytes.
 #include "vv_paste_px.h"
 #include "vv_ring_bits.h"
+#include "vv_wave_bytes.h"
 #include "../../include/vvgrain.h"
 #pragma clang fp contract(off)
 
 namespace {
 
+using vvwave::wave_sum;
 using vvring::TB;
 using vvring::TW;
 using vvring::TH;
@@ -30,12 +32,6 @@ static_assert(NSUM == 3 * BANDS * 3 && BANDS == 4, "n, Sx, Sy per channel and ba
 static_assert(SP >= SW && SP % 4 == 0, "pitch");
 // |L| <= 8 * 255 = 2040; a thread adds ROWS_PER_THREAD squares, a wave 64 threads: the 32-bit wave sum holds
 static_assert(64ull * ROWS_PER_THREAD * 2040ull * 2040ull < (1ull << 32), "32-bit sums up to the wave");
-
-__device__ __forceinline__ unsigned wave_sum32(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // Immerkaer's operator, and max - min, on the 3 x 3 bytes round s (pitch SP)
 __device__ __forceinline__ int noise_op(const uint8_t* s) {
@@ -126,7 +122,7 @@ __global__ __launch_bounds__(TB) void ring_grain_stats_kernel(const uint8_t* __r
     if (any) {                                                                 // wave-uniform: `any` was set from LDS words every lane read
 #pragma unroll
         for (int i = 0; i < NSUM; ++i) {
-            const unsigned s = wave_sum32(acc[i]);
+            const unsigned s = wave_sum(acc[i]);
             if (lane == 0 && s) atomicAdd(&tot[i], (u64)s);
         }
     }

@@ -10,10 +10,12 @@
 // The time kernel keeps, per pixel, three small shift registers (input, dilated, closed) and reads every frame once: thread = 16 pixels with
 // 16-byte loads where H * W is a multiple of 16, else one pixel.
 #include "vv_common.h"
+#include "vv_wave_bytes.h"
 #include "../../include/vvmask.h"
 
 namespace {
 
+using vvwave::wave_sum;
 constexpr int MB = 256;                     // threads per block; a multiple of 64, and block b starts at pixel b * MB: lane = pixel index & 63
 
 __device__ __forceinline__ int ld_agent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -32,11 +34,6 @@ __device__ __forceinline__ void unite(int* L, int a, int b) {
         if (old == a) return;
         a = old;
     }
-}
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // grid (ceil(N / MB), S) for the per-pixel kernels below: frame = blockIdx.y, pixel i = blockIdx.x * MB + threadIdx.x < N

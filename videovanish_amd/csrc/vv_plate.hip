@@ -13,45 +13,26 @@
 // leaves it in src (at unmasked frames: the frame's own index where it is usable), so the backward walk reads src and dil only, no image byte.
 // The counts go registers -> wave reduction -> LDS -> one pair of 64-bit global atomics per block, as in vv_tone.hip: integer adds in any order.
 #include "vv_common.h"
+#include "vv_wave_bytes.h"
 #include "../../include/vvplate.h"
 #include "../../include/vvplategrain.h"
 #include <type_traits>
 
 namespace {
 
+using vvwave::load_mask;
+using vvwave::load_px;
+using vvwave::wave_sum;
 constexpr int PB = 256;                     // threads per block
 constexpr unsigned NONE = VVP_NO_SOURCE;
 typedef unsigned long long u64;
 static_assert((u64)VVP_MAX_T * 255 * 255 < (1ull << 32), "S2 in 32 bits");
-
-struct __attribute__((aligned(4))) U3 { unsigned a, b, c; };
 
 // the tile test: unit u's first pixel decides (VEC: the launcher made all P pixels share a row and a tile)
 __device__ __forceinline__ bool occupied(const uint8_t* occ, int64_t i0, int W, int tile, int tw) {
     if (!occ) return true;
     const int y = (int)(i0 / W), x = (int)(i0 % W);
     return occ[(int64_t)(y / tile) * tw + x / tile] != 0;
-}
-// the P mask bytes at m, byte p in bits 8 p ..
-template <bool VEC> __device__ __forceinline__ unsigned load_mask(const uint8_t* m) {
-    if constexpr (VEC) return *reinterpret_cast<const unsigned*>(m);
-    else return *m;
-}
-// the 3 P image bytes at px, as values
-template <bool VEC> __device__ __forceinline__ void load_px(const uint8_t* px, unsigned* v) {
-    if constexpr (VEC) {
-        const U3 q = *reinterpret_cast<const U3*>(px);
-        const unsigned w[3] = {q.a, q.b, q.c};
-#pragma unroll
-        for (int j = 0; j < 12; ++j) v[j] = (w[j >> 2] >> ((j & 3) * 8)) & 255u;
-    } else {
-        v[0] = px[0]; v[1] = px[1]; v[2] = px[2];
-    }
-}
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 template <bool VEC>

@@ -7,10 +7,13 @@
 // HBM-bound byte kernels, one thread per pixel, coalesced along x.  The per-pixel arithmetic is vv_image_px.h, the same statement
 // vv_resize_bilinear_u8 and vv_feather_composite use, so the fused paste equals that chain byte for byte.
 #include "vv_image_px.h"
+#include "vv_wave_bytes.h"
 #pragma clang fp contract(off)
 
 namespace {
 
+using vvwave::wave_max;
+using vvwave::wave_min;
 constexpr int EB = 256;
 
 // ---- bounding box -------------------------------------------------------------------------------------------
@@ -19,16 +22,6 @@ __global__ void bbox_init_kernel(int* bbox, int T, int H, int W) {
     const int t = blockIdx.x * EB + threadIdx.x;
     if (t >= T) return;
     bbox[t * 4 + 0] = H; bbox[t * 4 + 1] = W; bbox[t * 4 + 2] = 0; bbox[t * 4 + 3] = 0;
-}
-__device__ __forceinline__ int wave_min(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
 }
 // grid (row groups, T): block b of frame t scans rows b, b + gridDim.x, ...; each wave reduces its lanes' extents and, when it saw a mask
 // pixel, folds them into the frame's box with four global integer atomics (min / max: order-independent, so the result is deterministic)

@@ -14,42 +14,21 @@
 // the banks.  K sweeps inside a K-pixel halo equal K global sweeps on the interior: a pixel d pixels inside the loaded region is exact through
 // sweep d (what lies outside the region reaches it after d + 1 sweeps at the earliest), and the interior has d >= K.
 #include "vv_common.h"
+#include "vv_wave_bytes.h"
 #include "../../include/vvshadow.h"
 
 namespace {
 
+using vvwave::load_mask;
+using vvwave::load_px;
+using vvwave::store_mask;
+using vvwave::wave_sum;
 constexpr int PB = 256;                     // threads per block
 typedef unsigned long long u64;
 typedef long long i64;
 static_assert((u64)VVH_MAX_T * 255 * 255 < (1ull << 32), "T2 in 32 bits");
 static_assert((u64)VVH_MAX_T * 765 * 2 < (1ull << 32), "rule 2 in 32 bits");
 
-struct __attribute__((aligned(4))) U3 { unsigned a, b, c; };
-
-template <bool VEC> __device__ __forceinline__ unsigned load_mask(const uint8_t* m) {
-    if constexpr (VEC) return *reinterpret_cast<const unsigned*>(m);
-    else return *m;
-}
-template <bool VEC> __device__ __forceinline__ void store_mask(uint8_t* m, unsigned w) {
-    if constexpr (VEC) *reinterpret_cast<unsigned*>(m) = w;
-    else *m = (uint8_t)w;
-}
-// the 3 P image bytes at px, as values
-template <bool VEC> __device__ __forceinline__ void load_px(const uint8_t* px, unsigned* v) {
-    if constexpr (VEC) {
-        const U3 q = *reinterpret_cast<const U3*>(px);
-        const unsigned w[3] = {q.a, q.b, q.c};
-#pragma unroll
-        for (int j = 0; j < 12; ++j) v[j] = (w[j >> 2] >> ((j & 3) * 8)) & 255u;
-    } else {
-        v[0] = px[0]; v[1] = px[1]; v[2] = px[2];
-    }
-}
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 // every non-zero byte of w -> 255
 __device__ __forceinline__ unsigned norm4(unsigned w) {
     const unsigned t = (((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) & 0x80808080u;

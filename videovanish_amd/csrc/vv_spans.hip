@@ -6,16 +6,17 @@
 // mask; otherwise one pixel per step.  Every accumulation is an integer add -- registers, then LDS atomics, then one set of global integer atomics
 // per block -- so the result is independent of the order of threads and blocks and equals the numpy restatement bit for bit (as vv_mask_bbox's min / max).
 #include "vv_common.h"
+#include "vv_wave_bytes.h"
 #include "../../include/vvspans.h"
 
 namespace {
 
+using vvwave::luma;
+using vvwave::wave_sum;
 constexpr int SB = 256;                    // threads per block
 constexpr int BINS = VVS_HIST_BINS;
 constexpr int REP = 16;                    // LDS copies of the block's two histograms: thread i adds into copy i % REP (fewer same-address adds)
 constexpr int PX_PER_BLOCK = 32768;        // at most this many pixels per block (+ rounding): 255 * pixels stays far below 2^32 in the 32-bit partials
-
-__device__ __forceinline__ unsigned luma(unsigned r, unsigned g, unsigned b) { return (77u * r + 150u * g + 29u * b + 128u) >> 8; }
 
 // a thread's partial sums; its histogram adds are run-length merged (neighbouring pixels mostly share a bin): (bin, count) pending per frame
 struct Acc {
@@ -43,11 +44,6 @@ __device__ __forceinline__ void load48(const uint8_t* p, unsigned* w) {
         const uint4 v = q[k];
         w[k * 4 + 0] = v.x; w[k * 4 + 1] = v.y; w[k * 4 + 2] = v.z; w[k * 4 + 3] = v.w;
     }
-}
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // grid (nblk, T - 1).  VEC: units of 16 pixels, N % 16 == 0 and 16-byte aligned bases (checked by the launcher); else units of one pixel.  Block b of

@@ -9,26 +9,19 @@
 // statement vv_roi.hip uses, so an identity table gives vv_roi_paste_composite's bytes.
 #include "vv_image_px.h"
 #include "vv_ring_bits.h"
+#include "vv_wave_bytes.h"
 #include "../../include/vvtone.h"
 #pragma clang fp contract(off)
 
 namespace {
 
+using vvwave::wave_sum64;
 using vvring::TB;                                // threads per block: 4 waves
 using vvring::TW;                                // the tile: one lane per column, TH * TW / TB = 8 rows per thread
 using vvring::TH;
 using vvring::u64;
 constexpr int NSUM = 16;
 static_assert(VVT_MAX_RING == vvring::MAX_RING, "the ring of vv_ring_bits.h");
-
-__device__ __forceinline__ u64 wave_sum64(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
-        v += ((u64)hi << 32) | lo;
-    }
-    return v;
-}
 
 // the window's pixel (xx, yy) of frame t's Hm x Wm image `src`, as vv_roi_paste_composite reads it
 __device__ __forceinline__ void window_px(const uint8_t* src, int Hm, int Wm, int xx, int yy, int h, int w, uint8_t* p) {

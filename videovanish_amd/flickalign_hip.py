@@ -1,8 +1,8 @@
 """ctypes binding of the aligned inpaint deflicker entry points of libvvhip.so (include/vvflickalign.h; kernel: csrc/vv_flicker.hip).
 
-Built on hip.py, as flicker_hip.py is: the same library handle, device / contiguity checks and stream; the ABI of vvflickalign.h is declared
-once, in SIGNATURES, and applied when the library is first used through this module.  tests/test_deflickeralign_cpu.py holds the table against
-the header.  No fallback: a missing symbol or a launcher's error raises RuntimeError.
+Built on hip.py: PART (a hip.Part) declares vvflickalign.h's part of the library once, SIGNATURES is applied when the library is first used through
+this module, and the handle, the device / contiguity checks and the stream are hip's.  tests/test_deflickeralign_cpu.py checks the table against the
+header (tests/abiref.py).  No fallback: a missing symbol or a launcher's error raises RuntimeError.
 """
 import ctypes as C
 
@@ -22,19 +22,8 @@ SIGNATURES = {
     "vvc_hold": (I, (P, P, P, P, I, I, I, I, I, I, I, P, P, P)),
 }
 EXPORTS = list(SIGNATURES)
-_lib = None
-
-
-def lib():
-    """hip.lib() with the signatures of vvflickalign.h applied (once)."""
-    global _lib
-    if _lib is None:
-        _lib = hip.bind(hip.lib(), SIGNATURES, "vvc_abi_version", ABI_VERSION, "aligned deflicker")
-    return _lib
-
-
-def _check(rc, what):
-    hip.check(rc, what, lib, "vvc_last_error")
+PART = hip.Part("vvflickalign.h", "vvc_", ABI_VERSION, "aligned deflicker", SIGNATURES)
+lib, _check = PART.lib, PART.check
 
 
 def hold(win, offsets, track, mask2d, radius, tol, out=None):
@@ -51,10 +40,7 @@ def hold(win, offsets, track, mask2d, radius, tol, out=None):
     if track.dtype != torch.int32 or tuple(track.shape) != (T, TRACK_INTS):
         raise RuntimeError(f"hold: track must be [T, {TRACK_INTS}] int32")
     _, H0, W0 = mask2d.shape
-    if out is None:
-        out = torch.empty_like(win)
-    elif out.shape != win.shape or out.dtype != torch.uint8 or out.data_ptr() == win.data_ptr():
-        raise RuntimeError("hold: out must be a contiguous u8 buffer of win's shape, not win itself")
+    out = hip._out_like("hold", out, win, "win")
     sums = torch.empty((T, NSUM), dtype=torch.int64, device=win.device)
     with hip._Prof("flickalign_hold", 0.0, 2 * win.numel() + T * h * w):
         _check(lib().vvc_hold(hip._p(win), hip._p(offsets), hip._p(track), hip._p(mask2d), T, H0, W0, h, w, int(radius), int(tol), hip._p(out),

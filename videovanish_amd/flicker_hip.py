@@ -1,8 +1,8 @@
 """ctypes binding of the inpaint deflicker entry points of libvvhip.so (include/vvflicker.h; kernels: csrc/vv_flicker.hip).
 
-Built on hip.py, as tone_hip.py is: the same library handle, device / contiguity checks and stream; the ABI of vvflicker.h is declared once, in
-SIGNATURES, and applied when the library is first used through this module.  tests/test_deflicker_cpu.py holds the table against the header.
-No fallback: a missing symbol or a launcher's error raises RuntimeError.
+Built on hip.py: PART (a hip.Part) declares vvflicker.h's part of the library once, SIGNATURES is applied when the library is first used through this
+module, and the handle, the device / contiguity checks and the stream are hip's.  tests/test_deflicker_cpu.py checks the table against the header
+(tests/abiref.py).  No fallback: a missing symbol or a launcher's error raises RuntimeError.
 """
 import ctypes as C
 
@@ -23,19 +23,8 @@ SIGNATURES = {
     "vvf_hold": (I, (P, P, P, I, I, I, I, I, I, I, I, P, P, P)),
 }
 EXPORTS = list(SIGNATURES)
-_lib = None
-
-
-def lib():
-    """hip.lib() with the signatures of vvflicker.h applied (once)."""
-    global _lib
-    if _lib is None:
-        _lib = hip.bind(hip.lib(), SIGNATURES, "vvf_abi_version", ABI_VERSION, "deflicker")
-    return _lib
-
-
-def _check(rc, what):
-    hip.check(rc, what, lib, "vvf_last_error")
+PART = hip.Part("vvflicker.h", "vvf_", ABI_VERSION, "deflicker", SIGNATURES)
+lib, _check = PART.lib, PART.check
 
 
 def _need_clip(what, t):
@@ -69,10 +58,7 @@ def hold(win, offsets, mask2d, radius, tol, fixed=None, out=None):
     if offsets.dtype != torch.int32 or tuple(offsets.shape) != (T, 2) or mask2d.dtype != torch.uint8 or mask2d.dim() != 3 or mask2d.shape[0] != T:
         raise RuntimeError("hold: offsets must be [T, 2] int32 and mask2d [T, H0, W0] uint8")
     _, H0, W0 = mask2d.shape
-    if out is None:
-        out = torch.empty_like(win)
-    elif out.shape != win.shape or out.dtype != torch.uint8 or out.data_ptr() == win.data_ptr():
-        raise RuntimeError("hold: out must be a contiguous u8 buffer of win's shape, not win itself")
+    out = hip._out_like("hold", out, win, "win")
     sums = torch.empty((T, NSUM), dtype=torch.int64, device=win.device)
     with hip._Prof("flicker_hold", 0.0, 2 * win.numel() + T * h * w):
         _check(lib().vvf_hold(hip._p(win), hip._p(offsets), hip._p(mask2d), T, H0, W0, h, w, int(radius), int(tol), 1 if fixed else 0, hip._p(out),

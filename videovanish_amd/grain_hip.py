@@ -1,8 +1,8 @@
 """ctypes binding of the seam grain matching entry points of libvvhip.so (include/vvgrain.h; kernels: csrc/vv_grain.hip).
 
-Built on hip.py, as tone_hip.py is: the same library handle, device / contiguity checks and stream; the ABI of vvgrain.h is declared once, in
-SIGNATURES, and applied when the library is first used through this module.  tests/test_grainmatch_cpu.py holds the table against the header.
-No fallback: a missing symbol or a launcher's error raises RuntimeError.
+Built on hip.py: PART (a hip.Part) declares vvgrain.h's part of the library once, SIGNATURES is applied when the library is first used through this
+module, and the handle, the device / contiguity checks and the stream are hip's.  tests/test_grainmatch_cpu.py checks the table against the header
+(tests/abiref.py).  No fallback: a missing symbol or a launcher's error raises RuntimeError.
 """
 import ctypes as C
 
@@ -10,7 +10,6 @@ import torch
 
 from . import hip
 from .hip import I, P      # the ctypes shorthands of hip.SIGNATURES
-from .tone_hip import _need_window
 
 ABI_VERSION = 1
 MAX_RING = 32
@@ -25,24 +24,8 @@ SIGNATURES = {
     "vvg_paste_grain_composite": (I, (P, I, I, P, P, P, P, P, P, I, I, I, I, I, I, I, C.c_float, P, P)),
 }
 EXPORTS = list(SIGNATURES)
-_lib = None
-
-
-def lib():
-    """hip.lib() with the signatures of vvgrain.h applied (once)."""
-    global _lib
-    if _lib is None:
-        _lib = hip.bind(hip.lib(), SIGNATURES, "vvg_abi_version", ABI_VERSION, "grain matching")
-    return _lib
-
-
-def _check(rc, what):
-    hip.check(rc, what, lib, "vvg_last_error")
-
-
-def _need_table(what, name, tab, T):
-    if tab.dtype != torch.uint8 or tuple(tab.shape) != (T, 3, 256):
-        raise RuntimeError(f"{what}: {name} must be a [T, 3, 256] uint8 tensor")
+PART = hip.Part("vvgrain.h", "vvg_", ABI_VERSION, "grain matching", SIGNATURES)
+lib, _check = PART.lib, PART.check
 
 
 def ring_grain_stats(patch, orig, mask2d, offsets, lut, h, w, ring, flat):
@@ -53,8 +36,8 @@ def ring_grain_stats(patch, orig, mask2d, offsets, lut, h, w, ring, flat):
     if mask2d is None:
         raise RuntimeError("ring_grain_stats: the ring needs mask2d")
     hip._need_cuda(lut)
-    T, Hm, Wm, H0, W0 = _need_window("ring_grain_stats", patch, orig, mask2d, offsets)
-    _need_table("ring_grain_stats", "lut", lut, T)
+    T, Hm, Wm, H0, W0 = hip._need_window("ring_grain_stats", patch, orig, mask2d, offsets)
+    hip._need_table("ring_grain_stats", "lut", lut, T)
     sums = torch.empty((T, NSUM), dtype=torch.int64, device=orig.device)
     with hip._Prof("grain_ring_stats", 0.0, T * int(h) * int(w) + sums.numel() * 8):
         _check(lib().vvg_ring_grain_stats(hip._p(patch), Hm, Wm, hip._p(orig), hip._p(mask2d), hip._p(offsets), hip._p(lut), T, H0, W0, int(h), int(w),
@@ -68,15 +51,12 @@ def paste_grain_composite(patch, orig, mask2d, offsets, lut, amp, frame_ids, see
     and the pixel's FRAME coordinates; mode 0 = one value per pixel ("luma"), 1 = one per channel ("rgb").  feather_px < 0: plain paste (mask2d
     may be None).  out: an optional [T,H0,W0,3] u8 buffer to write (not orig)."""
     hip._need_cuda(lut, amp, frame_ids, out)
-    T, Hm, Wm, H0, W0 = _need_window("paste_grain_composite", patch, orig, mask2d, offsets)
-    _need_table("paste_grain_composite", "lut", lut, T)
-    _need_table("paste_grain_composite", "amp", amp, T)
+    T, Hm, Wm, H0, W0 = hip._need_window("paste_grain_composite", patch, orig, mask2d, offsets)
+    hip._need_table("paste_grain_composite", "lut", lut, T)
+    hip._need_table("paste_grain_composite", "amp", amp, T)
     if frame_ids.dtype != torch.int32 or tuple(frame_ids.shape) != (T,):
         raise RuntimeError("paste_grain_composite: frame_ids must be a [T] int32 tensor")
-    if out is None:
-        out = torch.empty_like(orig)
-    elif out.shape != orig.shape or out.dtype != torch.uint8 or out.data_ptr() == orig.data_ptr():
-        raise RuntimeError("paste_grain_composite: out must be a contiguous u8 buffer of orig's shape, not orig itself")
+    out = hip._out_like("paste_grain_composite", out, orig, "orig")
     with hip._Prof("grain_paste_composite", 0.0, T * H0 * W0 * (3 + 1 + 3) + patch.numel()):
         _check(lib().vvg_paste_grain_composite(hip._p(patch), Hm, Wm, hip._p(orig), hip._p(mask2d), hip._p(offsets), hip._p(lut), hip._p(amp),
                                                hip._p(frame_ids), int(seed), int(mode), T, H0, W0, int(h), int(w), float(feather_px), hip._p(out),

@@ -1,6 +1,7 @@
 """ctypes binding of libvvhip.so (include/vvhip.h).  PyTorch is used only for device memory and streams.
 
-The C ABI is declared once, in SIGNATURES, and lib() applies it: the wrappers pass plain Python values (an int64_t or float parameter is converted by its declaration, a pointer is
+The C ABI is declared once, in SIGNATURES, and lib() applies it (Part below: the binder of this header, CORE, and of every feature header, the PART of
+a *_hip module): the wrappers pass plain Python values (an int64_t or float parameter is converted by its declaration, a pointer is
 an address (data_ptr(), _p(t)), a struct goes through C.byref) and a value of the wrong kind raises ctypes.ArgumentError.  tests/test_abi_cpu.py holds table and struct mirrors against the header.
 
 There is NO fallback: if the shared library is missing or a launcher reports an error, a RuntimeError is raised
@@ -47,7 +48,6 @@ class _Prof:
 # environment variable is read anywhere in this module: behaviour is selected by API only.
 _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libvvhip.so")
 PROFILE_SHAPES = False   # bench.py --profile-shapes: profile keys of the GEMM / attention launches carry their M, N, K (tools/shape_table.py)
-_lib = None
 
 
 class ConvParams(C.Structure):
@@ -202,39 +202,46 @@ SIGNATURES = {
 EXPORTS = list(SIGNATURES)
 
 
-def bind(dll, signatures, version_fn, version, part=""):
-    """dll with a header's `signatures` (name -> (restype, argtypes)) applied.  RuntimeError when an export is missing or `version_fn` does not
-    return `version`; `part` names the header's part of the library in that message.  hip.lib() and every *_hip.lib() go through here."""
-    for name, (restype, argtypes) in signatures.items():
-        if not hasattr(dll, name):
-            raise RuntimeError(f"libvvhip.so does not export {name}")
-        fn = getattr(dll, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    v = getattr(dll, version_fn)()
-    if v != version:
-        raise RuntimeError(f"libvvhip.so {part + ' ' if part else ''}ABI version {v} != {version}")
-    return dll
+class Part:
+    """One header's part of libvvhip.so: the header's file name, the symbol prefix, the ABI version, the label of the part in error messages ("" for
+    vvhip.h itself) and `signatures` (name -> (restype, argtypes), in the header's order).  Nothing is resolved before lib() is first called.
+    Every *_hip module declares its header this way: PART = hip.Part(...); lib = PART.lib; _check = PART.check."""
+
+    def __init__(self, header, prefix, version, label, signatures):
+        self.header, self.prefix, self.version, self.label, self.signatures = header, prefix, version, label, signatures
+        self.dll = None      # the library handle with `signatures` applied, once the part has been used (tests reset it)
+
+    def lib(self):
+        """The library with this part's signatures applied (once): the core part loads _LIB_PATH, every other part binds over hip.lib().
+        RuntimeError when the library has not been built, an export is missing or <prefix>abi_version() is not `version` -- never falls back."""
+        if self.dll is None:
+            if self is CORE:
+                if not os.path.isfile(_LIB_PATH):
+                    raise RuntimeError(f"videovanish_amd: HIP extension missing ({_LIB_PATH}); run videovanish_amd/csrc/build.sh "
+                                       "or __graft_entry__.build() -- there is no CPU fallback")
+                dll = C.CDLL(_LIB_PATH)
+            else:
+                dll = CORE.lib()
+            for name, (restype, argtypes) in self.signatures.items():
+                if not hasattr(dll, name):
+                    raise RuntimeError(f"libvvhip.so does not export {name}")
+                fn = getattr(dll, name)
+                fn.restype, fn.argtypes = restype, argtypes
+            v = getattr(dll, self.prefix + "abi_version")()
+            if v != self.version:
+                raise RuntimeError(f"libvvhip.so {self.label + ' ' if self.label else ''}ABI version {v} != {self.version}")
+            self.dll = dll
+        return self.dll
+
+    def check(self, rc, what):
+        """RuntimeError with the library's message (<prefix>last_error()) when a launcher returned rc != 0."""
+        if rc != 0:
+            raise RuntimeError(f"{what} failed ({rc}): {getattr(self.lib(), self.prefix + 'last_error')().decode()}")
 
 
-def check(rc, what, lib, last_error):
-    """RuntimeError with the library's message (lib().<last_error>()) when a launcher returned rc != 0."""
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc}): {getattr(lib(), last_error)().decode()}")
-
-
-def lib():
-    """Load libvvhip.so (once).  Raises RuntimeError when it has not been built -- never falls back."""
-    global _lib
-    if _lib is None:
-        if not os.path.isfile(_LIB_PATH):
-            raise RuntimeError(f"videovanish_amd: HIP extension missing ({_LIB_PATH}); run videovanish_amd/csrc/build.sh "
-                               "or __graft_entry__.build() -- there is no CPU fallback")
-        _lib = bind(C.CDLL(_LIB_PATH), SIGNATURES, "vv_abi_version", ABI_VERSION)
-    return _lib
-
-
-def _check(rc, what):
-    check(rc, what, lib, "vv_last_error")
+CORE = Part("vvhip.h", "vv_", ABI_VERSION, "", SIGNATURES)
+lib = CORE.lib
+_check = CORE.check
 
 
 def _stream():
@@ -272,6 +279,48 @@ def _need_cuda(*ts):
             # kernels are launched on the CURRENT device's stream: a tensor on another GPU would be a cross-device pointer
             raise RuntimeError(f"videovanish_amd.hip: tensor on {t.device} but the current device is cuda:{cur} "
                                "(one process per GPU: torch.cuda.set_device(LOCAL_RANK) before building the model)")
+
+
+# ---- the tensor checks the byte-image wrappers share (hip.roi_paste_composite and the *_hip modules) ---------------------------------------------
+def _out_like(what, out, src, name):
+    """The caller's out= of a wrapper that must not write over its input `src` (called `name` in the message), or a fresh tensor."""
+    if out is None:
+        return torch.empty_like(src)
+    if out.shape != src.shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.data_ptr() == src.data_ptr():
+        raise RuntimeError(f"{what}: out must be a contiguous u8 buffer of {name}'s shape, not {name} itself")
+    return out
+
+
+def _need_clip(what, frames, *masks):
+    """frames [T,H,W,3] u8 and masks [T,H,W] u8 on the device -> (T, H, W)."""
+    _need_cuda(frames, *masks)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
+        raise RuntimeError(f"{what}: the frames must be a [T >= 1, H, W, 3] uint8 tensor")
+    T, H, W, _ = frames.shape
+    for m in masks:
+        if m.dtype != torch.uint8 or tuple(m.shape) != (T, H, W):
+            raise RuntimeError(f"{what}: every mask must be a [T, H, W] uint8 tensor of the frames' size")
+    return T, H, W
+
+
+def _need_table(what, name, tab, T):
+    """tab: one 256-entry byte table per frame and channel (a LUT, grain amplitudes)."""
+    if tab.dtype != torch.uint8 or tuple(tab.shape) != (T, 3, 256):
+        raise RuntimeError(f"{what}: {name} must be a [T, 3, 256] uint8 tensor")
+
+
+def _need_window(what, patch, orig, mask2d, offsets):
+    """The shapes the window pastes share (roi_paste_composite's arguments); -> (T, Hm, Wm, H0, W0)."""
+    _need_cuda(patch, orig, mask2d, offsets)
+    u8 = torch.uint8
+    if patch.dtype != u8 or orig.dtype != u8 or patch.dim() != 4 or orig.dim() != 4 or patch.shape[3] != 3 or orig.shape[3] != 3 or patch.shape[0] < 1:
+        raise RuntimeError(f"{what}: patch and orig must be [T >= 1, H, W, 3] uint8 tensors")
+    T, Hm, Wm, _ = patch.shape
+    _, H0, W0, _ = orig.shape
+    if orig.shape[0] != T or offsets.dtype != torch.int32 or tuple(offsets.shape) != (T, 2) or (
+            mask2d is not None and (mask2d.dtype != u8 or tuple(mask2d.shape) != (T, H0, W0))):
+        raise RuntimeError(f"{what}: shapes / dtypes do not match")
+    return T, Hm, Wm, H0, W0
 
 
 # vv_conv_gemm_route codes (vvhip.h VV_ROUTE_*): 128-row kernels = loader + tile
@@ -735,10 +784,7 @@ def roi_paste_composite(patch, orig, mask2d, offsets, h, w, feather_px, out=None
     _, H0, W0, _ = orig.shape
     if offsets.dtype != torch.int32 or tuple(offsets.shape) != (T, 2) or orig.shape[0] != T or patch.shape[3] != 3 or orig.shape[3] != 3 or (mask2d is not None and tuple(mask2d.shape) != (T, H0, W0)):
         raise RuntimeError("roi_paste_composite: shapes / dtypes do not match")
-    if out is None:
-        out = torch.empty_like(orig)
-    elif out.shape != orig.shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.data_ptr() == orig.data_ptr():
-        raise RuntimeError("roi_paste_composite: out must be a contiguous u8 buffer of orig's shape, not orig itself")
+    out = _out_like("roi_paste_composite", out, orig, "orig")
     with _Prof("roi_paste_composite", 0.0, T * H0 * W0 * (3 + 1 + 3) + patch.numel()):
         _check(lib().vv_roi_paste_composite(_p(patch), Hm, Wm, _p(orig), _p(mask2d), _p(offsets), T, H0, W0, int(h), int(w), feather_px, _p(out),
                                             _stream()), "vv_roi_paste_composite")

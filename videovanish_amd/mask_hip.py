@@ -1,8 +1,8 @@
 """ctypes binding of the mask clean-up entry points of libvvhip.so (include/vvmask.h; kernels: csrc/vv_mask.hip).
 
-Built on hip.py, as spans_hip.py is: the same library handle, device / contiguity checks and stream; the ABI of vvmask.h is declared once, in
-SIGNATURES, and applied when the library is first used through this module.  tests/test_maskclean_cpu.py holds the table against the header.
-No fallback: a missing symbol or a launcher's error raises RuntimeError.
+Built on hip.py: PART (a hip.Part) declares vvmask.h's part of the library once, SIGNATURES is applied when the library is first used through this
+module, and the handle, the device / contiguity checks and the stream are hip's.  tests/test_maskclean_cpu.py checks the table against the header
+(tests/abiref.py).  No fallback: a missing symbol or a launcher's error raises RuntimeError.
 """
 import ctypes as C
 
@@ -24,19 +24,8 @@ SIGNATURES = {
     "vvm_time_bridge_grow": (I, (P, I, I, I, I, I, P, P, P)),
 }
 EXPORTS = list(SIGNATURES)
-_lib = None
-
-
-def lib():
-    """hip.lib() with the signatures of vvmask.h applied (once)."""
-    global _lib
-    if _lib is None:
-        _lib = hip.bind(hip.lib(), SIGNATURES, "vvm_abi_version", ABI_VERSION, "mask clean-up")
-    return _lib
-
-
-def _check(rc, what):
-    hip.check(rc, what, lib, "vvm_last_error")
+PART = hip.Part("vvmask.h", "vvm_", ABI_VERSION, "mask clean-up", SIGNATURES)
+lib, _check = PART.lib, PART.check
 
 
 def _need_mask(mask2d, what):

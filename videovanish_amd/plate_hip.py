@@ -1,8 +1,8 @@
 """ctypes binding of the clean-plate fill entry points of libvvhip.so (include/vvplate.h; kernels: csrc/vv_plate.hip).
 
-Built on hip.py, as mask_hip.py is: the same library handle, device / contiguity checks and stream; the ABI of vvplate.h is declared once, in
-SIGNATURES, and applied when the library is first used through this module.  tests/test_platefill_cpu.py holds the table against the header.
-No fallback: a missing symbol or a launcher's error raises RuntimeError.
+Built on hip.py: PART (a hip.Part) declares vvplate.h's part of the library once, SIGNATURES is applied when the library is first used through this
+module, and the handle, the device / contiguity checks and the stream are hip's.  tests/test_platefill_cpu.py checks the table against the header
+(tests/abiref.py).  No fallback: a missing symbol or a launcher's error raises RuntimeError.
 """
 import ctypes as C
 
@@ -25,30 +25,14 @@ SIGNATURES = {
     "vvp_fill": (I, (P, P, P, P, P, I, I, I, I, P, P, P)),
 }
 EXPORTS = list(SIGNATURES)
-_lib = None
-
-
-def lib():
-    """hip.lib() with the signatures of vvplate.h applied (once)."""
-    global _lib
-    if _lib is None:
-        _lib = hip.bind(hip.lib(), SIGNATURES, "vvp_abi_version", ABI_VERSION, "clean-plate fill")
-    return _lib
-
-
-def _check(rc, what):
-    hip.check(rc, what, lib, "vvp_last_error")
+PART = hip.Part("vvplate.h", "vvp_", ABI_VERSION, "clean-plate fill", SIGNATURES)
+lib, _check = PART.lib, PART.check
 
 
 def _need_clip(what, frames, *masks, occ=None, tile=TILE):
-    """frames [T,H,W,3] u8 and masks [T,H,W] u8 on the device, occ [ceil(H/tile), ceil(W/tile)] u8 or None -> (T, H, W)."""
-    hip._need_cuda(frames, *masks, occ)
-    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
-        raise RuntimeError(f"{what}: the frames must be a [T >= 1, H, W, 3] uint8 tensor")
-    T, H, W, _ = frames.shape
-    for m in masks:
-        if m.dtype != torch.uint8 or tuple(m.shape) != (T, H, W):
-            raise RuntimeError(f"{what}: every mask must be a [T, H, W] uint8 tensor of the frames' size")
+    """hip._need_clip, and occ [ceil(H/tile), ceil(W/tile)] u8 or None on the device -> (T, H, W)."""
+    T, H, W = hip._need_clip(what, frames, *masks)
+    hip._need_cuda(occ)
     if occ is not None and (occ.dtype != torch.uint8 or tuple(occ.shape) != ((H + tile - 1) // tile, (W + tile - 1) // tile)):
         raise RuntimeError(f"{what}: occ must be the [ceil(H / tile), ceil(W / tile)] uint8 grid of hip.mask_tile_union")
     return T, H, W

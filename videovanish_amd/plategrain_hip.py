@@ -1,8 +1,8 @@
 """ctypes binding of the rotated clean-plate sources of libvvhip.so (include/vvplategrain.h; kernel: csrc/vv_plate.hip).
 
-Built on hip.py, as plate_hip.py is: the same library handle, device / contiguity checks and stream; the ABI of vvplategrain.h is declared
-once, in SIGNATURES, and applied when the library is first used through this module.  tests/test_plategrain_cpu.py holds the table against
-the header.  No fallback: a missing symbol or a launcher's error raises RuntimeError.
+Built on hip.py: PART (a hip.Part) declares vvplategrain.h's part of the library once, SIGNATURES is applied when the library is first used through
+this module, and the handle, the device / contiguity checks and the stream are hip's.  tests/test_plategrain_cpu.py checks the table against the
+header (tests/abiref.py).  No fallback: a missing symbol or a launcher's error raises RuntimeError.
 """
 import ctypes as C
 
@@ -21,19 +21,8 @@ SIGNATURES = {
     "vvl_sources": (I, (P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P, P, P, P)),
 }
 EXPORTS = list(SIGNATURES)
-_lib = None
-
-
-def lib():
-    """hip.lib() with the signatures of vvplategrain.h applied (once)."""
-    global _lib
-    if _lib is None:
-        _lib = hip.bind(hip.lib(), SIGNATURES, "vvl_abi_version", ABI_VERSION, "clean-plate grain")
-    return _lib
-
-
-def _check(rc, what):
-    hip.check(rc, what, lib, "vvl_last_error")
+PART = hip.Part("vvplategrain.h", "vvl_", ABI_VERSION, "clean-plate grain", SIGNATURES)
+lib, _check = PART.lib, PART.check
 
 
 def sources(frames, dil, notsample, occ, steady, n, s1, tol, outlier, max_gap, depth, reach, tile=plate_hip.TILE):

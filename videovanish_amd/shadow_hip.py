@@ -1,8 +1,8 @@
 """ctypes binding of the shadow-masking entry points of libvvhip.so (include/vvshadow.h; kernels: csrc/vv_shadow.hip).
 
-Built on hip.py, as plate_hip.py is: the same library handle, device / contiguity checks and stream; the ABI of vvshadow.h is declared once, in
-SIGNATURES, and applied when the library is first used through this module.  tests/test_shadowmask_cpu.py holds the table against the header.
-No fallback: a missing symbol or a launcher's error raises RuntimeError.
+Built on hip.py: PART (a hip.Part) declares vvshadow.h's part of the library once, SIGNATURES is applied when the library is first used through this
+module, and the handle, the device / contiguity checks and the stream are hip's.  tests/test_shadowmask_cpu.py checks the table against the header
+(tests/abiref.py).  No fallback: a missing symbol or a launcher's error raises RuntimeError.
 """
 import ctypes as C
 
@@ -25,19 +25,8 @@ SIGNATURES = {
     "vvh_merge": (I, (P, P, I, I, I, P, P, P)),
 }
 EXPORTS = list(SIGNATURES)
-_lib = None
-
-
-def lib():
-    """hip.lib() with the signatures of vvshadow.h applied (once)."""
-    global _lib
-    if _lib is None:
-        _lib = hip.bind(hip.lib(), SIGNATURES, "vvh_abi_version", ABI_VERSION, "shadow masking")
-    return _lib
-
-
-def _check(rc, what):
-    hip.check(rc, what, lib, "vvh_last_error")
+PART = hip.Part("vvshadow.h", "vvh_", ABI_VERSION, "shadow masking", SIGNATURES)
+lib, _check = PART.lib, PART.check
 
 
 def _need_masks(what, *masks):
@@ -52,16 +41,6 @@ def _need_masks(what, *masks):
     return tuple(m0.shape)
 
 
-def _need_clip(what, frames, *masks):
-    """frames [T,H,W,3] u8 and masks [T,H,W] u8 on the device -> (T, H, W)."""
-    hip._need_cuda(frames)
-    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
-        raise RuntimeError(f"{what}: the frames must be a [T >= 1, H, W, 3] uint8 tensor")
-    if _need_masks(what, *masks) != tuple(frames.shape[:3]):
-        raise RuntimeError(f"{what}: every mask must be a [T, H, W] uint8 tensor of the frames' size")
-    return tuple(frames.shape[:3])
-
-
 def _need_plate(what, H, W, ok, n2, t1):
     hip._need_cuda(ok, n2, t1)
     if (ok.dtype, tuple(ok.shape)) != (torch.uint8, (H, W)) or (n2.dtype, tuple(n2.shape)) != (torch.int32, (H, W)) or \
@@ -72,7 +51,7 @@ def _need_plate(what, H, W, ok, n2, t1):
 def plate(frames, notsample, min_samples, tol):
     """Rules 2 and 3 of vvshadow.h -> (ok [H,W] u8, n2 [H,W] int32, t1 [H,W,3] int32 holding the header's uint32 bits; both stay below 2^31) on
     the device (vvh_plate)."""
-    T, H, W = _need_clip("plate", frames, notsample)
+    T, H, W = hip._need_clip("plate", frames, notsample)
     dev = frames.device
     ok = torch.empty((H, W), dtype=torch.uint8, device=dev)
     n2 = torch.empty((H, W), dtype=torch.int32, device=dev)
@@ -86,7 +65,7 @@ def plate(frames, notsample, min_samples, tol):
 def candidates(frames, dil, ok, n2, t1, lo, hi, drop, chroma, floor):
     """Rule 4 of vvshadow.h -> (cand [T,H,W] u8 {0, 1}, counts [T,2] int64: column 0 = the candidates, column 1 = 0 for merge) on the device
     (vvh_candidates)."""
-    T, H, W = _need_clip("candidates", frames, dil)
+    T, H, W = hip._need_clip("candidates", frames, dil)
     _need_plate("candidates", H, W, ok, n2, t1)
     cand = torch.empty((T, H, W), dtype=torch.uint8, device=frames.device)
     counts = torch.empty((T, 2), dtype=torch.int64, device=frames.device)

@@ -1,8 +1,8 @@
 """ctypes binding of the mask-span entry points of libvvhip.so (include/vvspans.h; kernels: csrc/vv_spans.hip).
 
-Built on hip.py: the same library handle, device / contiguity checks and stream; the ABI of vvspans.h is declared once, in SIGNATURES, and applied
-when the library is first used through this module.  tests/test_spans_cpu.py holds the table against the header.  No fallback: a missing symbol or a
-launcher's error raises RuntimeError.
+Built on hip.py: PART (a hip.Part) declares vvspans.h's part of the library once, SIGNATURES is applied when the library is first used through this
+module, and the handle, the device / contiguity checks and the stream are hip's.  tests/test_spans_cpu.py checks the table against the header
+(tests/abiref.py).  No fallback: a missing symbol or a launcher's error raises RuntimeError.
 """
 import ctypes as C
 
@@ -23,19 +23,8 @@ SIGNATURES = {
     "vvs_frame_pair_stats": (I, (P, P, I, I, I, P, P, P)),
 }
 EXPORTS = list(SIGNATURES)
-_lib = None
-
-
-def lib():
-    """hip.lib() with the signatures of vvspans.h applied (once)."""
-    global _lib
-    if _lib is None:
-        _lib = hip.bind(hip.lib(), SIGNATURES, "vvs_abi_version", ABI_VERSION, "mask-span")
-    return _lib
-
-
-def _check(rc, what):
-    hip.check(rc, what, lib, "vvs_last_error")
+PART = hip.Part("vvspans.h", "vvs_", ABI_VERSION, "mask-span", SIGNATURES)
+lib, _check = PART.lib, PART.check
 
 
 def pair_stats(frames, mask2d=None):

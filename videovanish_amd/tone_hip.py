@@ -1,8 +1,8 @@
 """ctypes binding of the seam tone matching entry points of libvvhip.so (include/vvtone.h; kernels: csrc/vv_tone.hip).
 
-Built on hip.py, as mask_hip.py is: the same library handle, device / contiguity checks and stream; the ABI of vvtone.h is declared once, in
-SIGNATURES, and applied when the library is first used through this module.  tests/test_tonematch_cpu.py holds the table against the header.
-No fallback: a missing symbol or a launcher's error raises RuntimeError.
+Built on hip.py: PART (a hip.Part) declares vvtone.h's part of the library once, SIGNATURES is applied when the library is first used through this
+module, and the handle, the device / contiguity checks and the stream are hip's.  tests/test_tonematch_cpu.py checks the table against the header
+(tests/abiref.py).  No fallback: a missing symbol or a launcher's error raises RuntimeError.
 """
 import ctypes as C
 
@@ -22,33 +22,8 @@ SIGNATURES = {
     "vvt_paste_lut_composite": (I, (P, I, I, P, P, P, P, I, I, I, I, I, C.c_float, P, P)),
 }
 EXPORTS = list(SIGNATURES)
-_lib = None
-
-
-def lib():
-    """hip.lib() with the signatures of vvtone.h applied (once)."""
-    global _lib
-    if _lib is None:
-        _lib = hip.bind(hip.lib(), SIGNATURES, "vvt_abi_version", ABI_VERSION, "tone matching")
-    return _lib
-
-
-def _check(rc, what):
-    hip.check(rc, what, lib, "vvt_last_error")
-
-
-def _need_window(what, patch, orig, mask2d, offsets):
-    """The shapes both entry points share; -> (T, Hm, Wm, H0, W0)."""
-    hip._need_cuda(patch, orig, mask2d, offsets)
-    u8 = torch.uint8
-    if patch.dtype != u8 or orig.dtype != u8 or patch.dim() != 4 or orig.dim() != 4 or patch.shape[3] != 3 or orig.shape[3] != 3 or patch.shape[0] < 1:
-        raise RuntimeError(f"{what}: patch and orig must be [T >= 1, H, W, 3] uint8 tensors")
-    T, Hm, Wm, _ = patch.shape
-    _, H0, W0, _ = orig.shape
-    if orig.shape[0] != T or offsets.dtype != torch.int32 or tuple(offsets.shape) != (T, 2) or (
-            mask2d is not None and (mask2d.dtype != u8 or tuple(mask2d.shape) != (T, H0, W0))):
-        raise RuntimeError(f"{what}: shapes / dtypes do not match")
-    return T, Hm, Wm, H0, W0
+PART = hip.Part("vvtone.h", "vvt_", ABI_VERSION, "tone matching", SIGNATURES)
+lib, _check = PART.lib, PART.check
 
 
 def ring_stats(patch, orig, mask2d, offsets, h, w, ring):
@@ -57,7 +32,7 @@ def ring_stats(patch, orig, mask2d, offsets, h, w, ring):
     pixels (a box), with x = patch resized to the window and y = orig: n, sum x_c, sum y_c, sum x_c^2, sum x_c y_c, sum y_c^2."""
     if mask2d is None:
         raise RuntimeError("ring_stats: the ring needs mask2d")
-    T, Hm, Wm, H0, W0 = _need_window("ring_stats", patch, orig, mask2d, offsets)
+    T, Hm, Wm, H0, W0 = hip._need_window("ring_stats", patch, orig, mask2d, offsets)
     sums = torch.empty((T, 16), dtype=torch.int64, device=orig.device)
     with hip._Prof("tone_ring_stats", 0.0, T * int(h) * int(w) + sums.numel() * 8):
         _check(lib().vvt_ring_stats(hip._p(patch), Hm, Wm, hip._p(orig), hip._p(mask2d), hip._p(offsets), T, H0, W0, int(h), int(w), int(ring),
@@ -69,13 +44,9 @@ def paste_lut_composite(patch, orig, mask2d, offsets, lut, h, w, feather_px, out
     """hip.roi_paste_composite with the window's bytes sent through lut [T,3,256] u8 (out_c = lut[t, c, in_c]) before the feathered composite
     (vvt_paste_lut_composite).  feather_px < 0: plain paste (mask2d may be None).  out: an optional [T,H0,W0,3] u8 buffer to write (not orig)."""
     hip._need_cuda(lut, out)
-    T, Hm, Wm, H0, W0 = _need_window("paste_lut_composite", patch, orig, mask2d, offsets)
-    if lut.dtype != torch.uint8 or tuple(lut.shape) != (T, 3, 256):
-        raise RuntimeError("paste_lut_composite: lut must be a [T, 3, 256] uint8 tensor")
-    if out is None:
-        out = torch.empty_like(orig)
-    elif out.shape != orig.shape or out.dtype != torch.uint8 or out.data_ptr() == orig.data_ptr():
-        raise RuntimeError("paste_lut_composite: out must be a contiguous u8 buffer of orig's shape, not orig itself")
+    T, Hm, Wm, H0, W0 = hip._need_window("paste_lut_composite", patch, orig, mask2d, offsets)
+    hip._need_table("paste_lut_composite", "lut", lut, T)
+    out = hip._out_like("paste_lut_composite", out, orig, "orig")
     with hip._Prof("tone_paste_lut_composite", 0.0, T * H0 * W0 * (3 + 1 + 3) + patch.numel()):
         _check(lib().vvt_paste_lut_composite(hip._p(patch), Hm, Wm, hip._p(orig), hip._p(mask2d), hip._p(offsets), hip._p(lut), T, H0, W0, int(h), int(w),
                                              float(feather_px), hip._p(out), hip._stream()), "vvt_paste_lut_composite")
