@@ -16,6 +16,9 @@ configure(plate_fill=...) and $VV_PLATE_FILL), plate_align (clean-plate alignmen
 tracked first, so that the fill follows a panning camera: videovanish_amd/platealign.py; also configure(plate_align=...) and $VV_PLATE_ALIGN),
 plate_grain (clean-plate grain: with plate_fill, a filled pixel takes its bytes from a few usable frames in turn, not from the nearest alone, so
 that the grain inside the fill moves: videovanish_amd/plategrain.py; also configure(plate_grain=...) and $VV_PLATE_GRAIN),
+plate_tone (clean-plate exposure matching: with plate_fill, every frame of a segment is mapped to the segment's common exposure before the fill
+samples it and every filled pixel back to its own frame's, so that the fill survives exposure drift and flicker: videovanish_amd/platetone.py;
+also configure(plate_tone=...) and $VV_PLATE_TONE),
 shadow_mask (shadow masking: unmasked pixels that look like the shot's clean background uniformly darkened and hang on to the mask join it,
 between the mask clean-up and the clean-plate fill: videovanish_amd/shadowmask.py; also configure(shadow_mask=...) and $VV_SHADOW_MASK),
 deflicker (inpaint deflicker: the model's pixels are filtered along time before every other seam stage reads them, each the mean of its temporal
@@ -37,7 +40,7 @@ import torch
 
 from videovanish_amd import hip, infill
 from videovanish_amd import deflicker as deflicker_settings
-from videovanish_amd import deflickeralign, grainmatch, maskclean, platealign, platefill, plategrain, seamblend, shadowmask, tonematch
+from videovanish_amd import deflickeralign, grainmatch, maskclean, platealign, platefill, plategrain, platetone, seamblend, shadowmask, tonematch
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
 from videovanish_amd.config import RunConfig
@@ -62,6 +65,7 @@ last_seam_blend = None  # the infill.SeamBlendReport of the last run_infill_on_f
 last_plate_fill = None  # the infill.PlateFillReport of the last run_infill_on_frames call; None when the stage did not run
 last_plate_align = None # the infill.PlateAlignReport of the last run_infill_on_frames call; None when the tracker did not run
 last_plate_grain = None # the infill.PlateGrainReport of the last run_infill_on_frames call; None when the rotation was not asked for
+last_plate_tone = None  # the infill.PlateToneReport of the last run_infill_on_frames call; None when the matching was not asked for
 last_shadow_mask = None # the infill.ShadowMaskReport of the last run_infill_on_frames call; None when the stage did not run
 last_deflicker = None   # the infill.DeflickerReport of the last run_infill_on_frames call; None when the stage did not run
 last_deflicker_align = None  # the infill.DeflickerAlignReport of the last run_infill_on_frames call; None when the tracker did not run
@@ -94,6 +98,7 @@ OPTIONS = (
 MORE_OPTIONS = (
     Option("plate_grain", plategrain, "VV_PLATE_GRAIN", "clean-plate grain", "on|depth=4,reach=8"),
     Option("shadow_mask", shadowmask, "VV_SHADOW_MASK", "shadow masking", "on|guard=1,min_samples=4,tol=6,lo=30,hi=90,drop=12,chroma=20,floor=16,reach=32,min_area=16,grow=1"),
+    Option("plate_tone", platetone, "VV_PLATE_TONE", "clean-plate exposure matching", "on|mode=affine,ring=32,floor=16,min_pixels=1024,max_gain=25,max_offset=32"),
 )
 ALL_OPTIONS = OPTIONS + MORE_OPTIONS
 _OPTION = {o.name: o for o in ALL_OPTIONS}
@@ -101,7 +106,7 @@ _configured = {}        # configure(<option>=...): the value for calls that do n
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
-              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_grain=None, plate_align=None, plate_fill=None):
+              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -132,6 +137,8 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     alignment for calls that do not pass plate_align=.
     plate_grain = None / "on" / "depth=4,reach=8" (any subset) / a plategrain.PlateGrainConfig: clean-plate grain for calls that do not pass
     plate_grain=.
+    plate_tone = None / "on" / "mode=affine,ring=32,floor=16,min_pixels=1024,max_gain=25,max_offset=32" (any subset) / a platetone.PlateToneConfig:
+    clean-plate exposure matching for calls that do not pass plate_tone=.
     shadow_mask = None / "on" / "guard=1,min_samples=4,tol=6,lo=30,hi=90,drop=12,chroma=20,floor=16,reach=32,min_area=16,grow=1,max_bytes=N" (any
     subset) / a shadowmask.ShadowMaskConfig: shadow masking for calls that do not pass shadow_mask=.
     deflicker = None / "on" / "radius=2,tol=12" (any subset) / a deflicker.DeflickerConfig: inpaint deflicker for calls that do not pass
@@ -247,6 +254,13 @@ def plate_grain_config(plate_grain=None):
     return _setting("plate_grain", plate_grain)
 
 
+def plate_tone_config(plate_tone=None):
+    """The clean-plate exposure matching setting a call runs with: its own plate_tone= argument, else configure(plate_tone=...), else
+    $VV_PLATE_TONE (on | off | mode=affine|gain|offset,ring=N,floor=N,min_pixels=N,max_gain=N,max_offset=N).  None = the fill samples the frames
+    as they are.  plate_tone="off" (or False) asks for that whatever configure() or the environment say."""
+    return _setting("plate_tone", plate_tone)
+
+
 def shadow_mask_config(shadow_mask=None):
     """The shadow masking setting a call runs with: its own shadow_mask= argument, else configure(shadow_mask=...), else $VV_SHADOW_MASK (on | off |
     guard=N,min_samples=N,tol=N,lo=N,hi=N,drop=N,chroma=N,floor=N,reach=N,min_area=N,grow=N,max_bytes=N).  None = the masks as they are.
@@ -270,7 +284,7 @@ def deflicker_align_config(deflicker_align=None):
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
-                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_grain=None, plate_align=None, plate_fill=None):
+                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -324,6 +338,13 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     still a byte of the clip at that place; the pixels filled, the masks and last_plate_fill are those of plate_fill alone, on the crop and
     on plate_align's canvas alike, and depth=1 gives its bytes.  What it rotated is kept in last_plate_grain.  Without an effective
     plate_fill it is a ValueError.
+    plate_tone (clean-plate exposure matching, opt-in, needs plate_fill): "on" / "mode=affine,ring=32,floor=16,min_pixels=1024,max_gain=25,
+    max_offset=32" / a videovanish_amd.platetone.PlateToneConfig fits, per segment, frame and channel, how the frame's exposure differs from the
+    segment's mean image over the pixels that are never masked (a gain and an offset, clamped; rules: include/platetone.h), maps the fill's
+    crop, widened by `ring`, to the common exposure, runs the unchanged fill on it and maps every filled pixel back to the exposure of the
+    frame it lands in, so that a clip whose brightness drifts or flickers by more than the fill's tol is still filled.  Pixels that are not
+    filled keep their bytes; a clip without drift gives the bytes of the call without it, and a segment filled on plate_align's canvas is not
+    matched.  What it fitted is kept in last_plate_tone.  Without an effective plate_fill it is a ValueError.
     shadow_mask (shadow masking, opt-in): "on" / "guard=1,min_samples=4,tol=6,lo=30,hi=90,drop=12,chroma=20,floor=16,reach=32,min_area=16,grow=1,
     max_bytes=N" / a videovanish_amd.shadowmask.ShadowMaskConfig extends, after the mask clean-up and before the clean-plate fill, every frame's
     mask over the cast shadow of what it covers (infill.shadow_mask; rules: include/vvshadow.h): per segment between the cuts of spans= / cuts=
@@ -346,14 +367,14 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     under a pan or tilt too.  A frame the tracker loses takes no sample and gives none; after a cut inside a clip call every later frame is
     lost and stays unfiltered: spans="cuts" (or "masked-cuts") splits the call there.  A locked-off clip gives the bytes of deflicker alone.
     What it found is kept in last_deflicker_align.  Without an effective deflicker it is a ValueError."""
-    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_plate_grain, last_shadow_mask, last_deflicker, last_deflicker_align
+    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_plate_grain, last_plate_tone, last_shadow_mask, last_deflicker, last_deflicker_align
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
     ccfg = mask_clean_config(mask_clean)
     tcfg = tone_match_config(tone_match)
     gcfg = grain_match_config(grain_match)
     fcfg = deflicker_config(deflicker)
-    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_plate_grain = last_shadow_mask = last_deflicker = last_deflicker_align = None
+    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_plate_grain = last_plate_tone = last_shadow_mask = last_deflicker = last_deflicker_align = None
     pcfg = plate_fill_config(plate_fill)
     acfg = plate_align_config(plate_align)
     if acfg is not None and pcfg is None:
@@ -361,6 +382,9 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     lcfg = plate_grain_config(plate_grain)
     if lcfg is not None and pcfg is None:
         raise ValueError("plate_grain= (clean-plate grain) needs plate_fill= (clean-plate fill)")
+    ecfg = plate_tone_config(plate_tone)
+    if ecfg is not None and pcfg is None:
+        raise ValueError("plate_tone= (clean-plate exposure matching) needs plate_fill= (clean-plate fill)")
     hcfg = shadow_mask_config(shadow_mask)
     facfg = deflicker_align_config(deflicker_align)
     if facfg is not None and fcfg is None:
@@ -368,7 +392,7 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     bcfg = seam_blend_config(seam_blend, feather_px if keep_unmasked_original else None)
     if compat_reference_early_return:
         on = dict(roi=rcfg, spans=scfg, mask_clean=ccfg, tone_match=tcfg, grain_match=gcfg, seam_blend=bcfg, plate_fill=pcfg, plate_align=acfg,
-                  plate_grain=lcfg, shadow_mask=hcfg, deflicker=fcfg, deflicker_align=facfg)
+                  plate_grain=lcfg, plate_tone=ecfg, shadow_mask=hcfg, deflicker=fcfg, deflicker_align=facfg)
         for o in ALL_OPTIONS:
             if on[o.name] is not None:
                 raise ValueError(f"{o.name}= ({o.phrase}) cannot be combined with compat_reference_early_return=True")
@@ -391,16 +415,20 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     if hcfg is not None:
         dil_t, last_shadow_mask = infill.shadow_mask(frames_rgb, dil_t, hcfg, found)
     if pcfg is not None:
-        more, found_align, found_grain = {}, [], []
+        more, found_align, found_grain, found_tone = {}, [], [], []
         if acfg is not None:
             more.update(acfg=acfg, align_out=found_align)
         if lcfg is not None:
             more.update(gcfg=lcfg, grain_out=found_grain)
+        if ecfg is not None:
+            more.update(tcfg=ecfg, tone_out=found_tone)
         frames_rgb, dil_t, last_plate_fill = infill.plate_fill(frames_rgb, dil_t, pcfg, found, **more)      # downstream these are the originals
         if acfg is not None:
             last_plate_align = found_align[0]
         if lcfg is not None:
             last_plate_grain = found_grain[0]
+        if ecfg is not None:
+            last_plate_tone = found_tone[0]
 
     stages = infill.Stages(lambda: _load_model(dev, ckpt), _load_prior, _run_prior,
                            lambda f, d, prior, p: _run_model(f, d, prior, max_img_size, p, num_inference_steps, scheduler))
@@ -542,6 +570,11 @@ def main():
                     help="With --plate-fill: a filled pixel takes its bytes from up to `depth` usable frames in turn (the nearest and the next ones on "
                          "its side, at most `reach` frames from it), not from the nearest alone, so that the grain inside the fill moves as it does "
                          "around it.  Prints one line with what it rotated.")
+    ap.add_argument("--plate-tone", type=_setting_arg("plate_tone"), default=None, metavar=_OPTION["plate_tone"].metavar,
+                    help="With --plate-fill: fit, per segment, frame and channel, a gain and an offset (mode=gain, mode=offset: one of them) between the "
+                         "frame and the segment's mean image over the pixels that are never masked, run the fill at that common exposure and map "
+                         "every filled pixel back to its own frame's, so that exposure drift and flicker beyond the fill's tol still fill.  "
+                         "Prints one line with what it matched.")
     ap.add_argument("--shadow-mask", type=_setting_arg("shadow_mask"), default=None, metavar=_OPTION["shadow_mask"].metavar,
                     help="Shadow masking before the clean-plate fill: extend every frame's mask over the cast shadow of what it covers.  Unmasked "
                          "pixels at `lo` .. `hi` percent of the shot's clean background (at least `drop` levels darker, the three channels within "
@@ -607,6 +640,11 @@ def main():
         r = last_plate_grain
         filled, rotated = int(r.filled.sum()), int(r.rotated.sum())
         print(f"plate grain: {filled} px filled, {100.0 * rotated / max(filled, 1):.1f} % of them from another frame than the nearest")
+    if args.plate_tone is not None and last_plate_tone is not None:
+        r = last_plate_tone
+        print(f"plate tone: {int((~r.identity).sum())} of {r.identity.size} frames matched, largest |gain - 1| {float(np.abs(r.gain - 1.0).max(initial=0.0)):.4f}, "
+              f"largest |offset| {float(np.abs(r.offset).max(initial=0.0)):.2f}, {sum(p == 'unfit' for p in r.path)} segments unfit, "
+              f"{sum(p == 'canvas' for p in r.path)} on the canvas, of {len(r.segments)}")
     if args.shadow_mask is not None and last_shadow_mask is not None:
         r = last_shadow_mask
         print(f"shadow mask: {int(r.added.sum())} px added in {int((r.added > 0).sum())} of {r.added.size} frames from {int(r.candidates.sum())} candidate px, "

@@ -6,14 +6,14 @@ deflicker along time (with its alignment along a translation tracked per clip ca
 ring's originals have and the model's pixels lack, the membrane that carries the ring's difference original - model into the hole.  Each stage
 reports per clip call; tone_report, grain_report, seam_blend_report, deflicker_report and deflicker_align_report assemble a call's report from
 them.  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is module state.  Rules and reasons: DESIGN.md
-§10, §11, §12, §13, §14, §15, §16, §17, §18, §19, §21."""
+§10, §11, §12, §13, §14, §15, §16, §17, §18, §19, §21, §23."""
 import dataclasses
 from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
 
-from . import align_hip, blend_hip, deflicker, deflickeralign, flickalign_hip, flicker_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platealign, platefill, plategrain_hip, seamblend, shadow_hip, shadowmask, spans_hip, tone_hip, tonematch
+from . import align_hip, blend_hip, deflicker, deflickeralign, flickalign_hip, flicker_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platealign, platefill, plategrain_hip, platetone, platetone_bind, seamblend, shadow_hip, shadowmask, spans_hip, tone_hip, tonematch
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -158,6 +158,21 @@ class PlateGrainReport(NamedTuple):
     segments: tuple
 
 
+class PlateToneReport(NamedTuple):
+    """What plate_fill(tcfg=) matched: per frame the fitted gain and offset per channel (float64 [T,3]: the exact rationals of the fit, rounded
+    for reading only; 1 and 0 where nothing was fitted) and the identity flag (bool [T]: the frame's tables are the identity, it is left
+    alone); per segment of `segments` the support n (0 where none was counted) and the path: "matched" (the fill ran on the normalised crop),
+    "identity" (every frame's tables are the identity: the fill as without the option), "unfit" (fewer than min_pixels of support: the
+    same), "canvas" (filled on plate_align's canvas: not matched) or "skipped" (no mask pixel, the fill itself was skipped or found no tracked frame to
+    fill, or the widened crop exceeds max_bytes or 2^24 pixels: that segment is filled unmatched)."""
+    gain: np.ndarray
+    offset: np.ndarray
+    identity: np.ndarray
+    n: tuple
+    path: tuple
+    segments: tuple
+
+
 class PlateAlignReport(NamedTuple):
     """What the tracker of plate_fill(acfg=) found, per segment of `segments` (a tuple each): off [T,2] int32 = the frame's (x, y) on the canvas,
     key [T] = the key frame it was tracked against, tracked [T] bool, residual [T] = the mean absolute luma difference of its level-0 best
@@ -208,14 +223,21 @@ def _plan_alignment(frames_rgb, d_seg, boxes, pcfg, acfg):
     return track_t, track, cbox, "fallback" if platealign.canvas_bytes(T, cbox) > pcfg.max_bytes else "canvas"
 
 
-def _fill_device(f, d, invalid, pcfg, gcfg=None):
+def _not_sample(d, pcfg):
+    """Rule 1 of include/vvplate.h, complemented: the masks d [T,h,w] grown `guard` frames in time (d itself for guard = 0)."""
+    return d if pcfg.guard == 0 else mask_hip.time_bridge_grow(d, 0, pcfg.guard)[0]
+
+
+def _fill_device(f, d, invalid, pcfg, gcfg=None, notsample=None):
     """The fill itself on resident frames f [T,h,w,3] (written in place) and their masks d [T,h,w]: the tile occupancy, the sample frames from
     time_bridge_grow(., 0, guard) (and not where `invalid` is set: the canvas places no tracked frame covers), stats, sources, the margin
     (mask_collapse_dilate of the unfilled remainder), fill -> (d' on the device, counts [T,3] = (filled, left, rotated) on the host, steady
     pixels).  gcfg = a plategrain.PlateGrainConfig with depth > 1: vvl_sources in place of vvp_sources, and the fill gathers from its live
-    sources (include/vvplategrain.h); rotated = the filled pixels whose live source is not the nearest one, 0 otherwise."""
+    sources (include/vvplategrain.h); rotated = the filled pixels whose live source is not the nearest one, 0 otherwise.  notsample = the
+    sample frames of d where the caller has them already (_not_sample)."""
     occ = hip.mask_tile_union(d, plate_hip.TILE)
-    notsample = d if pcfg.guard == 0 else mask_hip.time_bridge_grow(d, 0, pcfg.guard)[0]
+    if notsample is None:
+        notsample = _not_sample(d, pcfg)
     if invalid is not None:
         notsample = torch.bitwise_or(notsample, invalid)
     st, n, s1 = plate_hip.stats(f, notsample, occ, pcfg.min_samples, pcfg.tol)
@@ -247,6 +269,43 @@ def _fill_on_crop(frames_rgb, d, box, pcfg, gcfg=None):
     return new, d2, c, steady
 
 
+def _tables(raw, T, dev):
+    """T * 3 * 256 bytes -> [T,3,256] u8 on the device."""
+    return torch.from_numpy(np.frombuffer(raw, np.uint8).reshape(T, 3, 256).copy()).to(dev)
+
+
+def _fill_matched(frames_rgb, d, box, pcfg, gcfg, tcfg):
+    """One segment under plate_tone (rules: include/platetone.h) on the widened crop `box` (d = the masks' crop, contiguous): the
+    crop crosses to the device, mean_plane and, with enough support, moments; the integer fit and the tables on the host.  An unfit segment
+    and one whose frames are all identity end here: -> (path, fit, None) and the caller runs the fill as without the option.  Otherwise apply,
+    the unchanged fill on the normalised crop (_fill_device, handed the sample frames found here), restore into a fresh buffer next to the
+    original crop -> ("matched", fit, what _fill_on_crop returns)."""
+    y0, x0, y1, x1 = box
+    T = len(frames_rgb)
+    f = torch.from_numpy(np.stack([fr[y0:y1, x0:x1] for fr in frames_rgb])).to(d.device)
+    notsample = _not_sample(d, pcfg)
+    mean, support, n = platetone_bind.mean_plane(f, notsample, tcfg.floor)
+    n = int(n.item())
+    if n < tcfg.min_pixels:
+        return "unfit", platetone.fit_segment(n, [()] * T, tcfg), None
+    fit = platetone.fit_segment(n, platetone_bind.moments(f, mean, support).cpu().numpy(), tcfg)
+    if fit.all_identity:
+        return "identity", fit, None
+    ident = torch.from_numpy(np.frombuffer(fit.identity, np.uint8).copy()).to(d.device)
+    f1 = platetone_bind.apply(f, _tables(fit.fwd, T, d.device), ident)
+    d2, c, steady = _fill_device(f1, d, None, pcfg, gcfg, notsample)
+    idx = np.nonzero(c[:, 0])[0]
+    new = {}
+    if not len(idx):
+        return "matched", fit, (new, None, c, steady)
+    out = platetone_bind.restore(f, f1, d, d2, _tables(fit.back, T, d.device))
+    got = out[torch.from_numpy(idx).to(f.device)].cpu().numpy()
+    for j, i in enumerate(idx):
+        new[int(i)] = np.array(frames_rgb[i], copy=True)
+        new[int(i)][y0:y1, x0:x1] = got[j]
+    return "matched", fit, (new, d2, c, steady)
+
+
 def _fill_on_canvas(frames_rgb, d_seg, track_t, track, box, pcfg, gcfg=None):
     """Steps 5 and 7 - 9 of DESIGN.md §17 for one segment: the canvas from per-frame slices, the unchanged vvp_ kernels on it, the filled pixels
     back into copies of their frames -> ({frame index: new frame}, dil' [T,H,W] or None when nothing was filled, counts [T,3] as _fill_device's, steady)."""
@@ -275,7 +334,7 @@ def _fill_on_canvas(frames_rgb, d_seg, track_t, track, box, pcfg, gcfg=None):
     return new, align_hip.unplace_mask(d2, d_seg, track_t, box), c, steady
 
 
-def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None, gcfg=None, grain_out=None):
+def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None, gcfg=None, grain_out=None, tcfg=None, tone_out=None):
     """The clean-plate fill (platefill.py; rules: include/vvplate.h): frames_rgb = the T host frames [H,W,3] u8, dil_t = the masks
     [T,H,W] u8 on the device, pcfg = a PlateFillConfig, cuts = frame indices or None (one segment).  Per segment of spans.segments: the crop of
     the union box of its masks (platefill.crop_box) crosses to the device and is filled in place (_fill_device); only the crops of frames
@@ -291,7 +350,13 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None, gc
     gcfg = a plategrain.PlateGrainConfig (rule: include/vvplategrain.h), opt-in: wherever a segment is filled, on the crop or on
     the canvas, every masked frame takes its bytes from up to `depth` usable frames in turn, not from the nearest alone, so that the grain inside
     the fill moves; the pixels filled, dil' and the PlateFillReport are those without it, and depth = 1 is the call without it.  grain_out = a
-    list that receives the call's PlateGrainReport."""
+    list that receives the call's PlateGrainReport.
+    tcfg = a platetone.PlateToneConfig (rules: include/platetone.h), opt-in: a segment filled on the crop takes that crop widened
+    by `ring` (shadowmask.widen_box), fits every frame's exposure to the segment's mean image over the pixels no frame masks, runs the fill
+    on the normalised crop and maps every filled pixel back to its frame's exposure (_fill_matched); an unfilled pixel keeps its bytes.  A
+    segment without enough support, or whose frames all fit the identity, takes the path above as it is; a segment on the canvas is not
+    matched; one whose widened crop exceeds max_bytes or 2^24 pixels is flagged "skipped" and filled as without the option.  tone_out = a list
+    that receives the call's PlateToneReport."""
     T, H, W = dil_t.shape
     cuts = tuple(int(c) for c in (cuts or ()))
     segs = tuple(span_planner.segments(T, cuts))
@@ -300,6 +365,7 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None, gc
     filled, left, rotated = np.zeros(T, np.int64), np.zeros(T, np.int64), np.zeros(T, np.int64)
     steady, skipped = [], []
     arep = [[] for _ in range(6)]
+    tgain, toff, tident, tn, tpath = np.ones((T, 3)), np.zeros((T, 3)), np.ones(T, bool), [], []
     for s, e in segs:
         # the segment's plan: "crop" / "canvas" fill; "empty" (no mask pixel), "skipped" (the crop is too large), "none" (no tracked frame has a mask pixel) do not
         plan, d, at = "crop", dil_t[s:e], ()
@@ -320,6 +386,8 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None, gc
                 d = d[(slice(None),) + at].contiguous()
         steady.append(0)
         skipped.append(plan == "skipped")
+        tn.append(0)
+        tpath.append("canvas" if plan == "canvas" else "skipped")
         if plan in ("none", "skipped", "canvas"):       # the masked pixels as they are; the canvas fill replaces those of its tracked frames
             left[s:e] = (d != 0).flatten(1).sum(1).cpu().numpy()
         if plan not in ("crop", "canvas"):
@@ -328,7 +396,21 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None, gc
             new, d2, c, steady[-1] = _fill_on_canvas(frames_rgb[s:e], d, track_t, track, cbox, pcfg, gcfg)
             left[s:e] = np.where(track[:, 3] == 1, c[:, 1], left[s:e])
         else:
-            new, d2, c, steady[-1] = _fill_on_crop(frames_rgb[s:e], d, box, pcfg, gcfg)
+            res = None
+            if tcfg is not None:
+                wbox = shadowmask.widen_box(box, H, W, tcfg.ring)
+                wide = (slice(wbox[0], wbox[2]), slice(wbox[1], wbox[3]))
+                if platefill.crop_bytes(e - s, wbox) <= pcfg.max_bytes and (wbox[2] - wbox[0]) * (wbox[3] - wbox[1]) <= platetone.MAX_PIXELS:
+                    tpath[-1], fit, res = _fill_matched(frames_rgb[s:e], dil_t[(slice(s, e),) + wide].contiguous(), wbox, pcfg, gcfg, tcfg)
+                    tn[-1] = fit.n
+                    tgain[s:e] = [[f.an / f.ad for f in fs] for fs in fit.fits]
+                    toff[s:e] = [[f.bn / f.bd for f in fs] for fs in fit.fits]
+                    tident[s:e] = np.frombuffer(fit.identity, np.uint8) != 0
+            if res is None:
+                res = _fill_on_crop(frames_rgb[s:e], d, box, pcfg, gcfg)
+            else:
+                at = wide
+            new, d2, c, steady[-1] = res
             left[s:e] = c[:, 1]
         filled[s:e], rotated[s:e] = c[:, 0], c[:, 2]
         for i, fr in new.items():
@@ -341,6 +423,8 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None, gc
         align_out.append(PlateAlignReport(*(tuple(v) for v in arep), segs))
     if gcfg is not None and grain_out is not None:
         grain_out.append(PlateGrainReport(rotated, filled.copy(), segs))
+    if tcfg is not None and tone_out is not None:
+        tone_out.append(PlateToneReport(tgain, toff, tident, tuple(tn), tuple(tpath), segs))
     return frames, dil, PlateFillReport(filled, left, tuple(steady), tuple(skipped), segs, cuts)
 
 
