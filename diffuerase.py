@@ -10,7 +10,9 @@ videovanish_amd/maskclean.py; also configure(mask_clean=...) and $VV_MASK_CLEAN)
 the ring of unmasked pixels round the mask before the composite: videovanish_amd/tonematch.py; also configure(tone_match=...) and $VV_TONE_MATCH), grain_match (seam grain matching: the pasted pixels get the grain
 the original pixels of that ring have and the model's lack: videovanish_amd/grainmatch.py; also configure(grain_match=...) and $VV_GRAIN_MATCH), seam_blend (seam membrane blending: the
 difference original - model on that ring, interpolated harmonically into the hole and added to the pasted pixels: videovanish_amd/seamblend.py;
-also configure(seam_blend=...) and $VV_SEAM_BLEND), plate_fill (clean-plate fill: masked pixels whose background other frames of the shot show are
+also configure(seam_blend=...) and $VV_SEAM_BLEND), detail_match (seam detail matching: the pasted pixels get, or lose, as much of their own
+high-pass as makes the model's rendering of that ring as sharp as the original there: videovanish_amd/detailmatch.py; also
+configure(detail_match=...) and $VV_DETAIL_MATCH), plate_fill (clean-plate fill: masked pixels whose background other frames of the shot show are
 filled from the nearest such frame and leave the mask before anything plans or runs the model: videovanish_amd/platefill.py; also
 configure(plate_fill=...) and $VV_PLATE_FILL), plate_align (clean-plate alignment: with plate_fill, one integer translation per frame is
 tracked first, so that the fill follows a panning camera: videovanish_amd/platealign.py; also configure(plate_align=...) and $VV_PLATE_ALIGN),
@@ -40,7 +42,7 @@ import torch
 
 from videovanish_amd import hip, infill
 from videovanish_amd import deflicker as deflicker_settings
-from videovanish_amd import deflickeralign, grainmatch, maskclean, platealign, platefill, plategrain, platetone, seamblend, shadowmask, tonematch
+from videovanish_amd import deflickeralign, detailmatch, grainmatch, maskclean, platealign, platefill, plategrain, platetone, seamblend, shadowmask, tonematch
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
 from videovanish_amd.config import RunConfig
@@ -69,6 +71,7 @@ last_plate_tone = None  # the infill.PlateToneReport of the last run_infill_on_f
 last_shadow_mask = None # the infill.ShadowMaskReport of the last run_infill_on_frames call; None when the stage did not run
 last_deflicker = None   # the infill.DeflickerReport of the last run_infill_on_frames call; None when the stage did not run
 last_deflicker_align = None  # the infill.DeflickerAlignReport of the last run_infill_on_frames call; None when the tracker did not run
+last_detail_match = None     # the infill.DetailMatchReport of the last run_infill_on_frames call; None when the stage did not run
 
 
 class Option(NamedTuple):
@@ -99,6 +102,8 @@ MORE_OPTIONS = (
     Option("plate_grain", plategrain, "VV_PLATE_GRAIN", "clean-plate grain", "on|depth=4,reach=8"),
     Option("shadow_mask", shadowmask, "VV_SHADOW_MASK", "shadow masking", "on|guard=1,min_samples=4,tol=6,lo=30,hi=90,drop=12,chroma=20,floor=16,reach=32,min_area=16,grow=1"),
     Option("plate_tone", platetone, "VV_PLATE_TONE", "clean-plate exposure matching", "on|mode=affine,ring=32,floor=16,min_pixels=1024,max_gain=25,max_offset=32"),
+    Option("detail_match", detailmatch, "VV_DETAIL_MATCH", "seam detail matching",
+           "on|ring=8,edge=12,smooth=2,min_pixels=256,max_sharpen=2.0,max_soften=1.0,dead=0.06,overshoot=4,strength=1.0"),
 )
 ALL_OPTIONS = OPTIONS + MORE_OPTIONS
 _OPTION = {o.name: o for o in ALL_OPTIONS}
@@ -106,7 +111,7 @@ _configured = {}        # configure(<option>=...): the value for calls that do n
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
-              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
+              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -131,6 +136,8 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     matching for calls that do not pass grain_match=.
     seam_blend = None / "on" / "ring=12,presmooth=2,sweeps=8,max_shift=32,strength=1.0" (any subset) / a seamblend.SeamBlendConfig: seam membrane
     blending for calls that do not pass seam_blend=.
+    detail_match = None / "on" / "ring=8,edge=12,smooth=2,min_pixels=256,max_sharpen=2.0,max_soften=1.0,dead=0.06,overshoot=4,strength=1.0" (any
+    subset) / a detailmatch.DetailMatchConfig: seam detail matching for calls that do not pass detail_match=.
     plate_fill = None / "on" / "guard=1,min_samples=4,tol=6,outlier=3,max_gap=0,margin=2,max_bytes=N" (any subset) / a platefill.PlateFillConfig:
     clean-plate fill for calls that do not pass plate_fill=.
     plate_align = None / "on" / "levels=4,radius=4,min_overlap=25,max_residual=12" (any subset) / a platealign.PlateAlignConfig: clean-plate
@@ -233,6 +240,13 @@ def seam_blend_config(seam_blend=None, feather_px=None):
     return _setting("seam_blend", seam_blend, feather_px)
 
 
+def detail_match_config(detail_match=None):
+    """The seam detail matching setting a call runs with: its own detail_match= argument, else configure(detail_match=...), else $VV_DETAIL_MATCH
+    (on | off | ring=N,edge=N,smooth=N,min_pixels=N,max_sharpen=X,max_soften=X,dead=X,overshoot=N,strength=X).  None = no detail matching.
+    detail_match="off" (or False) asks for none whatever configure() or the environment say."""
+    return _setting("detail_match", detail_match)
+
+
 def plate_fill_config(plate_fill=None):
     """The clean-plate fill setting a call runs with: its own plate_fill= argument, else configure(plate_fill=...), else $VV_PLATE_FILL (on | off |
     guard=N,min_samples=N,tol=N,outlier=N,max_gap=N,margin=N,max_bytes=N).  None = no fill.  plate_fill="off" (or False) asks for none whatever
@@ -284,7 +298,7 @@ def deflicker_align_config(deflicker_align=None):
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
-                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
+                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -319,6 +333,14 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     feathered composite (infill.finish), for the full frame and for every roi window, inside each span: a correction that varies across the
     hole, which one gain and offset cannot give; in front of it tone matching fits its offset alone (gain 1), whatever its mode.  The ring must be wider than ceil(feather_px).  What it measured and added is kept in
     last_seam_blend.  A model frame that equals the original on the ring gives the bytes of the call without it.
+    detail_match (seam detail matching, opt-in): "on" / "ring=8,edge=12,smooth=2,min_pixels=256,max_sharpen=2.0,max_soften=1.0,dead=0.06,
+    overshoot=4,strength=1.0" / a videovanish_amd.detailmatch.DetailMatchConfig fits, per frame, how much of its own 3 x 3 high-pass the model's
+    rendering lacks, or has too much of, against the original over the structured part of that ring (an exact integer least-squares fit, pooled
+    over neighbouring frames, capped, with a dead zone; rules: include/detailmatch.h) and applies that amount to every pixel of the window as an
+    unsharp mask clamped to the range of the pixel's neighbourhood, after the deflicker and before tone matching, membrane blending and grain
+    matching measure the rendering (infill.finish), for the full frame and for every roi window, inside each span.  What it measured and
+    applied is kept in last_detail_match.  A model frame that equals the original on the ring gives the bytes of the call without it, and so
+    does strength=0.
     plate_fill (clean-plate fill, opt-in): "on" / "guard=1,min_samples=4,tol=6,outlier=3,max_gap=0,margin=2,max_bytes=N" / a
     videovanish_amd.platefill.PlateFillConfig fills, after the dilation and the mask clean-up and before anything plans or runs, every masked
     pixel whose background the same shot shows steadily in other frames at the same place with the bytes of the nearest such frame
@@ -367,14 +389,15 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     under a pan or tilt too.  A frame the tracker loses takes no sample and gives none; after a cut inside a clip call every later frame is
     lost and stays unfiltered: spans="cuts" (or "masked-cuts") splits the call there.  A locked-off clip gives the bytes of deflicker alone.
     What it found is kept in last_deflicker_align.  Without an effective deflicker it is a ValueError."""
-    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_plate_grain, last_plate_tone, last_shadow_mask, last_deflicker, last_deflicker_align
+    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_plate_grain, last_plate_tone, last_shadow_mask, last_deflicker, last_deflicker_align, last_detail_match
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
     ccfg = mask_clean_config(mask_clean)
     tcfg = tone_match_config(tone_match)
     gcfg = grain_match_config(grain_match)
     fcfg = deflicker_config(deflicker)
-    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_plate_grain = last_plate_tone = last_shadow_mask = last_deflicker = last_deflicker_align = None
+    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_plate_grain = last_plate_tone = last_shadow_mask = last_deflicker = last_deflicker_align = last_detail_match = None
+    dcfg = detail_match_config(detail_match)
     pcfg = plate_fill_config(plate_fill)
     acfg = plate_align_config(plate_align)
     if acfg is not None and pcfg is None:
@@ -392,7 +415,7 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     bcfg = seam_blend_config(seam_blend, feather_px if keep_unmasked_original else None)
     if compat_reference_early_return:
         on = dict(roi=rcfg, spans=scfg, mask_clean=ccfg, tone_match=tcfg, grain_match=gcfg, seam_blend=bcfg, plate_fill=pcfg, plate_align=acfg,
-                  plate_grain=lcfg, plate_tone=ecfg, shadow_mask=hcfg, deflicker=fcfg, deflicker_align=facfg)
+                  plate_grain=lcfg, plate_tone=ecfg, shadow_mask=hcfg, deflicker=fcfg, deflicker_align=facfg, detail_match=dcfg)
         for o in ALL_OPTIONS:
             if on[o.name] is not None:
                 raise ValueError(f"{o.name}= ({o.phrase}) cannot be combined with compat_reference_early_return=True")
@@ -434,7 +457,7 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
                            lambda f, d, prior, p: _run_model(f, d, prior, max_img_size, p, num_inference_steps, scheduler))
 
     seam = {}               # finish's keywords of the stages that are on; each *_out list gets one report per clip call, in the order of the spans
-    for key, cfg in (("tone", tcfg), ("grain", gcfg), ("blend", bcfg), ("flicker", fcfg), ("flicker_align", facfg)):
+    for key, cfg in (("tone", tcfg), ("grain", gcfg), ("blend", bcfg), ("flicker", fcfg), ("flicker_align", facfg), ("detail", dcfg)):
         if cfg is not None:
             seam.update({key: cfg, key + "_out": []})
 
@@ -459,6 +482,8 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         last_deflicker = infill.deflicker_report(seam["flicker_out"], plan, T)
     if facfg is not None:
         last_deflicker_align = infill.deflicker_align_report(seam["flicker_align_out"], plan)
+    if dcfg is not None:
+        last_detail_match = infill.detail_report(seam["detail_out"], plan, T)
     return out
 
 
@@ -557,6 +582,11 @@ def main():
                     help="Seam membrane blending before the composite: interpolate the difference original - model from the ring of unmasked pixels "
                          "within `ring` px of the mask harmonically into the hole and add it to every pasted pixel, so that the patch meets the "
                          "original along the whole outline (a correction that varies across the hole).  Prints one line with what it added.")
+    ap.add_argument("--detail-match", type=_setting_arg("detail_match"), default=None, metavar=_OPTION["detail_match"].metavar,
+                    help="Seam detail matching before the other seam stages: fit, over the structured part of the ring of unmasked pixels within "
+                         "`ring` px of the mask, how much of its own 3 x 3 high-pass the model's rendering lacks (or has too much of) against the "
+                         "original, and sharpen (or soften) every pasted pixel by that amount, clamped to its neighbourhood's range plus `overshoot`.  "
+                         "Prints one line with what it applied.")
     ap.add_argument("--plate-fill", type=_setting_arg("plate_fill"), default=None, metavar=_OPTION["plate_fill"].metavar,
                     help="Clean-plate fill before anything plans or runs the model: a masked pixel whose background the same shot shows steadily (a "
                          "standard deviation of at most `tol` over at least `min_samples` unmasked frames, `guard` frames away from the mask) is filled "
@@ -625,6 +655,11 @@ def main():
         touched = (r.max_shift > 0.0).any(axis=(0, 2))
         print(f"seam blend: membrane added in {int(touched.sum())} of {touched.size} frames, largest |shift| {float(r.max_shift.max()):.2f}, "
               f"largest ring RMS {float(r.rms_diff.max()):.2f}")
+    if args.detail_match is not None and last_detail_match is not None:
+        r = last_detail_match
+        matched, unfit = (r.amount != 0.0).any(axis=0), ((r.amount == 0.0) & ~r.dead).all(axis=0)
+        print(f"detail match: {int(matched.sum())} of {matched.size} frames matched, largest sharpen {float(max(r.amount.max(initial=0.0), 0.0)):.3f}, "
+              f"largest soften {float(max(-r.amount.min(initial=0.0), 0.0)):.3f}, {int(unfit.sum())} frames unfit")
     if args.plate_fill is not None and last_plate_fill is not None:
         r = last_plate_fill
         print(f"plate fill: {int(r.filled.sum())} px filled in {int((r.filled > 0).sum())} frames, {int(r.left.sum())} px left to the model in "

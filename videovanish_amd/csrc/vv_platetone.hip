@@ -17,6 +17,7 @@ namespace {
 
 using vvwave::load_mask;
 using vvwave::load_px;
+using vvwave::store_px;
 using vvwave::wave_sum;
 using vvwave::wave_sum64;
 using vvwave::U3;
@@ -26,18 +27,6 @@ typedef unsigned long long u64;
 static_assert((u64)VVE_MAX_T * 255 < (1ull << 32), "P in 32 bits");
 static_assert((u64)MAX_PX * 255 * 255 < (1ull << 32), "a thread's Svr in 32 bits");
 static_assert((u64)VVE_MAX_PIXELS * 255 * 255 < (1ull << 40), "Svr and Srr below 2^40");
-
-// the 3 P image bytes at px from values (load_px's inverse)
-template <bool VEC> __device__ __forceinline__ void store_px(uint8_t* px, const unsigned* v) {
-    if constexpr (VEC) {
-        unsigned w[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) w[k] = v[4 * k] | (v[4 * k + 1] << 8) | (v[4 * k + 2] << 16) | (v[4 * k + 3] << 24);
-        *reinterpret_cast<U3*>(px) = U3{w[0], w[1], w[2]};
-    } else {
-        px[0] = (uint8_t)v[0]; px[1] = (uint8_t)v[1]; px[2] = (uint8_t)v[2];
-    }
-}
 
 // frame t's three 256-byte tables into LDS; the caller synchronises
 __device__ __forceinline__ void stage_table(const uint8_t* __restrict__ tabs, int t, unsigned* lds) {

@@ -1,5 +1,5 @@
 // What the byte-image kernels (the image-stage features: vv_spans, vv_mask, vv_tone, vv_grain, vv_blend, vv_plate, vv_align, vv_flicker,
-// vv_shadow, and the boxes of vv_roi) share, one statement each: the wave-64 butterfly reductions their counts and extents go through before
+// vv_shadow, vv_platetone, vv_detail, and the boxes of vv_roi) share, one statement each: the wave-64 butterfly reductions their counts and extents go through before
 // they reach LDS or a global atomic, the luma of the cut statistics and the tracker, and the 4-pixel loads and stores of masks and RGB bytes.
 // All integer: a reduction gives the same value in every lane whatever the order.  A file takes what it uses with using-declarations; a helper
 // that differs between two files in any token stays in its file.
@@ -65,6 +65,17 @@ template <bool VEC> __device__ __forceinline__ void load_px(const uint8_t* px, u
         for (int j = 0; j < 12; ++j) v[j] = (w[j >> 2] >> ((j & 3) * 8)) & 255u;
     } else {
         v[0] = px[0]; v[1] = px[1]; v[2] = px[2];
+    }
+}
+// the 3 P image bytes at px from values (load_px's inverse)
+template <bool VEC> __device__ __forceinline__ void store_px(uint8_t* px, const unsigned* v) {
+    if constexpr (VEC) {
+        unsigned w[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) w[k] = v[4 * k] | (v[4 * k + 1] << 8) | (v[4 * k + 2] << 16) | (v[4 * k + 3] << 24);
+        *reinterpret_cast<U3*>(px) = U3{w[0], w[1], w[2]};
+    } else {
+        px[0] = (uint8_t)v[0]; px[1] = (uint8_t)v[1]; px[2] = (uint8_t)v[2];
     }
 }
 

@@ -4,16 +4,16 @@ sequence (run_windows) and ONE closing step (finish).  The full frame is no wind
 several.  The closing step is one loop over the windows; in it the opt-in seam stages run on each window's pixels before they are pasted: the
 deflicker along time (with its alignment along a translation tracked per clip call), the tone fit to the ring round the mask, the grain the
 ring's originals have and the model's pixels lack, the membrane that carries the ring's difference original - model into the hole.  Each stage
-reports per clip call; tone_report, grain_report, seam_blend_report, deflicker_report and deflicker_align_report assemble a call's report from
-them.  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is module state.  Rules and reasons: DESIGN.md
-§10, §11, §12, §13, §14, §15, §16, §17, §18, §19, §21, §23."""
+reports per clip call; tone_report, grain_report, seam_blend_report, deflicker_report, deflicker_align_report and detail_report assemble a call's
+report from them.  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is module state.  Rules and reasons: DESIGN.md
+§10, §11, §12, §13, §14, §15, §16, §17, §18, §19, §21, §23, §24."""
 import dataclasses
 from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
 
-from . import align_hip, blend_hip, deflicker, deflickeralign, flickalign_hip, flicker_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platealign, platefill, plategrain_hip, platetone, platetone_bind, seamblend, shadow_hip, shadowmask, spans_hip, tone_hip, tonematch
+from . import align_hip, blend_hip, deflicker, deflickeralign, detailmatch, detailmatch_bind, flickalign_hip, flicker_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platealign, platefill, plategrain_hip, platetone, platetone_bind, seamblend, shadow_hip, shadowmask, spans_hip, tone_hip, tonematch
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -692,8 +692,27 @@ def deflicker_align_report(parts, spans):
     return DeflickerAlignReport(*(tuple(c) for c in ([list(v) for v in zip(*cols)] or [[] for _ in range(5)])), tuple(tuple(s) for s in spans))
 
 
+class DetailMatchReport(NamedTuple):
+    """What seam detail matching measured and applied, per window k and frame t (K = 1 for the full frame): the counted pixels of the frame's own
+    ring, the amount of the model's own high-pass added (negative: taken away; 0: the frame is left as it is), the mean of (H(original) -
+    H(model))^2 over that ring before the stage, and whether the cap cut the fit or the dead zone took it for 0 (detailmatch.DetailFit,
+    stacked).  Frames outside every span, frames this rank does not hold and windows a span does not have are zero rows."""
+    n: np.ndarray               # [K,T] int64
+    amount: np.ndarray          # [K,T] float64
+    residual: np.ndarray        # [K,T] float64
+    clamped: np.ndarray         # [K,T] bool
+    dead: np.ndarray            # [K,T] bool
+
+
+def detail_report(parts, spans, T, K=1):
+    """The report of a call over T frames from its clips' reports: parts[i] (finish's detail_out) covers the frames spans[i] = (a, b); at least K
+    windows."""
+    return _merged(DetailMatchReport, (_zeros(dtype=np.int64), _zeros(), _zeros(), _zeros(dtype=bool), _zeros(dtype=bool)), parts, spans, T, K)
+
+
 def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return=False, tone=None, tone_out=None,
-           grain=None, grain_out=None, frame0=0, blend=None, blend_out=None, flicker=None, flicker_out=None, flicker_align=None, flicker_align_out=None):
+           grain=None, grain_out=None, frame0=0, blend=None, blend_out=None, flicker=None, flicker_out=None, flicker_align=None, flicker_align_out=None,
+           detail=None, detail_out=None):
     """The model's frames into frames of the original size.  No plan and no stage (full_frame; reference :69-112): resize when the model ran
     at another size, feathered composite with the originals when keep_unmasked_original, in place in outs[0].  The reference returns from
     inside its loop (:114) so only frame 0 is post-processed; the evident intent (all frames) is the default here,
@@ -728,7 +747,14 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
     along it (flickalign_hip.hold in place of flicker_hip.hold).  A clip beyond the tracker's limits ("untracked"), a single frame and a clip
     whose frames all sit at offset zero ("static") take the unaligned filter exactly as above, fixed form included.  A frame the tracker
     loses (after a cut inside the clip call: every later frame) stays unfiltered.  (track, path) of the clip call is appended to
-    flicker_align_out (deflicker_align_report).  Without flicker_align nothing here changes and no vvc_ symbol is resolved."""
+    flicker_align_out (deflicker_align_report).  Without flicker_align nothing here changes and no vvc_ symbol is resolved.
+    detail (a detailmatch.DetailMatchConfig; rules: include/detailmatch.h): a seam stage, so the full frame takes the loop as
+    the window (0, 0, H0, W0).  Per window, directly after model_px (after the deflicker): ring_detail_stats of the model's pixels against the
+    running buffer, the [T,12] sums to the host (one synchronisation), detailmatch.fit, the [T] amounts to the device, and
+    detailmatch_bind.sharpen materialises the window's pixels at the window's size with that amount of their own high-pass added or taken
+    away; everything above then reads the sharpened [n,h,w,3] patch at equal size, so tone, membrane and grain measure the sharpened
+    rendering and the window ends in the same paste call.  One more window-sized clip buffer lives on the device meanwhile.  The clip's
+    DetailMatchReport is appended to detail_out.  Without detail nothing here changes and no vvd_ symbol is resolved."""
     H0, W0 = frames_rgb[0].shape[:2]
     T = len(outs[0])
     fsums = []      # deflicker: the [T,12] sums of every window filtered so far
@@ -772,7 +798,7 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
             out = hip.feather_composite(out.contiguous(), up(frames_rgb).contiguous(), dil_t[idx].contiguous(), float(feather_px))   # :77-112
         return out
 
-    seam = tone is not None or grain is not None or blend is not None
+    seam = tone is not None or grain is not None or blend is not None or detail is not None
     feather = float(feather_px if keep_unmasked_original else -1.0)
 
     def pasted(idx, up):
@@ -790,7 +816,7 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
         # a shift that varies round the ring is correlated with the picture there and misleads a fitted gain; what varies is the membrane's to
         # take, so in front of it the tone stage fits the offset alone
         tone_cfg = tone if tone is None or blend is None else dataclasses.replace(tone, mode="offset")
-        tfits, gfits, bfits = [], [], []
+        tfits, gfits, bfits, dfits = [], [], [], []
 
         def whole(rows):        # [n,nsum] of this rank's frames -> [T,nsum], zero rows for the others
             sums = np.zeros((T, rows.shape[1]), np.int64)
@@ -801,10 +827,15 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
             src, dst = bufs[k % 2], bufs[(k + 1) % 2]
             offs = torch.from_numpy(np.ascontiguousarray(offsets[idx], np.int32)).to(dev)
             patch = model_px(o, idx, up, offsets, (h, w), offs, mask)
+            if detail is not None:
+                rows = detailmatch_bind.ring_detail_stats(patch, src, mask, offs, h, w, detail.ring, detail.edge).cpu().numpy()
+                dfits.append(detailmatch.held_rows(detailmatch.fit(whole(rows), detail), idx))
+                amounts = torch.from_numpy(detailmatch.q8(dfits[-1].amount[idx])).to(dev)
+                patch = detailmatch_bind.sharpen(patch, amounts, h, w, detail.overshoot)
             if tone is not None:
                 tfits.append(tonematch.fit(whole(tone_hip.ring_stats(patch, src, mask, offs, h, w, tone.ring).cpu().numpy()), tone_cfg))
                 lut = torch.from_numpy(tonematch.tables(tfits[-1].gain[idx], tfits[-1].offset[idx])).to(dev)
-            elif seam:
+            elif grain is not None or blend is not None:
                 lut = torch.from_numpy(np.ascontiguousarray(ident)).to(dev)
             if grain is not None:
                 rows = grain_hip.ring_grain_stats(patch, src, mask, offs, lut, h, w, grain.ring, grain.flat).cpu().numpy()
@@ -827,14 +858,16 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
                 tone_hip.paste_lut_composite(patch, src, mask, offs, lut, h, w, feather, out=dst)
             else:
                 hip.roi_paste_composite(patch, src, mask, offs, h, w, feather, out=dst)
-        for fits, out, report in ((tfits, tone_out, ToneMatchReport), (gfits, grain_out, GrainMatchReport), (bfits, blend_out, SeamBlendReport)):
+        for fits, out, report in ((tfits, tone_out, ToneMatchReport), (gfits, grain_out, GrainMatchReport), (bfits, blend_out, SeamBlendReport),
+                                  (dfits, detail_out, DetailMatchReport)):
             if fits and out is not None:
                 out.append(report(*(np.stack(f) for f in zip(*fits))))
         return bufs[len(wins) % 2]
 
     if seam or plans:
         asked = [(out, empty, len(out)) for cfg, out, empty in ((tone, tone_out, tone_report), (grain, grain_out, grain_report),
-                                                                 (blend, blend_out, seam_blend_report)) if cfg is not None and out is not None]
+                                                                 (blend, blend_out, seam_blend_report), (detail, detail_out, detail_report))
+                 if cfg is not None and out is not None]
         res = _on_device(list(outs[0]) if plans else outs[0], T, dev, pasted)
         for out, empty, before in asked:
             if len(out) == before:                                                        # this rank holds no frame of the clip: identity / zero rows
