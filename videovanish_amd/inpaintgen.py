@@ -30,6 +30,31 @@ def token_grid(h, w):
     return (h + 2 * P3 - K7) // S3 + 1, (w + 2 * P3 - K7) // S3 + 1
 
 
+def tap_major_perm(ch, taps=49):
+    """index c * taps + k of a channel-major patch vector (F.unfold's order) at position k * ch + c: x_tap_major = x_channel_major[perm]"""
+    return torch.arange(ch * taps).view(ch, taps).t().reshape(-1)
+
+
+def encoder_dense_weight(w, g, cprev):
+    """grouped weights [co, (256 + cprev) / g, 3, 3] over cat_g([x0_g | prev_g]) -> dense [co, 256 + cprev, 3, 3] over columns [x0 (256) | prev (cprev)],
+    zero outside the group"""
+    co = w.shape[0]
+    wd = torch.zeros(co, 256 + cprev, 3, 3, dtype=w.dtype)
+    a, p, og = 256 // g, cprev // g, co // g
+    for j in range(g):
+        wd[j * og:(j + 1) * og, j * a:(j + 1) * a] = w[j * og:(j + 1) * og, :a]
+        wd[j * og:(j + 1) * og, 256 + j * p:256 + (j + 1) * p] = w[j * og:(j + 1) * og, a:]
+    return wd
+
+
+def pool_dense_weight(pw_, dim, kk):
+    """depth-wise pool weights [dim, 1, kh, kw] -> dense [dim, kk * dim] over tap-major columns k * dim + c"""
+    wd = torch.zeros(dim, kk, dim, dtype=pw_.dtype)
+    ar = torch.arange(dim)
+    wd[ar, :, ar] = pw_.reshape(dim, kk)
+    return wd.reshape(dim, kk * dim)
+
+
 class _Linear:
     def __init__(self, ctx, weight, bias):
         self.ctx, self.N, self.K = ctx, weight.shape[0], weight.shape[1]
@@ -53,11 +78,7 @@ class _Encoder:
                 # reference: groups g over cat_g([x0_g | prev_g]).  Dense two-source form: columns [x0 (256) | prev (cprev)], zero outside the group
                 cprev = cin
                 w, b = ctx.src.conv(f"{name}.layers.{i}", (256 + cprev) // g, co, 3, 1.0)
-                wd = torch.zeros(co, 256 + cprev, 3, 3)
-                a, p, og = 256 // g, cprev // g, co // g
-                for j in range(g):
-                    wd[j * og:(j + 1) * og, j * a:(j + 1) * a] = w[j * og:(j + 1) * og, :a]
-                    wd[j * og:(j + 1) * og, 256 + j * p:256 + (j + 1) * p] = w[j * og:(j + 1) * og, a:]
+                wd = encoder_dense_weight(w, g, cprev)
                 wp, K = packing.pack_conv(wd, ctx.h16, None)
                 self.layers.append((ctx.dev(wp), K, ctx.dev(b.float()), co, s, True))
             else:
@@ -192,22 +213,24 @@ class _TransformerBlock:
         self.qkv = _Linear(ctx, torch.cat(ws_, 0), torch.cat(bs_, 0))
         pw_, pb_ = src.conv(f"{name}.attention.pool_layer", 1, dim, pool[0], 1.0)          # depth-wise [dim, 1, 4, 4]
         kk = pool[0] * pool[1]
-        wd = torch.zeros(dim, kk, dim)                                                       # dense form over tap-major columns k * dim + c
-        ar = torch.arange(dim)
-        wd[ar, :, ar] = pw_.reshape(dim, kk)
-        self.poolw = _Linear(ctx, wd.reshape(dim, kk * dim), pb_)
+        self.poolw = _Linear(ctx, pool_dense_weight(pw_, dim, kk), pb_)                     # dense form over tap-major columns k * dim + c
         w, b = src.linear(f"{name}.attention.proj", dim, dim)
         self.proj = _Linear(ctx, w, b)
         ch = hidden // 49
         self.ch = ch
         w1, b1_ = src.linear(f"{name}.mlp.fc1.0", dim, hidden)                              # rows c * 49 + k  ->  tap-major k * ch + c
-        perm = torch.arange(hidden).view(ch, 49).t().reshape(-1)
+        perm = tap_major_perm(ch)
         self.fc1 = _Linear(ctx, w1[perm], b1_[perm])
         w2, b2_ = src.linear(f"{name}.mlp.fc2.1", hidden, dim)
         self.fc2 = _Linear(ctx, w2[:, perm], b2_)
 
     def __call__(self, x, t, fh, fw, h, w, tabs, masked_win, zero7, zero4):
         """x fp32 [t*fh*fw, dim] (residual stream) -> fp32, same shape."""
+        x = self.attention_half(x, t, tabs, masked_win, zero4)
+        return self.ffn_half(x, t, fh, fw, h, w, zero7)
+
+    def attention_half(self, x, t, tabs, masked_win, zero4):
+        """x + proj(sparse window attention(norm1(x)))"""
         ctx, dt, dim = self.ctx, self.ctx.dt, self.dim
         wh, ww = self.ws
         L = wh * ww
@@ -235,7 +258,11 @@ class _TransformerBlock:
                           o_bs=L * dim, q_rs=3 * dim, k_rs=3 * dim, v_rs=3 * dim, o_rs=dim, k_off=dim, v_off=2 * dim)
             outs.append(o)
         att = hip.gather_rows(torch.cat(outs, 0) if len(outs) > 1 else outs[0], masked_win["inv"])
-        x = self.proj(att, res0=x, out_dtype=torch.float32)
+        return self.proj(att, res0=x, out_dtype=torch.float32)
+
+    def ffn_half(self, x, t, fh, fw, h, w, zero7):
+        """x + fc2(unfold(GELU(fold(fc1(norm2(x))) / overlap count)))"""
+        ctx, dt = self.ctx, self.ctx.dt
         y = hip.layernorm(dt, x, self.n2[0], self.n2[1])
         hmid = self.fc1(y)                                                            # [n, 49 * ch] tap-major
         grid = hip.fold_patches(dt, hmid, t, fh, fw, self.ch, h, w, K7, S3, P3, normalise=True, gelu=True, out_dtype=ctx.h16)
@@ -250,7 +277,7 @@ class InpaintGenerator:
         self.encoder = _Encoder(ctx, f"{name}.encoder")
         self.prop = _FeaturePropagation(ctx, f"{name}.feat_prop_module", C, deform_groups)
         w, b = ctx.src.linear(f"{name}.ss.embedding", 49 * C, hidden)                      # columns c * 49 + k -> tap-major k * C + c
-        perm = torch.arange(49 * C).view(C, 49).t().reshape(-1)
+        perm = tap_major_perm(C)
         self.ss = _Linear(ctx, w[:, perm], b)
         self.blocks = [_TransformerBlock(ctx, f"{name}.transformers.transformer.{d}", hidden, n_head, ws, pool) for d in range(depths)]
         w, b = ctx.src.linear(f"{name}.sc.embedding", hidden, 49 * C)
@@ -274,7 +301,6 @@ class InpaintGenerator:
         """frames u8 [t,H,W,3] (local frames first, then reference frames; already holding the propagated content), completed flows fp32
         [l_t-1,H,W,2] at full resolution, masks u8 [t,H,W] (dilated input masks / masks still open after the image propagation).
         Returns the raw prediction of the local frames, fp32 [l_t*H*W, 3] (before tanh)."""
-        ctx, dt, C = self.ctx, self.ctx.dt, self.C
         t, H, W, _ = frames_u8.shape
         if H % 4 or W % 4:
             raise RuntimeError(f"InpaintGenerator: H={H}, W={W} must be multiples of 4")
@@ -289,11 +315,32 @@ class InpaintGenerator:
             local = self.prop(enc[:l_t * hw], hip.flow_down4(flows_f.contiguous()), hip.flow_down4(flows_b.contiguous()), masks2, l_t, h, w)
             enc = torch.cat([local, enc[l_t * hw:]], 0)
         fh, fw = token_grid(h, w)
-        zero7 = torch.zeros((t * fh * fw, 2 * 49), dtype=torch.float32, device=dev)
-        col, _, _ = hip.deform_im2col(dt, enc, B=t, H=h, W=w, kh=K7, kw=K7, stride=S3, pad=P3, dil=1, deform_groups=1, offset=zero7)
-        tok = self.ss(col, out_dtype=torch.float32)
+        tok, zero7 = self.soft_split(enc, t, h, w)
+        per_parity = self.window_masks(m_in[:l_t], t, fh, fw, dev)
+        tb0 = per_parity[0]["tabs"]
+        zero4 = self.zero4(t, tb0, dev)
+        for d, blk in enumerate(self.blocks):
+            pp = per_parity[d % self.t_dilation]
+            tok = blk(tok, t, fh, fw, h, w, pp["tabs"], pp, zero7, zero4)
+        enc = self.soft_comp(tok, enc, t, fh, fw, h, w)
+        return self.decoder(enc[:l_t * hw], l_t, h, w)
+
+    def soft_split(self, enc, t, h, w):
+        """enc fp32 [t*h*w, C] -> (tokens fp32 [t*fh*fw, hidden], the zero offsets of the 7x7 stride-3 gather)"""
+        fh, fw = token_grid(h, w)
+        zero7 = torch.zeros((t * fh * fw, 2 * 49), dtype=torch.float32, device=enc.device)
+        col, _, _ = hip.deform_im2col(self.ctx.dt, enc, B=t, H=h, W=w, kh=K7, kw=K7, stride=S3, pad=P3, dil=1, deform_groups=1, offset=zero7)
+        return self.ss(col, out_dtype=torch.float32), zero7
+
+    def zero4(self, t, tabs, dev):
+        return torch.zeros((t * tabs["ph"] * tabs["pw"], 2 * self.pool[0] * self.pool[1]), dtype=torch.float32, device=dev)
+
+    def window_masks(self, m_local, t, fh, fw, dev):
+        """m_local bool [l_t, h, w]: the 1/4-resolution hole masks of the local frames.  Per parity of t_dilation: which windows touch a hole, their
+        query / key gather tables, the clean windows' table and the inverse scatter over cat([masked outputs, clean outputs])."""
+        l_t = m_local.shape[0]
         # hole mask of the local frames on the token grid (max pool 7/3/3), then per window
-        mpad = np.pad(m_in[:l_t], ((0, 0), (P3, P3), (P3, P3)))
+        mpad = np.pad(m_local, ((0, 0), (P3, P3), (P3, P3)))
         mp = np.lib.stride_tricks.sliding_window_view(mpad, (K7, K7), axis=(1, 2))[:, ::S3, ::S3][:, :fh, :fw].any((3, 4))
         wh, ww = self.ws
         per_parity = {}
@@ -315,18 +362,21 @@ class InpaintGenerator:
                 nm=len(mi), nu=len(ui), Lk=tb["k_idx"].shape[1],
                 m_q=to_dev(tb["q_idx"][mi]) if len(mi) else None, m_k=to_dev(tb["k_idx"][mi]) if len(mi) else None,
                 u_q=to_dev(tb["q_idx"][ui]) if len(ui) else None, inv=to_dev(inv_cat), tabs=tb)
-        tb0 = per_parity[0]["tabs"]
-        zero4 = torch.zeros((t * tb0["ph"] * tb0["pw"], 2 * self.pool[0] * self.pool[1]), dtype=torch.float32, device=dev)
-        for d, blk in enumerate(self.blocks):
-            pp = per_parity[d % self.t_dilation]
-            tok = blk(tok, t, fh, fw, h, w, pp["tabs"], pp, zero7, zero4)
-        comp = hip.fold_patches(dt, self.sc(tok), t, fh, fw, C, h, w, K7, S3, P3, out_dtype=ctx.h16)
+        return per_parity
+
+    def soft_comp(self, tok, enc, t, fh, fw, h, w):
+        """tokens fp32 [t*fh*fw, hidden], enc fp32 [t*h*w, C] -> enc + bias_conv(fold(embedding(tokens))), fp32"""
+        comp = hip.fold_patches(self.ctx.dt, self.sc(tok), t, fh, fw, self.C, h, w, K7, S3, P3, out_dtype=self.ctx.h16)
         enc, _, _ = self.sc_conv(comp, t, h, w, res0=enc, out_dtype=torch.float32)
-        x = enc[:l_t * hw]
+        return enc
+
+    def decoder(self, x, l_t, h, w):
+        """x fp32 [l_t*h*w, C] -> the raw prediction fp32 [l_t*4h*4w, 3] (before tanh)"""
+        dt = self.ctx.dt
         x, _, _ = self.d0(hip.upsample2x_bilinear(dt, x, l_t, h, w), l_t, 2 * h, 2 * w, act=0.2)
         x, _, _ = self.d2(x, l_t, 2 * h, 2 * w, act=0.2)
-        x, _, _ = self.d4(hip.upsample2x_bilinear(dt, x, l_t, 2 * h, 2 * w), l_t, H, W, act=0.2)
-        x, _, _ = self.d6(x, l_t, H, W, out_dtype=torch.float32)
+        x, _, _ = self.d4(hip.upsample2x_bilinear(dt, x, l_t, 2 * h, 2 * w), l_t, 4 * h, 4 * w, act=0.2)
+        x, _, _ = self.d6(x, l_t, 4 * h, 4 * w, out_dtype=torch.float32)
         return x
 
 
