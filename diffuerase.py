@@ -8,7 +8,9 @@ inference: only the runs of masked frames are processed, and nothing crosses a h
 $VV_SPANS), mask_clean (mask clean-up between the dilation and the planners: speckles dropped, dropouts bridged, the mask grown in time:
 videovanish_amd/maskclean.py; also configure(mask_clean=...) and $VV_MASK_CLEAN), tone_match (seam tone matching: the model's pixels are fitted to
 the ring of unmasked pixels round the mask before the composite: videovanish_amd/tonematch.py; also configure(tone_match=...) and $VV_TONE_MATCH), grain_match (seam grain matching: the pasted pixels get the grain
-the original pixels of that ring have and the model's lack: videovanish_amd/grainmatch.py; also configure(grain_match=...) and $VV_GRAIN_MATCH), seam_blend (seam membrane blending: the
+the original pixels of that ring have and the model's lack: videovanish_amd/grainmatch.py; also configure(grain_match=...) and $VV_GRAIN_MATCH),
+grain_shape (grain shape: with grain_match, the size of that grain is fitted on the ring as well and the added noise is shaped by it:
+videovanish_amd/grainshape.py; also configure(grain_shape=...) and $VV_GRAIN_SHAPE), seam_blend (seam membrane blending: the
 difference original - model on that ring, interpolated harmonically into the hole and added to the pasted pixels: videovanish_amd/seamblend.py;
 also configure(seam_blend=...) and $VV_SEAM_BLEND), detail_match (seam detail matching: the pasted pixels get, or lose, as much of their own
 high-pass as makes the model's rendering of that ring as sharp as the original there: videovanish_amd/detailmatch.py; also
@@ -42,7 +44,7 @@ import torch
 
 from videovanish_amd import hip, infill
 from videovanish_amd import deflicker as deflicker_settings
-from videovanish_amd import deflickeralign, detailmatch, grainmatch, maskclean, platealign, platefill, plategrain, platetone, seamblend, shadowmask, tonematch
+from videovanish_amd import deflickeralign, detailmatch, grainmatch, grainshape, maskclean, platealign, platefill, plategrain, platetone, seamblend, shadowmask, tonematch
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
 from videovanish_amd.config import RunConfig
@@ -72,6 +74,7 @@ last_shadow_mask = None # the infill.ShadowMaskReport of the last run_infill_on_
 last_deflicker = None   # the infill.DeflickerReport of the last run_infill_on_frames call; None when the stage did not run
 last_deflicker_align = None  # the infill.DeflickerAlignReport of the last run_infill_on_frames call; None when the tracker did not run
 last_detail_match = None     # the infill.DetailMatchReport of the last run_infill_on_frames call; None when the stage did not run
+last_grain_shape = None      # the infill.GrainShapeReport of the last run_infill_on_frames call; None when the shape was not asked for
 
 
 class Option(NamedTuple):
@@ -104,6 +107,7 @@ MORE_OPTIONS = (
     Option("plate_tone", platetone, "VV_PLATE_TONE", "clean-plate exposure matching", "on|mode=affine,ring=32,floor=16,min_pixels=1024,max_gain=25,max_offset=32"),
     Option("detail_match", detailmatch, "VV_DETAIL_MATCH", "seam detail matching",
            "on|ring=8,edge=12,smooth=2,min_pixels=256,max_sharpen=2.0,max_soften=1.0,dead=0.06,overshoot=4,strength=1.0"),
+    Option("grain_shape", grainshape, "VV_GRAIN_SHAPE", "grain shape", "on|max_a=0.5,dead=0.05,min_pairs=512,smooth=4,max_gain=6"),
 )
 ALL_OPTIONS = OPTIONS + MORE_OPTIONS
 _OPTION = {o.name: o for o in ALL_OPTIONS}
@@ -111,7 +115,7 @@ _configured = {}        # configure(<option>=...): the value for calls that do n
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
-              mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
+              mask_clean=None, tone_match=None, grain_match=None, grain_shape=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -134,6 +138,8 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     for calls that do not pass tone_match=.
     grain_match = None / "on" / "luma" / "rgb" / "mode=rgb,ring=8,strength=0.8,seed=3" (any subset) / a grainmatch.GrainMatchConfig: seam grain
     matching for calls that do not pass grain_match=.
+    grain_shape = None / "on" / "max_a=0.5,dead=0.05,min_pairs=512,smooth=4,max_gain=6" (any subset) / a grainshape.GrainShapeConfig: grain shape
+    for calls that do not pass grain_shape=.
     seam_blend = None / "on" / "ring=12,presmooth=2,sweeps=8,max_shift=32,strength=1.0" (any subset) / a seamblend.SeamBlendConfig: seam membrane
     blending for calls that do not pass seam_blend=.
     detail_match = None / "on" / "ring=8,edge=12,smooth=2,min_pixels=256,max_sharpen=2.0,max_soften=1.0,dead=0.06,overshoot=4,strength=1.0" (any
@@ -233,6 +239,13 @@ def grain_match_config(grain_match=None):
     return _setting("grain_match", grain_match)
 
 
+def grain_shape_config(grain_shape=None):
+    """The grain shape setting a call runs with: its own grain_shape= argument, else configure(grain_shape=...), else $VV_GRAIN_SHAPE (on | off |
+    max_a=X,dead=X,min_pairs=N,smooth=N,max_gain=X).  None = grain matching adds white noise.  grain_shape="off" (or False) asks for that
+    whatever configure() or the environment say."""
+    return _setting("grain_shape", grain_shape)
+
+
 def seam_blend_config(seam_blend=None, feather_px=None):
     """The seam membrane blending setting a call runs with: its own seam_blend= argument, else configure(seam_blend=...), else $VV_SEAM_BLEND (on |
     off | ring=N,presmooth=N,sweeps=N,max_shift=N,strength=X).  None = no blending.  seam_blend="off" (or False) asks for none whatever
@@ -298,7 +311,7 @@ def deflicker_align_config(deflicker_align=None):
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
-                         mask_clean=None, tone_match=None, grain_match=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
+                         mask_clean=None, tone_match=None, grain_match=None, grain_shape=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -327,6 +340,13 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     frame and for every roi window, inside each span; the noise of a pixel depends on the seed, the frame's index in this call and the
     pixel's position in the frame only.  What it measured and added is kept in last_grain_match.  A model frame that equals the original on
     the ring gives the bytes of the call without it.
+    grain_shape (grain shape, opt-in, needs grain_match): "on" / "max_a=0.5,dead=0.05,min_pairs=512,smooth=4,max_gain=6" / a
+    videovanish_amd.grainshape.GrainShapeConfig fits, per frame (and per channel in "rgb" mode) and axis, the SIZE of that grain from the lag-1
+    correlation of the noise operator's responses over the same ring (rules: include/grainshape.h), corrects the level the operator
+    under-reads on grain that is not white, and sends the added noise through the separable kernel [a, 1, a] per axis, 0 <= a <= 0.5: from
+    white to the binomial blur, for footage whose grain has been resized, debayered, denoised or compressed.  What it fitted is kept in
+    last_grain_shape.  Grain that is white gives a = 0 and the bytes of grain_match alone.  Without an effective grain_match it is a
+    ValueError.
     seam_blend (seam membrane blending, opt-in): "on" / "ring=12,presmooth=2,sweeps=8,max_shift=32,strength=1.0" / a
     videovanish_amd.seamblend.SeamBlendConfig interpolates, per frame and channel, the difference original - model from that ring harmonically
     into the hole (after tone matching's table, when both are on) and adds this membrane to every pasted pixel before the grain and the
@@ -389,15 +409,18 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     under a pan or tilt too.  A frame the tracker loses takes no sample and gives none; after a cut inside a clip call every later frame is
     lost and stays unfiltered: spans="cuts" (or "masked-cuts") splits the call there.  A locked-off clip gives the bytes of deflicker alone.
     What it found is kept in last_deflicker_align.  Without an effective deflicker it is a ValueError."""
-    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_plate_grain, last_plate_tone, last_shadow_mask, last_deflicker, last_deflicker_align, last_detail_match
+    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_plate_grain, last_plate_tone, last_shadow_mask, last_deflicker, last_deflicker_align, last_detail_match, last_grain_shape
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
     ccfg = mask_clean_config(mask_clean)
     tcfg = tone_match_config(tone_match)
     gcfg = grain_match_config(grain_match)
     fcfg = deflicker_config(deflicker)
-    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_plate_grain = last_plate_tone = last_shadow_mask = last_deflicker = last_deflicker_align = last_detail_match = None
+    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_plate_grain = last_plate_tone = last_shadow_mask = last_deflicker = last_deflicker_align = last_detail_match = last_grain_shape = None
     dcfg = detail_match_config(detail_match)
+    ncfg = grain_shape_config(grain_shape)
+    if ncfg is not None and gcfg is None:
+        raise ValueError("grain_shape= (grain shape) needs grain_match= (seam grain matching)")
     pcfg = plate_fill_config(plate_fill)
     acfg = plate_align_config(plate_align)
     if acfg is not None and pcfg is None:
@@ -415,7 +438,7 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     bcfg = seam_blend_config(seam_blend, feather_px if keep_unmasked_original else None)
     if compat_reference_early_return:
         on = dict(roi=rcfg, spans=scfg, mask_clean=ccfg, tone_match=tcfg, grain_match=gcfg, seam_blend=bcfg, plate_fill=pcfg, plate_align=acfg,
-                  plate_grain=lcfg, plate_tone=ecfg, shadow_mask=hcfg, deflicker=fcfg, deflicker_align=facfg, detail_match=dcfg)
+                  plate_grain=lcfg, plate_tone=ecfg, shadow_mask=hcfg, deflicker=fcfg, deflicker_align=facfg, detail_match=dcfg, grain_shape=ncfg)
         for o in ALL_OPTIONS:
             if on[o.name] is not None:
                 raise ValueError(f"{o.name}= ({o.phrase}) cannot be combined with compat_reference_early_return=True")
@@ -457,7 +480,8 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
                            lambda f, d, prior, p: _run_model(f, d, prior, max_img_size, p, num_inference_steps, scheduler))
 
     seam = {}               # finish's keywords of the stages that are on; each *_out list gets one report per clip call, in the order of the spans
-    for key, cfg in (("tone", tcfg), ("grain", gcfg), ("blend", bcfg), ("flicker", fcfg), ("flicker_align", facfg), ("detail", dcfg)):
+    for key, cfg in (("tone", tcfg), ("grain", gcfg), ("blend", bcfg), ("flicker", fcfg), ("flicker_align", facfg), ("detail", dcfg),
+                     ("grain_shape", ncfg)):
         if cfg is not None:
             seam.update({key: cfg, key + "_out": []})
 
@@ -484,6 +508,8 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         last_deflicker_align = infill.deflicker_align_report(seam["flicker_align_out"], plan)
     if dcfg is not None:
         last_detail_match = infill.detail_report(seam["detail_out"], plan, T)
+    if ncfg is not None:
+        last_grain_shape = infill.grain_shape_report(seam["grain_shape_out"], plan, T)
     return out
 
 
@@ -578,6 +604,10 @@ def main():
                     help="Seam grain matching before the composite: measure, over the flat part of the ring of unmasked pixels within `ring` px of the "
                          "mask, the grain the original pixels have and the model's lack, and add white noise of that level to every pasted pixel (on / "
                          "luma: one noise value per pixel; rgb: one per channel).  Prints one line with what it added.")
+    ap.add_argument("--grain-shape", type=_setting_arg("grain_shape"), default=None, metavar=_OPTION["grain_shape"].metavar,
+                    help="With --grain-match: fit the SIZE of the grain on the same ring as well (per axis the a of a kernel [a, 1, a], 0 = white, "
+                         "0.5 = the binomial blur), correct the level that the white estimate under-reads on soft grain, and add noise shaped by "
+                         "that kernel.  For footage that was resized, debayered, denoised or compressed.  Prints one line with what it fitted.")
     ap.add_argument("--seam-blend", type=_setting_arg("seam_blend"), default=None, metavar=_OPTION["seam_blend"].metavar,
                     help="Seam membrane blending before the composite: interpolate the difference original - model from the ring of unmasked pixels "
                          "within `ring` px of the mask harmonically into the hole and add it to every pasted pixel, so that the patch meets the "
@@ -650,6 +680,11 @@ def main():
         r = last_grain_match
         touched = (r.sigma_added > 0.0).any(axis=(0, 2, 3))
         print(f"grain match: grain added in {int(touched.sum())} of {touched.size} frames, largest sigma {float(r.sigma_added.max()):.2f}")
+    if args.grain_shape is not None and last_grain_shape is not None:
+        r = last_grain_shape
+        shaped = (r.a > 0.0).any(axis=(0, 2, 3))
+        print(f"grain shape: grain shaped in {int(shaped.sum())} of {shaped.size} frames, largest a {float(r.a.max(initial=0.0)):.3f}, "
+              f"largest level gain {float(r.k.max(initial=1.0)):.2f}, largest sigma {float(r.sigma_pixel.max(initial=0.0)):.2f}")
     if args.seam_blend is not None and last_seam_blend is not None:
         r = last_seam_blend
         touched = (r.max_shift > 0.0).any(axis=(0, 2))

@@ -102,11 +102,9 @@ class GrainFit(NamedTuple):
     sigma_added: np.ndarray     # [T,3,4] float64
 
 
-def fit(sums, cfg):
-    """sums [T,36] int64 (a frame this rank does not hold, or without a ring: zeros) -> GrainFit.  Frame t is fitted to the pooled sums of frames
-    t - smooth .. t + smooth.  Per channel and band in fp64: var = (Sy - Sx) / (36 n), the difference taken on the integers; a band whose pooled
-    n < min_count takes the channel's sums over all four bands, and 0 where those are short of min_count too; sigma_added = min(strength *
-    sqrt(max(var, 0)), max_sigma).  A frame whose own ring holds no counted pixel gets 0.  Where Sx == Sy the result is exactly 0.0."""
+def variances(sums, cfg):
+    """The part of fit that grainshape.fit shares: sums [T,36] int64 -> (own [T,3,4,3] = the sums as given, live [T,3,4] bool, den [T,3,4] =
+    36 n of the pooled ring (36 where not live), sx, sy [T,3,4] int64 = the pooled sums of the band, or of the channel where the band is short)."""
     sums = np.asarray(sums, np.int64).reshape(-1, 3, BANDS, 3)
     T = len(sums)
     p = pool(sums.reshape(T, NSUM), cfg.smooth).reshape(T, 3, BANDS, 3)
@@ -115,6 +113,15 @@ def fit(sums, cfg):
     n, sx, sy = use[..., 0], use[..., 1], use[..., 2]
     live = (n >= cfg.min_count) & (sums[..., 0].sum(axis=(1, 2)) > 0)[:, None, None]
     den = OP_GAIN * np.where(live, n, 1).astype(np.float64)
+    return sums, live, den, sx, sy
+
+
+def fit(sums, cfg):
+    """sums [T,36] int64 (a frame this rank does not hold, or without a ring: zeros) -> GrainFit.  Frame t is fitted to the pooled sums of frames
+    t - smooth .. t + smooth.  Per channel and band in fp64: var = (Sy - Sx) / (36 n), the difference taken on the integers; a band whose pooled
+    n < min_count takes the channel's sums over all four bands, and 0 where those are short of min_count too; sigma_added = min(strength *
+    sqrt(max(var, 0)), max_sigma).  A frame whose own ring holds no counted pixel gets 0.  Where Sx == Sy the result is exactly 0.0."""
+    sums, live, den, sx, sy = variances(sums, cfg)
     sigma = lambda s: np.where(live, np.sqrt(np.maximum(s, 0).astype(np.float64) / den), 0.0)
     added = np.minimum(float(cfg.strength) * sigma(sy - sx), float(cfg.max_sigma))
     return GrainFit(sums[..., 0].copy(), sigma(sy), sigma(sx), added)

@@ -13,7 +13,7 @@ from typing import Callable, NamedTuple
 import numpy as np
 import torch
 
-from . import align_hip, blend_hip, deflicker, deflickeralign, detailmatch, detailmatch_bind, flickalign_hip, flicker_hip, grain_hip, grainmatch, hip, mask_hip, plate_hip, platealign, platefill, plategrain_hip, platetone, platetone_bind, seamblend, shadow_hip, shadowmask, spans_hip, tone_hip, tonematch
+from . import align_hip, blend_hip, deflicker, deflickeralign, detailmatch, detailmatch_bind, flickalign_hip, flicker_hip, grain_hip, grainmatch, grainshape, grainshape_bind, hip, mask_hip, plate_hip, platealign, platefill, plategrain_hip, platetone, platetone_bind, seamblend, shadow_hip, shadowmask, spans_hip, tone_hip, tonematch
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -710,8 +710,32 @@ def detail_report(parts, spans, T, K=1):
     return _merged(DetailMatchReport, (_zeros(dtype=np.int64), _zeros(), _zeros(), _zeros(dtype=bool), _zeros(dtype=bool)), parts, spans, T, K)
 
 
+class GrainShapeReport(NamedTuple):
+    """What grain shape fitted, per window k and frame t (K = 1 for the full frame).  Per channel and axis (0 = x, 1 = y): the counted pairs of
+    the frame's own ring, rho = the lag-1 correlation of the grain's response to Immerkaer's operator over the pooled ring, the a of the
+    shaping kernel [a, 1, a] that was applied (0: white), and whether the fit was cut at an end of [0, max_a] or fell into the dead zone.  Per
+    channel: k, the factor by which the white estimate of the level was raised.  Per channel and band: the sigma of the shaped noise added, at
+    pixel scale (grainshape.GrainShapeFit, stacked).  Frames outside every span, frames this rank does not hold and windows a span does not
+    have are zero rows with k = 1."""
+    pairs: np.ndarray           # [K,T,3,2] int64
+    rho: np.ndarray             # [K,T,3,2] float64
+    a: np.ndarray               # [K,T,3,2] float64
+    k: np.ndarray               # [K,T,3] float64
+    sigma_pixel: np.ndarray     # [K,T,3,4] float64
+    clamped: np.ndarray         # [K,T,3,2] bool
+    dead: np.ndarray            # [K,T,3,2] bool
+    n = property(lambda self: self.pairs)       # what _merged sizes the windows by
+
+
+def grain_shape_report(parts, spans, T, K=1):
+    """The report of a call over T frames from its clips' reports: parts[i] (finish's grain_shape_out) covers the frames spans[i] = (a, b); at
+    least K windows."""
+    return _merged(GrainShapeReport, (_zeros(3, 2, dtype=np.int64), _zeros(3, 2), _zeros(3, 2), lambda K, T: np.ones((K, T, 3)),
+                                      _zeros(3, grainmatch.BANDS), _zeros(3, 2, dtype=bool), _zeros(3, 2, dtype=bool)), parts, spans, T, K)
+
+
 def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return=False, tone=None, tone_out=None,
-           grain=None, grain_out=None, frame0=0, blend=None, blend_out=None, flicker=None, flicker_out=None, flicker_align=None, flicker_align_out=None,
+           grain=None, grain_out=None, grain_shape=None, grain_shape_out=None, frame0=0, blend=None, blend_out=None, flicker=None, flicker_out=None, flicker_align=None, flicker_align_out=None,
            detail=None, detail_out=None):
     """The model's frames into frames of the original size.  No plan and no stage (full_frame; reference :69-112): resize when the model ran
     at another size, feathered composite with the originals when keep_unmasked_original, in place in outs[0].  The reference returns from
@@ -754,7 +778,15 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
     detailmatch_bind.sharpen materialises the window's pixels at the window's size with that amount of their own high-pass added or taken
     away; everything above then reads the sharpened [n,h,w,3] patch at equal size, so tone, membrane and grain measure the sharpened
     rendering and the window ends in the same paste call.  One more window-sized clip buffer lives on the device meanwhile.  The clip's
-    DetailMatchReport is appended to detail_out.  Without detail nothing here changes and no vvd_ symbol is resolved."""
+    DetailMatchReport is appended to detail_out.  Without detail nothing here changes and no vvd_ symbol is resolved.
+    grain_shape (a grainshape.GrainShapeConfig, with grain; rules: include/grainshape.h): per window,
+    grainshape_bind.ring_shape_stats runs next to ring_grain_stats on the same looked-up pixels -- both are launched, then both [T,36] and
+    [T,30] sums come to the host behind the one synchronisation --, grainshape.fit gives the taps and the amplitudes of the white noise in
+    front of the shaping kernel, and the window ends in grainshape_bind.paste_shaped_composite, with or without blend's membrane.  The clip's
+    GrainShapeReport is appended to grain_shape_out; grain_out gets grain matching's own fit, whose sigma_added is then the white estimate and
+    not what was added.  Without grain_shape nothing here changes and no vvn_ symbol is resolved."""
+    if grain_shape is not None and grain is None:
+        raise ValueError("finish: grain_shape shapes the noise grain adds and needs it")
     H0, W0 = frames_rgb[0].shape[:2]
     T = len(outs[0])
     fsums = []      # deflicker: the [T,12] sums of every window filtered so far
@@ -816,7 +848,7 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
         # a shift that varies round the ring is correlated with the picture there and misleads a fitted gain; what varies is the membrane's to
         # take, so in front of it the tone stage fits the offset alone
         tone_cfg = tone if tone is None or blend is None else dataclasses.replace(tone, mode="offset")
-        tfits, gfits, bfits, dfits = [], [], [], []
+        tfits, gfits, bfits, dfits, nfits = [], [], [], [], []
 
         def whole(rows):        # [n,nsum] of this rank's frames -> [T,nsum], zero rows for the others
             sums = np.zeros((T, rows.shape[1]), np.int64)
@@ -838,9 +870,17 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
             elif grain is not None or blend is not None:
                 lut = torch.from_numpy(np.ascontiguousarray(ident)).to(dev)
             if grain is not None:
-                rows = grain_hip.ring_grain_stats(patch, src, mask, offs, lut, h, w, grain.ring, grain.flat).cpu().numpy()
+                rows = grain_hip.ring_grain_stats(patch, src, mask, offs, lut, h, w, grain.ring, grain.flat)
+                if grain_shape is not None:                                               # launched before the download: one synchronisation for both
+                    pairs = grainshape_bind.ring_shape_stats(patch, src, mask, offs, lut, h, w, grain.ring, grain.flat)
+                rows = rows.cpu().numpy()
                 gfits.append(grainmatch.fit(whole(rows), grain))
-                amp = torch.from_numpy(grainmatch.tables(gfits[-1].sigma_added[idx])).to(dev)
+                if grain_shape is not None:
+                    shaped = grainshape.fit(whole(pairs.cpu().numpy()), whole(rows), grain, grain_shape)
+                    nfits.append(shaped[:7])
+                    amp, taps = torch.from_numpy(shaped.amp[idx]).to(dev), torch.from_numpy(np.ascontiguousarray(shaped.taps[idx])).to(dev)
+                else:
+                    amp = torch.from_numpy(grainmatch.tables(gfits[-1].sigma_added[idx])).to(dev)
             if blend is not None:
                 rows, scratch = [], None
                 for a, b in seamblend.groups(n, h, w):
@@ -849,9 +889,15 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
                     field, _, part = blend_hip.solve(patch[a:b], src[a:b], mask[a:b], offs[a:b], lut[a:b], h, w, blend.ring, blend.presmooth,
                                                      blend.sweeps, blend.max_shift, scratch=scratch)
                     rows.append(part.cpu().numpy())
-                    blend_hip.paste_blend_composite(patch[a:b], src[a:b], mask[a:b], offs[a:b], lut[a:b], field, blend.strength_q8, amp[a:b],
-                                                    ids[a:b], seed, mode, h, w, feather, out=dst[a:b])
+                    if grain_shape is not None:
+                        grainshape_bind.paste_shaped_composite(patch[a:b], src[a:b], mask[a:b], offs[a:b], lut[a:b], field, blend.strength_q8, amp[a:b],
+                                                               taps[a:b], ids[a:b], seed, mode, h, w, feather, out=dst[a:b])
+                    else:
+                        blend_hip.paste_blend_composite(patch[a:b], src[a:b], mask[a:b], offs[a:b], lut[a:b], field, blend.strength_q8, amp[a:b],
+                                                        ids[a:b], seed, mode, h, w, feather, out=dst[a:b])
                 bfits.append(seamblend.fit(whole(np.concatenate(rows))))
+            elif grain_shape is not None:
+                grainshape_bind.paste_shaped_composite(patch, src, mask, offs, lut, None, 0, amp, taps, ids, seed, mode, h, w, feather, out=dst)
             elif grain is not None:
                 grain_hip.paste_grain_composite(patch, src, mask, offs, lut, amp, ids, seed, mode, h, w, feather, out=dst)
             elif tone is not None:
@@ -859,14 +905,15 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
             else:
                 hip.roi_paste_composite(patch, src, mask, offs, h, w, feather, out=dst)
         for fits, out, report in ((tfits, tone_out, ToneMatchReport), (gfits, grain_out, GrainMatchReport), (bfits, blend_out, SeamBlendReport),
-                                  (dfits, detail_out, DetailMatchReport)):
+                                  (dfits, detail_out, DetailMatchReport), (nfits, grain_shape_out, GrainShapeReport)):
             if fits and out is not None:
                 out.append(report(*(np.stack(f) for f in zip(*fits))))
         return bufs[len(wins) % 2]
 
     if seam or plans:
         asked = [(out, empty, len(out)) for cfg, out, empty in ((tone, tone_out, tone_report), (grain, grain_out, grain_report),
-                                                                 (blend, blend_out, seam_blend_report), (detail, detail_out, detail_report))
+                                                                 (blend, blend_out, seam_blend_report), (detail, detail_out, detail_report),
+                                                                 (grain_shape, grain_shape_out, grain_shape_report))
                  if cfg is not None and out is not None]
         res = _on_device(list(outs[0]) if plans else outs[0], T, dev, pasted)
         for out, empty, before in asked:
