@@ -156,22 +156,37 @@ class FlowCompleteNet:
         self.d10, self.d12 = _Conv(ctx, f"{name}.decoder1.0", c2, c2), _Conv(ctx, f"{name}.decoder1.2.conv", c2, c1)
         self.u0, self.u2 = _Conv(ctx, f"{name}.upsample.0", c1, c1), _Conv(ctx, f"{name}.upsample.2.conv", c1, 2)
 
-    def complete(self, flow, mask_u8):
-        """flow fp32 [T,H,W,2] (masked inside by this call), mask u8 [T,H,W] (non-zero = hole), H, W % 8 == 0 -> fp32 [T*H*W, 2]."""
+    # the stages of `complete`, callable one by one (tests/test_fc_stages_gpu.py); T frames, H x W the full resolution
+    def input_stage(self, flow, mask_u8):
+        """vv_fc_input + downsample.0: flow fp32 [T,H,W,2], mask u8 [T,H,W] -> h16 [T*(H/2)*(W/2), c1]."""
         T, H, W, _ = flow.shape
-        if H % 8 or W % 8:
-            raise RuntimeError(f"FlowCompleteNet: H={H}, W={W} must be multiples of 8")
-        dt = self.ctx.dt
         xin = hip.fc_input(flow.contiguous(), mask_u8.contiguous(), 2)
-        x, H2, W2 = self.down(xin.reshape(-1, 8), T, H + 4, W + 4, stride=2, pad=0, act=0.2)
+        x, _, _ = self.down(xin.reshape(-1, 8), T, H + 4, W + 4, stride=2, pad=0, act=0.2)
+        return x
+
+    def encoder1(self, x, T, H2, W2):
+        """h16 [T*H2*W2, c1] -> h16 [T*(H2/2)*(W2/2), c2]."""
         e1, _, _ = self.e10(x, T, H2, W2)
-        e1, H4, W4 = self.e12(e1, T, H2, W2)
+        e1, _, _ = self.e12(e1, T, H2, W2)
+        return e1
+
+    def encoder2(self, e1, T, H4, W4):
+        """h16 [T*H4*W4, c2] -> h16 [T*(H4/2)*(W4/2), c3]."""
         e2, _, _ = self.e20(e1, T, H4, W4)
-        e2, H8, W8 = self.e22(e2, T, H4, W4)
+        e2, _, _ = self.e22(e2, T, H4, W4)
+        return e2
+
+    def middle(self, e2, T, H8, W8):
+        """the three dilated convolutions: h16 [T*H8*W8, c3] -> fp32."""
         mid = e2
         for i, conv in enumerate(self.mid):
             mid = conv(mid, T, H8, W8, 0.2, torch.float32 if i == 2 else self.ctx.h16)
-        prop = self.prop(mid, T, H8, W8)
+        return mid
+
+    def decoder(self, prop, e1, T, H, W):
+        """decoder2 + encoder1 skip, decoder1, upsample: prop fp32 [T*(H/8)*(W/8), c3], e1 h16 [T*(H/4)*(W/4), c2] -> fp32 [T*H*W, 2]."""
+        dt = self.ctx.dt
+        H2, W2, H4, W4, H8, W8 = H // 2, W // 2, H // 4, W // 4, H // 8, W // 8
         d2, _, _ = self.d20(prop, T, H8, W8, act=0.2)
         d2, _, _ = self.d22(hip.upsample2x_bilinear(dt, d2, T, H8, W8), T, H4, W4, act=0.2, out_dtype=torch.float32)
         hip.add_inplace(dt, d2, e1)
@@ -180,6 +195,18 @@ class FlowCompleteNet:
         up, _, _ = self.u0(d1, T, H2, W2, act=0.2)
         pred, _, _ = self.u2(hip.upsample2x_bilinear(dt, up, T, H2, W2), T, H, W, out_dtype=torch.float32)
         return pred
+
+    def complete(self, flow, mask_u8):
+        """flow fp32 [T,H,W,2] (masked inside by this call), mask u8 [T,H,W] (non-zero = hole), H, W % 8 == 0 -> fp32 [T*H*W, 2]."""
+        T, H, W, _ = flow.shape
+        if H % 8 or W % 8:
+            raise RuntimeError(f"FlowCompleteNet: H={H}, W={W} must be multiples of 8")
+        x = self.input_stage(flow, mask_u8)
+        e1 = self.encoder1(x, T, H // 2, W // 2)
+        e2 = self.encoder2(e1, T, H // 4, W // 4)
+        mid = self.middle(e2, T, H // 8, W // 8)
+        prop = self.prop(mid, T, H // 8, W // 8)
+        return self.decoder(prop, e1, T, H, W)
 
     def forward_bidirect_flow(self, flows_fw, flows_bw, masks_u8):
         """flows fp32 [T-1,H,W,2] (t -> t+1 / t+1 -> t), masks u8 [T,H,W] -> raw predictions (fw, bw), each fp32 [T-1,H,W,2]."""
