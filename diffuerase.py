@@ -29,7 +29,9 @@ deflicker (inpaint deflicker: the model's pixels are filtered along time before 
 neighbours within a tolerance, so that the patch stops shimmering while moving edges stay as they are: videovanish_amd/deflicker.py; also
 configure(deflicker=...) and $VV_DEFLICKER), deflicker_align (aligned inpaint deflicker: with deflicker, one integer translation per frame is
 tracked first, so that the filter follows a panning camera: videovanish_amd/deflickeralign.py; also configure(deflicker_align=...) and
-$VV_DEFLICKER_ALIGN).
+$VV_DEFLICKER_ALIGN), deflicker_local (block-matched inpaint deflicker: with deflicker, one integer displacement per small block and temporal
+neighbour is found by block matching first, so that the filter follows parallax, a zoom and a second plane of motion:
+videovanish_amd/deflickerlocal.py; also configure(deflicker_local=...) and $VV_DEFLICKER_LOCAL).
 There is no CPU fallback: without the HIP extension / a GPU this raises.
 
 This file is the boundary: the reference's names and module state, the settings, and the stages (weights, prior, model) that read that state.
@@ -44,7 +46,7 @@ import torch
 
 from videovanish_amd import hip, infill
 from videovanish_amd import deflicker as deflicker_settings
-from videovanish_amd import deflickeralign, detailmatch, grainmatch, grainshape, maskclean, platealign, platefill, plategrain, platetone, seamblend, shadowmask, tonematch
+from videovanish_amd import deflickeralign, deflickerlocal, detailmatch, grainmatch, grainshape, maskclean, platealign, platefill, plategrain, platetone, seamblend, shadowmask, tonematch
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
 from videovanish_amd.config import RunConfig
@@ -75,6 +77,7 @@ last_deflicker = None   # the infill.DeflickerReport of the last run_infill_on_f
 last_deflicker_align = None  # the infill.DeflickerAlignReport of the last run_infill_on_frames call; None when the tracker did not run
 last_detail_match = None     # the infill.DetailMatchReport of the last run_infill_on_frames call; None when the stage did not run
 last_grain_shape = None      # the infill.GrainShapeReport of the last run_infill_on_frames call; None when the shape was not asked for
+last_deflicker_local = None  # the infill.DeflickerLocalReport of the last run_infill_on_frames call; None when the search was not asked for
 
 
 class Option(NamedTuple):
@@ -108,6 +111,7 @@ MORE_OPTIONS = (
     Option("detail_match", detailmatch, "VV_DETAIL_MATCH", "seam detail matching",
            "on|ring=8,edge=12,smooth=2,min_pixels=256,max_sharpen=2.0,max_soften=1.0,dead=0.06,overshoot=4,strength=1.0"),
     Option("grain_shape", grainshape, "VV_GRAIN_SHAPE", "grain shape", "on|max_a=0.5,dead=0.05,min_pairs=512,smooth=4,max_gain=6"),
+    Option("deflicker_local", deflickerlocal, "VV_DEFLICKER_LOCAL", "block-matched inpaint deflicker", "on|block=8,search=4,lam=32"),
 )
 ALL_OPTIONS = OPTIONS + MORE_OPTIONS
 _OPTION = {o.name: o for o in ALL_OPTIONS}
@@ -115,7 +119,7 @@ _configured = {}        # configure(<option>=...): the value for calls that do n
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
-              mask_clean=None, tone_match=None, grain_match=None, grain_shape=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
+              mask_clean=None, tone_match=None, grain_match=None, grain_shape=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, deflicker_local=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -157,7 +161,9 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     deflicker = None / "on" / "radius=2,tol=12" (any subset) / a deflicker.DeflickerConfig: inpaint deflicker for calls that do not pass
     deflicker=.
     deflicker_align = None / "on" / "levels=4,radius=4,min_overlap=25,max_residual=12" (any subset) / a platealign.PlateAlignConfig: aligned
-    inpaint deflicker for calls that do not pass deflicker_align=."""
+    inpaint deflicker for calls that do not pass deflicker_align=.
+    deflicker_local = None / "on" / "block=8,search=4,lam=32" (any subset) / a deflickerlocal.DeflickerLocalConfig: block-matched inpaint
+    deflicker for calls that do not pass deflicker_local=."""
     global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded
     given = locals()
     for o in reversed(ALL_OPTIONS):         # validated now, kept as given: configure(roi="off") means the full frame whatever $VV_ROI says
@@ -308,10 +314,17 @@ def deflicker_align_config(deflicker_align=None):
     return _setting("deflicker_align", deflicker_align)
 
 
+def deflicker_local_config(deflicker_local=None):
+    """The block-matched deflicker setting a call runs with: its own deflicker_local= argument, else configure(deflicker_local=...), else
+    $VV_DEFLICKER_LOCAL (on | off | block=N,search=N,lam=N).  None = the filter reads its neighbours at one place per frame.
+    deflicker_local="off" (or False) asks for that whatever configure() or the environment say."""
+    return _setting("deflicker_local", deflicker_local)
+
+
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
-                         mask_clean=None, tone_match=None, grain_match=None, grain_shape=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
+                         mask_clean=None, tone_match=None, grain_match=None, grain_shape=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, deflicker_local=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -408,15 +421,23 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     place where the same piece of background sits in that neighbour frame (rules: include/vvflickalign.h), so that the patch stops shimmering
     under a pan or tilt too.  A frame the tracker loses takes no sample and gives none; after a cut inside a clip call every later frame is
     lost and stays unfiltered: spans="cuts" (or "masked-cuts") splits the call there.  A locked-off clip gives the bytes of deflicker alone.
-    What it found is kept in last_deflicker_align.  Without an effective deflicker it is a ValueError."""
-    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_plate_grain, last_plate_tone, last_shadow_mask, last_deflicker, last_deflicker_align, last_detail_match, last_grain_shape
+    What it found is kept in last_deflicker_align.  Without an effective deflicker it is a ValueError.
+    deflicker_local (block-matched inpaint deflicker, opt-in, needs deflicker): "on" / "block=8,search=4,lam=32" / a
+    videovanish_amd.deflickerlocal.DeflickerLocalConfig cuts every window into blocks of `block` x `block` pixels and finds, per block and
+    temporal neighbour, the integer displacement of at most `search` px whose summed byte difference plus `lam` per px of displacement is
+    smallest (block matching on the model's own pixels; rules: include/flicklocal.h); the filter then reads every neighbour along its block's
+    vector, so that the patch stops shimmering under parallax, a zoom and in front of a second plane of motion too.  With deflicker_align
+    the search starts from the tracked translation.  The gate is unchanged: no byte moves more than the deflicker's `tol`.  search=0 and a
+    deflicker of radius 0 give the bytes of the call without it.  What the search found is kept in last_deflicker_local, what the gate then
+    accepted in last_deflicker.  Without an effective deflicker it is a ValueError."""
+    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_plate_grain, last_plate_tone, last_shadow_mask, last_deflicker, last_deflicker_align, last_deflicker_local, last_detail_match, last_grain_shape
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
     ccfg = mask_clean_config(mask_clean)
     tcfg = tone_match_config(tone_match)
     gcfg = grain_match_config(grain_match)
     fcfg = deflicker_config(deflicker)
-    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_plate_grain = last_plate_tone = last_shadow_mask = last_deflicker = last_deflicker_align = last_detail_match = last_grain_shape = None
+    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_plate_grain = last_plate_tone = last_shadow_mask = last_deflicker = last_deflicker_align = last_deflicker_local = last_detail_match = last_grain_shape = None
     dcfg = detail_match_config(detail_match)
     ncfg = grain_shape_config(grain_shape)
     if ncfg is not None and gcfg is None:
@@ -435,10 +456,13 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     facfg = deflicker_align_config(deflicker_align)
     if facfg is not None and fcfg is None:
         raise ValueError("deflicker_align= (aligned inpaint deflicker) needs deflicker= (inpaint deflicker)")
+    flcfg = deflicker_local_config(deflicker_local)
+    if flcfg is not None and fcfg is None:
+        raise ValueError("deflicker_local= (block-matched inpaint deflicker) needs deflicker= (inpaint deflicker)")
     bcfg = seam_blend_config(seam_blend, feather_px if keep_unmasked_original else None)
     if compat_reference_early_return:
         on = dict(roi=rcfg, spans=scfg, mask_clean=ccfg, tone_match=tcfg, grain_match=gcfg, seam_blend=bcfg, plate_fill=pcfg, plate_align=acfg,
-                  plate_grain=lcfg, plate_tone=ecfg, shadow_mask=hcfg, deflicker=fcfg, deflicker_align=facfg, detail_match=dcfg, grain_shape=ncfg)
+                  plate_grain=lcfg, plate_tone=ecfg, shadow_mask=hcfg, deflicker=fcfg, deflicker_align=facfg, deflicker_local=flcfg, detail_match=dcfg, grain_shape=ncfg)
         for o in ALL_OPTIONS:
             if on[o.name] is not None:
                 raise ValueError(f"{o.name}= ({o.phrase}) cannot be combined with compat_reference_early_return=True")
@@ -481,7 +505,7 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
 
     seam = {}               # finish's keywords of the stages that are on; each *_out list gets one report per clip call, in the order of the spans
     for key, cfg in (("tone", tcfg), ("grain", gcfg), ("blend", bcfg), ("flicker", fcfg), ("flicker_align", facfg), ("detail", dcfg),
-                     ("grain_shape", ncfg)):
+                     ("grain_shape", ncfg), ("flicker_local", flcfg)):
         if cfg is not None:
             seam.update({key: cfg, key + "_out": []})
 
@@ -506,6 +530,8 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         last_deflicker = infill.deflicker_report(seam["flicker_out"], plan, T)
     if facfg is not None:
         last_deflicker_align = infill.deflicker_align_report(seam["flicker_align_out"], plan)
+    if flcfg is not None:
+        last_deflicker_local = infill.deflicker_local_report(seam["flicker_local_out"], plan, T)
     if dcfg is not None:
         last_detail_match = infill.detail_report(seam["detail_out"], plan, T)
     if ncfg is not None:
@@ -648,6 +674,11 @@ def main():
                     help="With --deflicker: track one integer translation per frame first (the tracker of --plate-align, per span) and read the "
                          "filter's temporal neighbours along it, so the patch stops shimmering under a pan or tilt too.  A frame the tracker "
                          "loses stays unfiltered; split at cuts with --spans cuts.  Prints one line with what it tracked.")
+    ap.add_argument("--deflicker-local", type=_setting_arg("deflicker_local"), default=None, metavar=_OPTION["deflicker_local"].metavar,
+                    help="With --deflicker: find one integer displacement per `block` x `block` pixels and temporal neighbour first (block matching "
+                         "within +-`search` px, `lam` per px of displacement against flat blocks' wandering) and read the filter's temporal "
+                         "neighbours along it, so the patch stops shimmering under parallax, a zoom and in front of moving background too.  "
+                         "Composes with --deflicker-align.  Prints one line with what it found.")
     ap.add_argument("--cuts", type=span_plan.parse_cuts, default=None, metavar="120,431",
                     help="Frame indices (relative to --start_frame) where a new shot begins: used instead of the detector.")
     args = ap.parse_args()
@@ -732,6 +763,12 @@ def main():
         lost = sum(int((~k).sum()) for k in r.tracked)
         far = max([int(np.abs(o[k]).max()) for o, k in zip(r.off, r.tracked) if k.any()] + [0])
         print(f"deflicker align: {len(r.path)} clip calls ({paths}), {lost} of {sum(len(k) for k in r.tracked)} frames lost, largest |offset| {far} px")
+    if args.deflicker_local is not None and last_deflicker_local is not None:
+        r = last_deflicker_local
+        matched, inside = int(r.blocks.sum()), 0 if last_deflicker is None else int(last_deflicker.n_mask.sum())
+        mean_n = float((last_deflicker.samples_mask * last_deflicker.n_mask).sum() / inside) if inside else 0.0
+        print(f"deflicker local: {matched} blocks matched, {100.0 * int(r.moved.sum()) / max(matched, 1):.1f} % of them moved, largest |vector| "
+              f"{int(r.max_vector.max(initial=0))} px, mean accepted samples inside the mask {mean_n:.2f}")
     tools.write_video_frames_to_path(out_video, out_frames, fps, H0, W0)
 
 

@@ -2,18 +2,18 @@
 (shadow_mask), the clean-plate fill (plate_fill), the temporal plan (span_plan, run_spans), and for each clip the windows (region_plans, run_clip), ONE crop -> prior -> model
 sequence (run_windows) and ONE closing step (finish).  The full frame is no window, roi= "static" / "follow" one, the "-regions" spellings
 several.  The closing step is one loop over the windows; in it the opt-in seam stages run on each window's pixels before they are pasted: the
-deflicker along time (with its alignment along a translation tracked per clip call), the tone fit to the ring round the mask, the grain the
+deflicker along time (with its alignment along a translation tracked per clip call and along block-matched vectors), the tone fit to the ring round the mask, the grain the
 ring's originals have and the model's pixels lack, the membrane that carries the ring's difference original - model into the hole.  Each stage
-reports per clip call; tone_report, grain_report, seam_blend_report, deflicker_report, deflicker_align_report and detail_report assemble a call's
+reports per clip call; tone_report, grain_report, seam_blend_report, deflicker_report, deflicker_align_report, deflicker_local_report and detail_report assemble a call's
 report from them.  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is module state.  Rules and reasons: DESIGN.md
-§10, §11, §12, §13, §14, §15, §16, §17, §18, §19, §21, §23, §24."""
+§10, §11, §12, §13, §14, §15, §16, §17, §18, §19, §21, §23, §24, §26."""
 import dataclasses
 from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
 
-from . import align_hip, blend_hip, deflicker, deflickeralign, detailmatch, detailmatch_bind, flickalign_hip, flicker_hip, grain_hip, grainmatch, grainshape, grainshape_bind, hip, mask_hip, plate_hip, platealign, platefill, plategrain_hip, platetone, platetone_bind, seamblend, shadow_hip, shadowmask, spans_hip, tone_hip, tonematch
+from . import align_hip, blend_hip, deflicker, deflickeralign, deflickerlocal, detailmatch, detailmatch_bind, flickalign_hip, flicker_hip, flicklocal_bind, grain_hip, grainmatch, grainshape, grainshape_bind, hip, mask_hip, plate_hip, platealign, platefill, plategrain_hip, platetone, platetone_bind, seamblend, shadow_hip, shadowmask, spans_hip, tone_hip, tonematch
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -692,6 +692,28 @@ def deflicker_align_report(parts, spans):
     return DeflickerAlignReport(*(tuple(c) for c in ([list(v) for v in zip(*cols)] or [[] for _ in range(5)])), tuple(tuple(s) for s in spans))
 
 
+class DeflickerLocalReport(NamedTuple):
+    """What the block matching of finish(flicker_local=) found, per window k and frame t (K = 1 for the full frame), over the frame's temporal
+    neighbours: the block and neighbour pairs that got a vector, how many of those vectors are not zero, the mean |dy| + |dx| and the largest
+    max(|dy|, |dx|) over the matched ones, and the winners' summed cost against the zero candidate's where that one was valid
+    (deflickerlocal.DeflickerLocalFit, stacked: exact integer sums).  What the gate then accepted stands in the DeflickerReport.  Frames outside
+    every span, frames this rank does not hold, windows a span does not have and calls with radius = 0 are zero rows."""
+    blocks: np.ndarray          # [K,T] int64
+    moved: np.ndarray           # [K,T] int64
+    mean_vector: np.ndarray     # [K,T] float64
+    max_vector: np.ndarray      # [K,T] int64
+    cost: np.ndarray            # [K,T] int64
+    cost_zero: np.ndarray       # [K,T] int64
+    n = property(lambda self: self.blocks)      # what _merged sizes the windows by
+
+
+def deflicker_local_report(parts, spans, T, K=1):
+    """The report of a call over T frames from its clips' reports: parts[i] (finish's flicker_local_out) covers the frames spans[i] = (a, b); at
+    least K windows."""
+    i64 = _zeros(dtype=np.int64)
+    return _merged(DeflickerLocalReport, (i64, i64, _zeros(), i64, i64, i64), parts, spans, T, K)
+
+
 class DetailMatchReport(NamedTuple):
     """What seam detail matching measured and applied, per window k and frame t (K = 1 for the full frame): the counted pixels of the frame's own
     ring, the amount of the model's own high-pass added (negative: taken away; 0: the frame is left as it is), the mean of (H(original) -
@@ -735,8 +757,8 @@ def grain_shape_report(parts, spans, T, K=1):
 
 
 def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, dev, compat_reference_early_return=False, tone=None, tone_out=None,
-           grain=None, grain_out=None, grain_shape=None, grain_shape_out=None, frame0=0, blend=None, blend_out=None, flicker=None, flicker_out=None, flicker_align=None, flicker_align_out=None,
-           detail=None, detail_out=None):
+           grain=None, grain_out=None, grain_shape=None, grain_shape_out=None, frame0=0, blend=None, blend_out=None, flicker=None, flicker_out=None, flicker_local=None, flicker_local_out=None,
+           flicker_align=None, flicker_align_out=None, detail=None, detail_out=None):
     """The model's frames into frames of the original size.  No plan and no stage (full_frame; reference :69-112): resize when the model ran
     at another size, feathered composite with the originals when keep_unmasked_original, in place in outs[0].  The reference returns from
     inside its loop (:114) so only frame 0 is post-processed; the evident intent (all frames) is the default here,
@@ -772,6 +794,12 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
     whose frames all sit at offset zero ("static") take the unaligned filter exactly as above, fixed form included.  A frame the tracker
     loses (after a cut inside the clip call: every later frame) stays unfiltered.  (track, path) of the clip call is appended to
     flicker_align_out (deflicker_align_report).  Without flicker_align nothing here changes and no vvc_ symbol is resolved.
+    flicker_local (a deflickerlocal.DeflickerLocalConfig, with flicker; rules: include/flicklocal.h): in model_px, after
+    window_pixels and with flicker.radius > 0, flicklocal_bind.search finds one displacement per block and temporal neighbour on the window's
+    own pixels and flicklocal_bind.hold filters along them, in place of flicker_hip.hold / flickalign_hip.hold; the track is flicker_align's
+    when its path is "tracked", else none (the binding's zero track).  The vectors stay on the device; the [T,2 radius+1,6] statistics come to
+    the host beside the filter's sums.  The clip's DeflickerLocalReport is appended to flicker_local_out.  With radius = 0 the path above
+    runs as it is.  Without flicker_local nothing here changes and no vvk_ symbol is resolved.
     detail (a detailmatch.DetailMatchConfig; rules: include/detailmatch.h): a seam stage, so the full frame takes the loop as
     the window (0, 0, H0, W0).  Per window, directly after model_px (after the deflicker): ring_detail_stats of the model's pixels against the
     running buffer, the [T,12] sums to the host (one synchronisation), detailmatch.fit, the [T] amounts to the device, and
@@ -787,9 +815,12 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
     not what was added.  Without grain_shape nothing here changes and no vvn_ symbol is resolved."""
     if grain_shape is not None and grain is None:
         raise ValueError("finish: grain_shape shapes the noise grain adds and needs it")
+    if flicker_local is not None and flicker is None:
+        raise ValueError("finish: flicker_local gives the deflicker its vectors and needs flicker")
     H0, W0 = frames_rgb[0].shape[:2]
     T = len(outs[0])
     fsums = []      # deflicker: the [T,12] sums of every window filtered so far
+    lstats = []     # deflicker_local: the [T,2 radius+1,6] statistics of every window searched so far
     ftrack = []     # deflicker_align: (track on the device | None, track on the host, path) of this clip call, found by the first model_px
 
     def tracked():
@@ -815,11 +846,17 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
         win = flicker_hip.window_pixels(up(o).contiguous(), h, w)
         offs = torch.from_numpy(place).to(dev) if offs is None else offs
         mask = dil_t[idx].contiguous() if mask is None else mask
-        if flicker_align is not None and tracked()[2] == "tracked":
+        if flicker_local is not None and flicker.radius > 0:
+            track = tracked()[0] if flicker_align is not None and tracked()[2] == "tracked" else None
+            mv, stats = flicklocal_bind.search(win, offs, track, flicker.radius, flicker_local)
+            held, sums = flicklocal_bind.hold(win, offs, track, mv, mask, flicker.radius, flicker_local.block, flicker.tol)
+        elif flicker_align is not None and tracked()[2] == "tracked":
             held, sums = flickalign_hip.hold(win, offs, tracked()[0], mask, flicker.radius, flicker.tol)
         else:
             held, sums = flicker_hip.hold(win, offs, mask, flicker.radius, flicker.tol, fixed=bool((place == place[0]).all()))
         fsums.append(sums.cpu().numpy())
+        if flicker_local is not None:
+            lstats.append(stats.cpu().numpy() if flicker.radius > 0 else np.zeros((T, 1, deflickerlocal.NSTAT), np.int64))
         return held
 
     def full_frame(idx, up):
@@ -926,6 +963,11 @@ def finish(outs, frames_rgb, dil_t, plans, feather_px, keep_unmasked_original, d
             flicker_out.append(DeflickerReport(*(np.stack(f) for f in zip(*(deflicker.fit(s) for s in fsums)))))
         else:                                                                             # this rank holds no frame of the clip: zero rows
             flicker_out.append(deflicker_report([], [], T, K=max(len(plans), 1)))
+    if flicker_local is not None and flicker_local_out is not None:
+        if lstats:
+            flicker_local_out.append(DeflickerLocalReport(*(np.stack(f) for f in zip(*(deflickerlocal.fit(s) for s in lstats)))))
+        else:                                                                             # this rank holds no frame of the clip: zero rows
+            flicker_local_out.append(deflicker_local_report([], [], T, K=max(len(plans), 1)))
     if flicker_align is not None and flicker_align_out is not None:                       # no model_px on this rank: nothing tracked
         flicker_align_out.append(ftrack[0][1:] if ftrack else (deflickeralign.identity_track(T), "none"))
     return res
