@@ -25,6 +25,9 @@ samples it and every filled pixel back to its own frame's, so that the fill surv
 also configure(plate_tone=...) and $VV_PLATE_TONE),
 shadow_mask (shadow masking: unmasked pixels that look like the shot's clean background uniformly darkened and hang on to the mask join it,
 between the mask clean-up and the clean-plate fill: videovanish_amd/shadowmask.py; also configure(shadow_mask=...) and $VV_SHADOW_MASK),
+overlay_mask (overlay masking: screen-fixed graphics -- a station logo, a channel bug -- are found from the edges that stand still while the
+picture under them moves and join the mask of every frame, between the mask clean-up and the shadow masking: videovanish_amd/overlaymask.py;
+also configure(overlay_mask=...), $VV_OVERLAY_MASK and find_overlays()),
 deflicker (inpaint deflicker: the model's pixels are filtered along time before every other seam stage reads them, each the mean of its temporal
 neighbours within a tolerance, so that the patch stops shimmering while moving edges stay as they are: videovanish_amd/deflicker.py; also
 configure(deflicker=...) and $VV_DEFLICKER), deflicker_align (aligned inpaint deflicker: with deflicker, one integer translation per frame is
@@ -46,7 +49,7 @@ import torch
 
 from videovanish_amd import hip, infill
 from videovanish_amd import deflicker as deflicker_settings
-from videovanish_amd import deflickeralign, deflickerlocal, detailmatch, grainmatch, grainshape, maskclean, platealign, platefill, plategrain, platetone, seamblend, shadowmask, tonematch
+from videovanish_amd import deflickeralign, deflickerlocal, detailmatch, grainmatch, grainshape, maskclean, overlaymask, platealign, platefill, plategrain, platetone, seamblend, shadowmask, tonematch
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
 from videovanish_amd.config import RunConfig
@@ -78,6 +81,7 @@ last_deflicker_align = None  # the infill.DeflickerAlignReport of the last run_i
 last_detail_match = None     # the infill.DetailMatchReport of the last run_infill_on_frames call; None when the stage did not run
 last_grain_shape = None      # the infill.GrainShapeReport of the last run_infill_on_frames call; None when the shape was not asked for
 last_deflicker_local = None  # the infill.DeflickerLocalReport of the last run_infill_on_frames call; None when the search was not asked for
+last_overlay_mask = None     # the infill.OverlayMaskReport of the last run_infill_on_frames call; None when the stage did not run
 
 
 class Option(NamedTuple):
@@ -112,6 +116,8 @@ MORE_OPTIONS = (
            "on|ring=8,edge=12,smooth=2,min_pixels=256,max_sharpen=2.0,max_soften=1.0,dead=0.06,overshoot=4,strength=1.0"),
     Option("grain_shape", grainshape, "VV_GRAIN_SHAPE", "grain shape", "on|max_a=0.5,dead=0.05,min_pairs=512,smooth=4,max_gain=6"),
     Option("deflicker_local", deflickerlocal, "VV_DEFLICKER_LOCAL", "block-matched inpaint deflicker", "on|block=8,search=4,lam=32"),
+    Option("overlay_mask", overlaymask, "VV_OVERLAY_MASK", "overlay masking",
+           "on|min_samples=12,mag=8,coh=80,max_share=25,close=2,max_hole=4096,min_area=64,max_area=10,border=0,grow=3"),
 )
 ALL_OPTIONS = OPTIONS + MORE_OPTIONS
 _OPTION = {o.name: o for o in ALL_OPTIONS}
@@ -119,7 +125,7 @@ _configured = {}        # configure(<option>=...): the value for calls that do n
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
-              mask_clean=None, tone_match=None, grain_match=None, grain_shape=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, deflicker_local=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
+              mask_clean=None, tone_match=None, grain_match=None, grain_shape=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, deflicker_local=None, overlay_mask=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -158,6 +164,8 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     clean-plate exposure matching for calls that do not pass plate_tone=.
     shadow_mask = None / "on" / "guard=1,min_samples=4,tol=6,lo=30,hi=90,drop=12,chroma=20,floor=16,reach=32,min_area=16,grow=1,max_bytes=N" (any
     subset) / a shadowmask.ShadowMaskConfig: shadow masking for calls that do not pass shadow_mask=.
+    overlay_mask = None / "on" / "min_samples=12,mag=8,coh=80,max_share=25,close=2,max_hole=4096,min_area=64,max_area=10,border=0,grow=3,
+    max_bytes=N" (any subset) / an overlaymask.OverlayMaskConfig: overlay masking for calls that do not pass overlay_mask=.
     deflicker = None / "on" / "radius=2,tol=12" (any subset) / a deflicker.DeflickerConfig: inpaint deflicker for calls that do not pass
     deflicker=.
     deflicker_align = None / "on" / "levels=4,radius=4,min_overlap=25,max_residual=12" (any subset) / a platealign.PlateAlignConfig: aligned
@@ -301,6 +309,13 @@ def shadow_mask_config(shadow_mask=None):
     return _setting("shadow_mask", shadow_mask)
 
 
+def overlay_mask_config(overlay_mask=None):
+    """The overlay masking setting a call runs with: its own overlay_mask= argument, else configure(overlay_mask=...), else $VV_OVERLAY_MASK (on |
+    off | min_samples=N,mag=N,coh=N,max_share=N,close=N,max_hole=N,min_area=N,max_area=N,border=N,grow=N,max_bytes=N).  None = the masks as
+    they are.  overlay_mask="off" (or False) asks for that whatever configure() or the environment say."""
+    return _setting("overlay_mask", overlay_mask)
+
+
 def deflicker_config(deflicker=None):
     """The inpaint deflicker setting a call runs with: its own deflicker= argument, else configure(deflicker=...), else $VV_DEFLICKER (on | off |
     radius=N,tol=N).  None = no deflicker.  deflicker="off" (or False) asks for none whatever configure() or the environment say."""
@@ -324,7 +339,7 @@ def deflicker_local_config(deflicker_local=None):
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
-                         mask_clean=None, tone_match=None, grain_match=None, grain_shape=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, deflicker_local=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
+                         mask_clean=None, tone_match=None, grain_match=None, grain_shape=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, deflicker_local=None, overlay_mask=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -408,6 +423,16 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     never a frame byte; the larger masks replace the dilated ones for the clean-plate fill, the planners, the prior, the model and the
     composite.  It needs neither plate_fill nor a locked-off camera: where the shot shows no steady background (a pan) nothing is added, and
     the call's bytes are those of the call without it.  What it added is kept in last_shadow_mask.
+    overlay_mask (overlay masking, opt-in): "on" / "min_samples=12,mag=8,coh=80,max_share=25,close=2,max_hole=4096,min_area=64,max_area=10,
+    border=0,grow=3,max_bytes=N" / a videovanish_amd.overlaymask.OverlayMaskConfig finds, after the mask clean-up and before the shadow
+    masking, the screen-fixed graphics of the clip -- a station logo, a channel bug, the frame of a timestamp -- and adds them to the mask of
+    every frame (infill.overlay_mask; rules: include/overlaymask.h): over the whole call and per pixel the luma gradients of the unmasked
+    frames are summed with their signs and by magnitude, a pixel whose gradient kept its direction is a persistent edge, the edges are
+    closed, the holes they enclose filled, and the parts of a plausible size away from the frame's border join the mask, grown by `grow`.
+    mask_frames may be all zero: the stage is a mask where none was painted.  Masks change, never a frame byte; the larger masks replace
+    the dilated ones for every later stage.  The rule needs the background to travel: a clip in which more than `max_share` percent of the
+    strong gradients are persistent is called static, nothing is added and the call's bytes are those of the call without it.  What it
+    found, every box included, is kept in last_overlay_mask; find_overlays() gives the same answer without loading a model.
     deflicker (inpaint deflicker, opt-in): "on" / "radius=2,tol=12" / a videovanish_amd.deflicker.DeflickerConfig filters the model's pixels
     along time where they reach the device, for the full frame and for every roi window, inside each span (infill.finish; rules:
     include/vvflicker.h): every pixel becomes the rounded mean of those of its neighbours at most `radius` frames away that lie within `tol`
@@ -430,14 +455,14 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     the search starts from the tracked translation.  The gate is unchanged: no byte moves more than the deflicker's `tol`.  search=0 and a
     deflicker of radius 0 give the bytes of the call without it.  What the search found is kept in last_deflicker_local, what the gate then
     accepted in last_deflicker.  Without an effective deflicker it is a ValueError."""
-    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_plate_grain, last_plate_tone, last_shadow_mask, last_deflicker, last_deflicker_align, last_deflicker_local, last_detail_match, last_grain_shape
+    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_plate_grain, last_plate_tone, last_shadow_mask, last_deflicker, last_deflicker_align, last_deflicker_local, last_detail_match, last_grain_shape, last_overlay_mask
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
     ccfg = mask_clean_config(mask_clean)
     tcfg = tone_match_config(tone_match)
     gcfg = grain_match_config(grain_match)
     fcfg = deflicker_config(deflicker)
-    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_plate_grain = last_plate_tone = last_shadow_mask = last_deflicker = last_deflicker_align = last_deflicker_local = last_detail_match = last_grain_shape = None
+    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_plate_grain = last_plate_tone = last_shadow_mask = last_deflicker = last_deflicker_align = last_deflicker_local = last_detail_match = last_grain_shape = last_overlay_mask = None
     dcfg = detail_match_config(detail_match)
     ncfg = grain_shape_config(grain_shape)
     if ncfg is not None and gcfg is None:
@@ -453,6 +478,7 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     if ecfg is not None and pcfg is None:
         raise ValueError("plate_tone= (clean-plate exposure matching) needs plate_fill= (clean-plate fill)")
     hcfg = shadow_mask_config(shadow_mask)
+    ocfg = overlay_mask_config(overlay_mask)
     facfg = deflicker_align_config(deflicker_align)
     if facfg is not None and fcfg is None:
         raise ValueError("deflicker_align= (aligned inpaint deflicker) needs deflicker= (inpaint deflicker)")
@@ -462,7 +488,7 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     bcfg = seam_blend_config(seam_blend, feather_px if keep_unmasked_original else None)
     if compat_reference_early_return:
         on = dict(roi=rcfg, spans=scfg, mask_clean=ccfg, tone_match=tcfg, grain_match=gcfg, seam_blend=bcfg, plate_fill=pcfg, plate_align=acfg,
-                  plate_grain=lcfg, plate_tone=ecfg, shadow_mask=hcfg, deflicker=fcfg, deflicker_align=facfg, deflicker_local=flcfg, detail_match=dcfg, grain_shape=ncfg)
+                  plate_grain=lcfg, plate_tone=ecfg, shadow_mask=hcfg, deflicker=fcfg, deflicker_align=facfg, deflicker_local=flcfg, detail_match=dcfg, grain_shape=ncfg, overlay_mask=ocfg)
         for o in ALL_OPTIONS:
             if on[o.name] is not None:
                 raise ValueError(f"{o.name}= ({o.phrase}) cannot be combined with compat_reference_early_return=True")
@@ -477,6 +503,8 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         if scfg is not None and scfg.cuts == "auto":        # the detector has run, on the despeckled masks: the span plan takes its cuts
             import dataclasses
             scfg = dataclasses.replace(scfg, cuts=last_mask_clean.cuts)
+    if ocfg is not None:        # before the cut detector and both plate stages: none of them samples the graphic as background
+        dil_t, last_overlay_mask = infill.overlay_mask(frames_rgb, dil_t, ocfg)
     if hcfg is not None or pcfg is not None:
         found = None if scfg is None else infill.clip_cuts(frames_rgb, dil_t, scfg)
         if scfg is not None and scfg.cuts == "auto":        # the detector has run, once for both stages: the span plan takes its cuts
@@ -537,6 +565,24 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     if ncfg is not None:
         last_grain_shape = infill.grain_shape_report(seam["grain_shape_out"], plan, T)
     return out
+
+
+def find_overlays(frames_rgb, mask_frames=None, overlay_mask="on"):
+    """The overlay masking alone, for a preview in a GUI or a script: frames_rgb = the clip's frames [H,W,3] u8, mask_frames = masks of their
+    size ([H,W] or [H,W,ch], non-zero = masked: those pixels give no sample in their frame; they are taken as they are, not dilated) or None
+    (no mask), overlay_mask = "on" / a settings string / a videovanish_amd.overlaymask.OverlayMaskConfig.  -> (overlay [H,W] u8 {0, 255}: the
+    pixels run_infill_on_frames(..., overlay_mask=...) would add to every frame's mask; the infill.OverlayMaskReport with the verdict and
+    every box).  Loads no model and changes no module state; "off" is a ValueError."""
+    ocfg = overlaymask.as_config(overlay_mask)
+    if ocfg is None:
+        raise ValueError("find_overlays: overlay_mask= must name a setting ('on', 'mag=8,...' or an OverlayMaskConfig), not switch the stage off")
+    H, W = frames_rgb[0].shape[:2]
+    if mask_frames is None:
+        dil = np.zeros((len(frames_rgb), H, W), np.uint8)
+    else:
+        dil = np.stack([((mm != 0).any(axis=2) if mm.ndim == 3 else mm != 0) for mm in mask_frames]).astype(np.uint8) * 255
+    _, report = infill.overlay_mask(frames_rgb, torch.from_numpy(dil).to(get_device()), ocfg)
+    return report.overlay, report
 
 
 def _load_model(dev, ckpt):
@@ -606,7 +652,8 @@ def main():
     tools = _frame_io()
     ap = argparse.ArgumentParser(description="Remove masked objects from a video (DiffuEraser hot path on MI355X).")
     ap.add_argument("--color_video", required=True, type=str, help="Input color video path.")
-    ap.add_argument("--mask_video", required=True, type=str, help="Input mask video path.")
+    ap.add_argument("--mask_video", required=False, type=str, help="Input mask video path (required unless --overlay-mask is given: then no "
+                                                                   "mask video means all-zero masks).")
     ap.add_argument("--prior_video", required=False, type=str, help="Input prior video path.")
     ap.add_argument("--start_frame", type=int, default=0, help="Index of first frame to process (default: 0).")
     ap.add_argument("--max_frames", type=int, default=-1, help="Max number of frames to process after start_frame.")
@@ -666,6 +713,12 @@ def main():
                          "pixels at `lo` .. `hi` percent of the shot's clean background (at least `drop` levels darker, the three channels within "
                          "`chroma` points of each other) that hang on to the mask within `reach` steps join it, grown by `grow`; parts under "
                          "`min_area` pixels are dropped.  Changes masks only.  Prints one line with what it added.")
+    ap.add_argument("--overlay-mask", type=_setting_arg("overlay_mask"), default=None, metavar=_OPTION["overlay_mask"].metavar,
+                    help="Overlay masking before the shadow masking: find the screen-fixed graphics of the clip (a station logo, a channel bug) from "
+                         "the edges that stand still while the picture under them moves (mean gradient at least `mag`, `coh` percent of it in one "
+                         "direction), close them, fill what they enclose and add the parts of `min_area` pixels to `max_area` percent of the frame, "
+                         "grown by `grow`, to every frame's mask.  Needs a moving background; --mask_video becomes optional.  Changes masks only.  "
+                         "Prints one line with what it found.")
     ap.add_argument("--deflicker", type=_setting_arg("deflicker"), default=None, metavar=_OPTION["deflicker"].metavar,
                     help="Inpaint deflicker before the seam stages: every pixel of the model's output becomes the mean of those of its neighbours at "
                          "most `radius` frames away (on: 2) that lie within `tol` levels of it (on: 12), so the patch stops shimmering; what changes by "
@@ -682,12 +735,17 @@ def main():
     ap.add_argument("--cuts", type=span_plan.parse_cuts, default=None, metavar="120,431",
                     help="Frame indices (relative to --start_frame) where a new shot begins: used instead of the detector.")
     args = ap.parse_args()
+    if args.mask_video is None and args.overlay_mask is None:
+        ap.error("the following arguments are required: --mask_video (or --overlay-mask, which finds a mask where none was painted)")
 
     assert os.path.isfile(args.color_video), "input video missing"
     out_video = args.out or (args.color_video + "_vanished.mkv")
     frames, fps = tools.load_video_frames_from_path(args.color_video, args.start_frame, args.max_frames)
     H0, W0 = frames[0].shape[:2]
-    mask_frames, mask_fps = tools.load_video_frames_from_path(args.mask_video, args.start_frame, args.max_frames)
+    if args.mask_video is None:
+        mask_frames = [np.zeros((H0, W0), np.uint8) for _ in frames]
+    else:
+        mask_frames, mask_fps = tools.load_video_frames_from_path(args.mask_video, args.start_frame, args.max_frames)
     Hm, Wm = mask_frames[0].shape[:2]
     prior_frames = None
     if args.prior_video is not None:      # the reference's test is inverted (:142); a supplied prior is used here
@@ -750,6 +808,11 @@ def main():
         r = last_shadow_mask
         print(f"shadow mask: {int(r.added.sum())} px added in {int((r.added > 0).sum())} of {r.added.size} frames from {int(r.candidates.sum())} candidate px, "
               f"{sum(r.skipped)} of {len(r.segments)} segments skipped")
+    if args.overlay_mask is not None and last_overlay_mask is not None:
+        r = last_overlay_mask
+        boxes = ", ".join(f"{x1 - x0} x {y1 - y0} at ({x0}, {y0}), {area} px" for x0, y0, x1, y1, area in r.boxes.tolist()) or "no box"
+        print(f"overlay mask: {r.verdict}, {r.found} overlays ({boxes}), {int(r.overlay.astype(bool).sum())} px in the overlay, "
+              f"{int(r.added.min())} .. {int(r.added.max())} px added per frame, {r.edges} of {r.strong} strong px persistent")
     if args.deflicker is not None and last_deflicker is not None:
         r = last_deflicker
         touched = (r.changed > 0).any(axis=0)

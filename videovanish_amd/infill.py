@@ -1,19 +1,19 @@
-"""The orchestration of one diffuerase.run_infill_on_frames call after the dilation: the mask clean-up (clean_masks), the shadow masking
-(shadow_mask), the clean-plate fill (plate_fill), the temporal plan (span_plan, run_spans), and for each clip the windows (region_plans, run_clip), ONE crop -> prior -> model
+"""The orchestration of one diffuerase.run_infill_on_frames call after the dilation: the mask clean-up (clean_masks), the overlay masking
+(overlay_mask), the shadow masking (shadow_mask), the clean-plate fill (plate_fill), the temporal plan (span_plan, run_spans), and for each clip the windows (region_plans, run_clip), ONE crop -> prior -> model
 sequence (run_windows) and ONE closing step (finish).  The full frame is no window, roi= "static" / "follow" one, the "-regions" spellings
 several.  The closing step is one loop over the windows; in it the opt-in seam stages run on each window's pixels before they are pasted: the
 deflicker along time (with its alignment along a translation tracked per clip call and along block-matched vectors), the tone fit to the ring round the mask, the grain the
 ring's originals have and the model's pixels lack, the membrane that carries the ring's difference original - model into the hole.  Each stage
 reports per clip call; tone_report, grain_report, seam_blend_report, deflicker_report, deflicker_align_report, deflicker_local_report and detail_report assemble a call's
 report from them.  The stages (weights, prior, model) come from the caller as a Stages record; nothing here is module state.  Rules and reasons: DESIGN.md
-§10, §11, §12, §13, §14, §15, §16, §17, §18, §19, §21, §23, §24, §26."""
+§10, §11, §12, §13, §14, §15, §16, §17, §18, §19, §21, §23, §24, §26, §27."""
 import dataclasses
 from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
 
-from . import align_hip, blend_hip, deflicker, deflickeralign, deflickerlocal, detailmatch, detailmatch_bind, flickalign_hip, flicker_hip, flicklocal_bind, grain_hip, grainmatch, grainshape, grainshape_bind, hip, mask_hip, plate_hip, platealign, platefill, plategrain_hip, platetone, platetone_bind, seamblend, shadow_hip, shadowmask, spans_hip, tone_hip, tonematch
+from . import align_hip, blend_hip, deflicker, deflickeralign, deflickerlocal, detailmatch, detailmatch_bind, flickalign_hip, flicker_hip, flicklocal_bind, grain_hip, grainmatch, grainshape, grainshape_bind, hip, mask_hip, overlaymask, overlaymask_bind, plate_hip, platealign, platefill, plategrain_hip, platetone, platetone_bind, seamblend, shadow_hip, shadowmask, spans_hip, tone_hip, tonematch
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -70,6 +70,62 @@ def clean_masks(m, dil_t, ccfg, cuts=None):
         dil_t = out
         counts[:, 2:] = c.cpu().numpy()
     return dil_t, MaskCleanReport(*(counts[:, k].copy() for k in range(4)), cuts)
+
+
+# ---- overlays: the screen-fixed graphics nobody painted a mask for ------------------------------------------------------------------------------
+class OverlayMaskReport(NamedTuple):
+    """What overlay_mask found: the verdict ("none": no strong pixel or nothing kept; "static": the scene itself stands still, nothing added;
+    "found"), rule 2's two counts, the kept components as boxes [K,5] int32 = (x0, y0, x1, y1, area) in label order (at most 256 of `found`,
+    the true count; x1, y1 exclusive), the pixels added to the mask per frame (int64 [T]) and the overlay O [H,W] u8 {0, 255} on the host."""
+    verdict: str
+    strong: int
+    edges: int
+    boxes: np.ndarray
+    found: int
+    added: np.ndarray
+    overlay: np.ndarray
+
+
+def overlay_mask(frames_rgb, dil_t, ocfg):
+    """The overlay masking (overlaymask.py; rules: include/overlaymask.h): frames_rgb = the T host frames [H,W,3] u8, dil_t = the
+    masks [T,H,W] u8 on the device, ocfg = an OverlayMaskConfig.  One call on the whole clip: the frames cross to the device in batches of at
+    most max_bytes (at least a frame) and add into one set of sums; the closing and the fringe are hip.mask_collapse_dilate, the components
+    mask_hip.label_components.  Returns (dil', OverlayMaskReport): dil' is dil_t itself for the verdicts "none" and "static", and neither the
+    frames nor dil_t is ever written.  Depends on nothing but its arguments: every rank gets the same masks."""
+    T, H, W = dil_t.shape
+    if T > overlaymask.MAX_T:
+        raise ValueError(f"overlay_mask: a clip call of at most {overlaymask.MAX_T} frames is supported, not {T}")
+    dev = dil_t.device
+    B = overlaymask_bind
+    acc = B.new_acc(H, W, dev)
+    step = ocfg.batch_frames(H, W)
+    for s in range(0, T, step):
+        f = torch.from_numpy(np.stack(frames_rgb[s:s + step])).to(dev)
+        B.accumulate(f, dil_t[s:s + step], acc)
+    edge, counts = B.classify(acc, ocfg.min_samples, ocfg.mag, ocfg.coh)
+    strong, edges = (int(c) for c in counts.cpu().numpy())
+
+    def nothing(verdict):
+        return dil_t, OverlayMaskReport(verdict, strong, edges, np.zeros((0, 5), np.int32), 0, np.zeros(T, np.int64), np.zeros((H, W), np.uint8))
+
+    if strong == 0:
+        return nothing("none")
+    if 100 * edges > ocfg.max_share * strong:
+        return nothing("static")
+    closed = hip.mask_collapse_dilate(edge[None, ..., None], ocfg.close) if ocfg.close else edge[None]                 # rule 4, [1,H,W]
+    lab = mask_hip.label_components((closed == 0).to(torch.uint8))[0]                                                 # rule 5: the components of ~C
+    holes, _, _ = B.select(lab, B.component_stats(lab), 0, ocfg.max_hole, True)
+    filled, _ = B.merge(closed, holes)
+    lab = mask_hip.label_components(filled)[0]                                                                        # rule 6
+    kept, boxes, nboxes = B.select(lab, B.component_stats(lab), ocfg.min_area, ocfg.max_area_px(H, W), not ocfg.border)
+    found = int(nboxes.item())
+    if found == 0:
+        return nothing("none")
+    o = hip.mask_collapse_dilate(kept[None, ..., None], ocfg.grow)[0] if ocfg.grow else kept                          # rule 7
+    dil, added = B.merge(dil_t, o)
+    b = boxes[:min(found, overlaymask.MAX_BOXES)].cpu().numpy()
+    b = b[np.argsort(b[:, 0], kind="stable")]
+    return dil, OverlayMaskReport("found", strong, edges, np.ascontiguousarray(b[:, [2, 3, 4, 5, 1]]), found, added.cpu().numpy(), o.cpu().numpy())
 
 
 # ---- shadows: what the object casts beside the mask --------------------------------------------------------------------------------------------
