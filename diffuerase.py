@@ -18,6 +18,8 @@ configure(detail_match=...) and $VV_DETAIL_MATCH), plate_fill (clean-plate fill:
 filled from the nearest such frame and leave the mask before anything plans or runs the model: videovanish_amd/platefill.py; also
 configure(plate_fill=...) and $VV_PLATE_FILL), plate_align (clean-plate alignment: with plate_fill, one integer translation per frame is
 tracked first, so that the fill follows a panning camera: videovanish_amd/platealign.py; also configure(plate_align=...) and $VV_PLATE_ALIGN),
+plate_warp (clean-plate warp: with plate_fill and plate_align, one affine map per frame is fitted to block-matched vectors, so that the fill
+follows zoom and roll too: videovanish_amd/platewarp.py; also configure(plate_warp=...) and $VV_PLATE_WARP),
 plate_grain (clean-plate grain: with plate_fill, a filled pixel takes its bytes from a few usable frames in turn, not from the nearest alone, so
 that the grain inside the fill moves: videovanish_amd/plategrain.py; also configure(plate_grain=...) and $VV_PLATE_GRAIN),
 plate_tone (clean-plate exposure matching: with plate_fill, every frame of a segment is mapped to the segment's common exposure before the fill
@@ -49,7 +51,7 @@ import torch
 
 from videovanish_amd import hip, infill
 from videovanish_amd import deflicker as deflicker_settings
-from videovanish_amd import deflickeralign, deflickerlocal, detailmatch, grainmatch, grainshape, maskclean, overlaymask, platealign, platefill, plategrain, platetone, seamblend, shadowmask, tonematch
+from videovanish_amd import deflickeralign, deflickerlocal, detailmatch, grainmatch, grainshape, maskclean, overlaymask, platealign, platefill, plategrain, platetone, platewarp, seamblend, shadowmask, tonematch
 from videovanish_amd import roi as roi_plan
 from videovanish_amd import spans as span_plan
 from videovanish_amd.config import RunConfig
@@ -82,6 +84,7 @@ last_detail_match = None     # the infill.DetailMatchReport of the last run_infi
 last_grain_shape = None      # the infill.GrainShapeReport of the last run_infill_on_frames call; None when the shape was not asked for
 last_deflicker_local = None  # the infill.DeflickerLocalReport of the last run_infill_on_frames call; None when the search was not asked for
 last_overlay_mask = None     # the infill.OverlayMaskReport of the last run_infill_on_frames call; None when the stage did not run
+last_plate_warp = None       # the infill.PlateWarpReport of the last run_infill_on_frames call; None when the warp was not asked for
 
 
 class Option(NamedTuple):
@@ -118,6 +121,7 @@ MORE_OPTIONS = (
     Option("deflicker_local", deflickerlocal, "VV_DEFLICKER_LOCAL", "block-matched inpaint deflicker", "on|block=8,search=4,lam=32"),
     Option("overlay_mask", overlaymask, "VV_OVERLAY_MASK", "overlay masking",
            "on|min_samples=12,mag=8,coh=80,max_share=25,close=2,max_hole=4096,min_area=64,max_area=10,border=0,grow=3"),
+    Option("plate_warp", platewarp, "VV_PLATE_WARP", "clean-plate warp", "on|block=16,search=8,min_texture=2,min_blocks=12,trim=10,rounds=3,max_linear=50"),
 )
 ALL_OPTIONS = OPTIONS + MORE_OPTIONS
 _OPTION = {o.name: o for o in ALL_OPTIONS}
@@ -125,7 +129,7 @@ _configured = {}        # configure(<option>=...): the value for calls that do n
 
 
 def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weights=None, reference_defaults=False, roi=None, spans=None,
-              mask_clean=None, tone_match=None, grain_match=None, grain_shape=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, deflicker_local=None, overlay_mask=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
+              mask_clean=None, tone_match=None, grain_match=None, grain_shape=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, deflicker_local=None, overlay_mask=None, shadow_mask=None, plate_tone=None, plate_warp=None, plate_grain=None, plate_align=None, plate_fill=None):
     """Select architecture / chunking / dtype for subsequently constructed models (tests use small configs).
     dist = (rank, world) with torch.distributed initialised, one process per GPU (torchrun); gather = "all": every rank returns
     every frame; "rank0": only rank 0 does (the other ranks get None for frames they do not own and should not write a file).
@@ -171,7 +175,9 @@ def configure(run: RunConfig = None, dist=None, gather="all", prior=None, weight
     deflicker_align = None / "on" / "levels=4,radius=4,min_overlap=25,max_residual=12" (any subset) / a platealign.PlateAlignConfig: aligned
     inpaint deflicker for calls that do not pass deflicker_align=.
     deflicker_local = None / "on" / "block=8,search=4,lam=32" (any subset) / a deflickerlocal.DeflickerLocalConfig: block-matched inpaint
-    deflicker for calls that do not pass deflicker_local=."""
+    deflicker for calls that do not pass deflicker_local=.
+    plate_warp = None / "on" / "block=16,search=8,min_texture=2,min_blocks=12,trim=10,rounds=3,max_linear=50" (any subset) / a
+    platewarp.PlateWarpConfig: clean-plate warp for calls that do not pass plate_warp=."""
     global _run_config, _dist, _gather, last_ckpt, _prior_stages, propainter, _weights, _loaded
     given = locals()
     for o in reversed(ALL_OPTIONS):         # validated now, kept as given: configure(roi="off") means the full frame whatever $VV_ROI says
@@ -288,6 +294,13 @@ def plate_align_config(plate_align=None):
     return _setting("plate_align", plate_align)
 
 
+def plate_warp_config(plate_warp=None):
+    """The clean-plate warp setting a call runs with: its own plate_warp= argument, else configure(plate_warp=...), else $VV_PLATE_WARP (on | off |
+    block=N,search=N,min_texture=N,min_blocks=N,trim=N,rounds=N,max_linear=N).  None = translations only.  plate_warp="off" (or False) asks
+    for that whatever configure() or the environment say."""
+    return _setting("plate_warp", plate_warp)
+
+
 def plate_grain_config(plate_grain=None):
     """The clean-plate grain setting a call runs with: its own plate_grain= argument, else configure(plate_grain=...), else $VV_PLATE_GRAIN
     (on | off | depth=N,reach=N).  None = every filled pixel takes the nearest usable frame.  plate_grain="off" (or False) asks for that whatever
@@ -339,7 +352,7 @@ def deflicker_local_config(deflicker_local=None):
 def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-Step",
                          propainer_frames=None, max_img_size=960, keep_unmasked_original=True, feather_px=3, prog=None,
                          *, num_inference_steps=None, scheduler=None, compat_reference_early_return=False, roi=None, spans=None, cuts=None,
-                         mask_clean=None, tone_match=None, grain_match=None, grain_shape=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, deflicker_local=None, overlay_mask=None, shadow_mask=None, plate_tone=None, plate_grain=None, plate_align=None, plate_fill=None):
+                         mask_clean=None, tone_match=None, grain_match=None, grain_shape=None, seam_blend=None, detail_match=None, deflicker=None, deflicker_align=None, deflicker_local=None, overlay_mask=None, shadow_mask=None, plate_tone=None, plate_warp=None, plate_grain=None, plate_align=None, plate_fill=None):
     """roi (mask-region inference, opt-in): "static" / "follow" / a videovanish_amd.roi.RoiConfig crops every frame to a window around the dilated
     masks, runs the prior and the model on that smaller clip and pastes the result back into the original frames: pixels outside the window are
     the original bytes.  Falls back to the full frame when no frame has a mask pixel or the window would be the whole frame.
@@ -402,6 +415,12 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     over a panning shot, is filled from the frames that show its background at another place.  A frame the tracker loses gives no sample
     and keeps its mask; a locked-off clip gives the bytes of the call without it.  What it found is kept in last_plate_align.  Without an
     effective plate_fill it is a ValueError.
+    plate_warp (clean-plate warp, opt-in, needs plate_fill and plate_align): "on" / "block=16,search=8,min_texture=2,min_blocks=12,trim=10,
+    rounds=3,max_linear=50" / a videovanish_amd.platewarp.PlateWarpConfig refines the tracked translations to one affine map per frame (whole
+    blocks matched against the held key, an exact trimmed least-squares fit on the host; rules: include/platewarp.h) and builds and reads the
+    canvas through these maps with nearest-neighbour gathers, so that the fill follows zoom and roll; every filled byte is still a byte of
+    the clip.  A frame whose fit fails keeps its translation; a locked-off clip and a pure pan give the bytes of the call without it.  What
+    it fitted is kept in last_plate_warp.  Without an effective plate_fill and plate_align it is a ValueError.
     plate_grain (clean-plate grain, opt-in, needs plate_fill): "on" / "depth=4,reach=8" / a videovanish_amd.plategrain.PlateGrainConfig makes
     every filled pixel take its bytes from up to `depth` usable frames in turn (the nearest one and the next ones on its side, none more than
     `reach` frames from it; rule: include/vvplategrain.h), so that the grain inside the fill moves as it does around it.  Every filled byte is
@@ -455,14 +474,14 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     the search starts from the tracked translation.  The gate is unchanged: no byte moves more than the deflicker's `tol`.  search=0 and a
     deflicker of radius 0 give the bytes of the call without it.  What the search found is kept in last_deflicker_local, what the gate then
     accepted in last_deflicker.  Without an effective deflicker it is a ValueError."""
-    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_plate_grain, last_plate_tone, last_shadow_mask, last_deflicker, last_deflicker_align, last_deflicker_local, last_detail_match, last_grain_shape, last_overlay_mask
+    global last_mask_clean, last_tone_match, last_grain_match, last_seam_blend, last_plate_fill, last_plate_align, last_plate_grain, last_plate_tone, last_shadow_mask, last_deflicker, last_deflicker_align, last_deflicker_local, last_detail_match, last_grain_shape, last_overlay_mask, last_plate_warp
     rcfg = roi_config(roi)
     scfg = spans_config(spans, cuts)
     ccfg = mask_clean_config(mask_clean)
     tcfg = tone_match_config(tone_match)
     gcfg = grain_match_config(grain_match)
     fcfg = deflicker_config(deflicker)
-    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_plate_grain = last_plate_tone = last_shadow_mask = last_deflicker = last_deflicker_align = last_deflicker_local = last_detail_match = last_grain_shape = last_overlay_mask = None
+    last_mask_clean = last_tone_match = last_grain_match = last_seam_blend = last_plate_fill = last_plate_align = last_plate_grain = last_plate_tone = last_shadow_mask = last_deflicker = last_deflicker_align = last_deflicker_local = last_detail_match = last_grain_shape = last_overlay_mask = last_plate_warp = None
     dcfg = detail_match_config(detail_match)
     ncfg = grain_shape_config(grain_shape)
     if ncfg is not None and gcfg is None:
@@ -471,6 +490,9 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     acfg = plate_align_config(plate_align)
     if acfg is not None and pcfg is None:
         raise ValueError("plate_align= (clean-plate alignment) needs plate_fill= (clean-plate fill)")
+    wcfg = plate_warp_config(plate_warp)
+    if wcfg is not None and (pcfg is None or acfg is None):
+        raise ValueError("plate_warp= (clean-plate warp) needs plate_fill= (clean-plate fill) and plate_align= (clean-plate alignment)")
     lcfg = plate_grain_config(plate_grain)
     if lcfg is not None and pcfg is None:
         raise ValueError("plate_grain= (clean-plate grain) needs plate_fill= (clean-plate fill)")
@@ -488,7 +510,7 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     bcfg = seam_blend_config(seam_blend, feather_px if keep_unmasked_original else None)
     if compat_reference_early_return:
         on = dict(roi=rcfg, spans=scfg, mask_clean=ccfg, tone_match=tcfg, grain_match=gcfg, seam_blend=bcfg, plate_fill=pcfg, plate_align=acfg,
-                  plate_grain=lcfg, plate_tone=ecfg, shadow_mask=hcfg, deflicker=fcfg, deflicker_align=facfg, deflicker_local=flcfg, detail_match=dcfg, grain_shape=ncfg, overlay_mask=ocfg)
+                  plate_grain=lcfg, plate_tone=ecfg, shadow_mask=hcfg, deflicker=fcfg, deflicker_align=facfg, deflicker_local=flcfg, detail_match=dcfg, grain_shape=ncfg, overlay_mask=ocfg, plate_warp=wcfg)
         for o in ALL_OPTIONS:
             if on[o.name] is not None:
                 raise ValueError(f"{o.name}= ({o.phrase}) cannot be combined with compat_reference_early_return=True")
@@ -513,9 +535,11 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
     if hcfg is not None:
         dil_t, last_shadow_mask = infill.shadow_mask(frames_rgb, dil_t, hcfg, found)
     if pcfg is not None:
-        more, found_align, found_grain, found_tone = {}, [], [], []
+        more, found_align, found_grain, found_tone, found_warp = {}, [], [], [], []
         if acfg is not None:
             more.update(acfg=acfg, align_out=found_align)
+        if wcfg is not None:
+            more.update(wcfg=wcfg, warp_out=found_warp)
         if lcfg is not None:
             more.update(gcfg=lcfg, grain_out=found_grain)
         if ecfg is not None:
@@ -523,6 +547,8 @@ def run_infill_on_frames(frames_rgb, mask_frames, mask_dilation_iter=8, ckpt="2-
         frames_rgb, dil_t, last_plate_fill = infill.plate_fill(frames_rgb, dil_t, pcfg, found, **more)      # downstream these are the originals
         if acfg is not None:
             last_plate_align = found_align[0]
+        if wcfg is not None:
+            last_plate_warp = found_warp[0]
         if lcfg is not None:
             last_plate_grain = found_grain[0]
         if ecfg is not None:
@@ -699,6 +725,11 @@ def main():
                     help="With --plate-fill: track one integer translation per frame first (a coarse-to-fine search over `levels` pyramid levels, "
                          "+-`radius` at the coarsest; a frame whose best match differs by more than `max_residual` levels on average is left out) "
                          "and fill on the canvas in which the background stands still.  For slow pans and tilts.  Prints one line with what it tracked.")
+    ap.add_argument("--plate-warp", type=_setting_arg("plate_warp"), default=None, metavar=_OPTION["plate_warp"].metavar,
+                    help="With --plate-fill and --plate-align: match `block`-pixel blocks of every tracked frame against its key frame +-`search` px round "
+                         "the tracked translation, fit one affine map per frame to the blocks' vectors (exact least squares, blocks further than "
+                         "`trim` tenths of a pixel from the fit dropped, at least `min_blocks` kept, linear coefficients up to `max_linear` thousandths) "
+                         "and fill on the canvas built through these maps.  For handheld and gimbal shots: zoom and roll.  Prints one line with what it fitted.")
     ap.add_argument("--plate-grain", type=_setting_arg("plate_grain"), default=None, metavar=_OPTION["plate_grain"].metavar,
                     help="With --plate-fill: a filled pixel takes its bytes from up to `depth` usable frames in turn (the nearest and the next ones on "
                          "its side, at most `reach` frames from it), not from the nearest alone, so that the grain inside the fill moves as it does "
@@ -795,6 +826,13 @@ def main():
         n = len(r.segments)
         print(f"plate align: {int(ok.sum())} of {ok.size} frames tracked, pan extent {max(span[:n])} x {max(span[n:])} px, "
               f"{sum(p == 'canvas' for p in r.path)} of {n} segments filled on a canvas")
+    if args.plate_warp is not None and last_plate_warp is not None:
+        r = last_plate_warp
+        failed, kept = np.concatenate(r.failed), np.concatenate(r.kept)
+        lin = np.concatenate([np.abs(m[:, [1, 2, 4, 5]] - np.array([1.0, 0.0, 0.0, 1.0])).max(axis=1) for m in r.maps]) if len(r.maps) else np.zeros(0)
+        print(f"plate warp: {int((kept > 0).sum())} of {kept.size} frames fitted, {int(failed.sum())} fits failed, largest linear coefficient "
+              f"{float(np.nanmax(lin, initial=0.0)):.4f}, largest rms {float(np.concatenate(r.rms).max(initial=0.0)):.2f} px, "
+              f"{sum(p == 'warp' for p in r.path)} of {len(r.segments)} segments filled on a warped canvas")
     if args.plate_grain is not None and last_plate_grain is not None:
         r = last_plate_grain
         filled, rotated = int(r.filled.sum()), int(r.rotated.sum())

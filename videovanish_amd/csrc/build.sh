@@ -24,7 +24,7 @@ pids=(); objs=()
 compile() {   # compile <src> <obj> [extra flags]
   local src=$1 obj=$OBJ/$2.o stale=; shift 2
   objs+=($obj)
-  for dep in $src.hip *.h ../../include/vvhip.h ../../include/vvspans.h ../../include/vvmask.h ../../include/vvtone.h ../../include/vvgrain.h ../../include/vvblend.h ../../include/vvplate.h ../../include/vvplategrain.h ../../include/vvalign.h ../../include/vvflicker.h ../../include/vvflickalign.h ../../include/vvshadow.h ../../include/platetone.h ../../include/detailmatch.h ../../include/grainshape.h ../../include/flicklocal.h ../../include/overlaymask.h $HERE/build.sh; do
+  for dep in $src.hip *.h ../../include/vvhip.h ../../include/vvspans.h ../../include/vvmask.h ../../include/vvtone.h ../../include/vvgrain.h ../../include/vvblend.h ../../include/vvplate.h ../../include/vvplategrain.h ../../include/vvalign.h ../../include/vvflicker.h ../../include/vvflickalign.h ../../include/vvshadow.h ../../include/platetone.h ../../include/detailmatch.h ../../include/grainshape.h ../../include/flicklocal.h ../../include/overlaymask.h ../../include/platewarp.h $HERE/build.sh; do
     if [ ! -f $obj ] || [ $dep -nt $obj ]; then stale=1; fi
   done
   if [ -n "$stale" ]; then
@@ -37,7 +37,7 @@ for f in vv_gemm vv_gemm256; do
   compile $f ${f}_bf16 -DVV_DT_ONLY=0
   compile $f ${f}_f16 -DVV_DT_ONLY=1
 done
-for f in vv_api vv_motion vv_chain vv_norm vv_elem vv_image vv_roi vv_spans vv_mask vv_tone vv_grain vv_grainshape vv_blend vv_detail vv_plate vv_platetone vv_shadow vv_overlay vv_align vv_flicker vv_flicklocal vv_flow vv_deform vv_sam2; do
+for f in vv_api vv_motion vv_chain vv_norm vv_elem vv_image vv_roi vv_spans vv_mask vv_tone vv_grain vv_grainshape vv_blend vv_detail vv_plate vv_platetone vv_platewarp vv_shadow vv_overlay vv_align vv_flicker vv_flicklocal vv_flow vv_deform vv_sam2; do
   compile $f $f
 done
 # attention, small head dims: MFMA results feed VALU code (softmax) every tile -> keep accumulators in arch VGPRs

@@ -23,6 +23,7 @@
 namespace {
 
 using vvwave::wave_sum;
+using vvwave::wave_min64;
 typedef unsigned long long u64;
 typedef long long i64;
 constexpr int FB = 256;                     // threads per block
@@ -35,16 +36,6 @@ static_assert(VVK_MAX_RADIUS == 4 && 2 * VVK_MAX_RADIUS + 1 <= 9, "n <= 9: the r
 static_assert(16ll * 16 * 3 * 255 + 2ll * MAXS * VVK_MAX_LAM < (1ll << 31), "a cost fits 31 bits");
 static_assert(2 * MAXS * MAXS < 256 && 2 * MAXS + 1 < 256, "the key's fields");
 static_assert(64 * 255 < (1 << 16) && 64 * 9 < (1 << 16), "a wave's sums of one pixel per lane fit the 16-bit halves");
-
-__device__ __forceinline__ u64 wave_min64(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
-        const u64 other = ((u64)hi << 32) | lo;
-        v = other < v ? other : v;
-    }
-    return v;
-}
 
 // grid (T * K * nby * xchunks): blockIdx.x = ((t * K + k) * nby + by) * xchunks + xc.  Reads of win are bounds-checked against the window of
 // the frame they come from (staging); the writes are the workgroup's own records of mv and the atomics into stats[t][k].

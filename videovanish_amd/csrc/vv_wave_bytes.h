@@ -24,6 +24,15 @@ __device__ __forceinline__ u64 wave_sum64(u64 v) {
     }
     return v;
 }
+__device__ __forceinline__ u64 wave_min64(u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
+        const u64 other = ((u64)hi << 32) | lo;
+        v = other < v ? other : v;
+    }
+    return v;
+}
 __device__ __forceinline__ unsigned wave_max(unsigned v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor(v, o, 64));

@@ -13,7 +13,7 @@ from typing import Callable, NamedTuple
 import numpy as np
 import torch
 
-from . import align_hip, blend_hip, deflicker, deflickeralign, deflickerlocal, detailmatch, detailmatch_bind, flickalign_hip, flicker_hip, flicklocal_bind, grain_hip, grainmatch, grainshape, grainshape_bind, hip, mask_hip, overlaymask, overlaymask_bind, plate_hip, platealign, platefill, plategrain_hip, platetone, platetone_bind, seamblend, shadow_hip, shadowmask, spans_hip, tone_hip, tonematch
+from . import align_hip, blend_hip, deflicker, deflickeralign, deflickerlocal, detailmatch, detailmatch_bind, flickalign_hip, flicker_hip, flicklocal_bind, grain_hip, grainmatch, grainshape, grainshape_bind, hip, mask_hip, overlaymask, overlaymask_bind, plate_hip, platealign, platefill, plategrain_hip, platetone, platetone_bind, platewarp, platewarp_bind, seamblend, shadow_hip, shadowmask, spans_hip, tone_hip, tonematch
 from . import roi as roi_plan
 from . import spans as span_planner
 
@@ -245,9 +245,28 @@ class PlateAlignReport(NamedTuple):
     segments: tuple
 
 
-def _track_segment(frames_rgb, d_seg, acfg, max_bytes):
+class PlateWarpReport(NamedTuple):
+    """What plate_fill(wcfg=) fitted, per segment of `segments` (a tuple each): maps [T,6] float64 = every frame's map to the canvas (ax, bx, cx,
+    ay, by, cy: x' = ax + bx x + cx y; the exact rationals, rounded for reading only; NaN for an untracked frame), usable / used / kept [T] int64
+    = the blocks vvw_search could match, those it matched within plate_align's max_residual, and those the trimmed fit kept; rms [T] = the root
+    mean square distance of the kept blocks' vectors from the fit, in pixels; failed [T] bool = the frames whose fit failed (they keep
+    plate_align's translation); the canvas box or None; and the path that ran: "warp" (filled on the warped canvas), "translation" (every map is
+    plate_align's integer translation: its canvas path as it is), "fallback" (the warped canvas exceeds max_bytes: plate_align's path),
+    "none", "empty", "untracked", "static" (plate_align's paths of those names: nothing was searched)."""
+    maps: tuple
+    usable: tuple
+    used: tuple
+    kept: tuple
+    rms: tuple
+    failed: tuple
+    box: tuple
+    path: tuple
+    segments: tuple
+
+
+def _track_segment(frames_rgb, d_seg, acfg, max_bytes, keep=None):
     """Pyramid in frame batches of at most max_bytes of image (only the luma planes stay resident), vva_track, and the ONE synchronisation:
-    -> (track on the device, track on the host)."""
+    -> (track on the device, track on the host).  keep = a list that receives the packed pyramid (plate_warp searches its level 0)."""
     T, H, W = d_seg.shape
     L = platealign.coarsest_level(H, W, acfg.levels)
     pyr = torch.empty((T, align_hip.frame_bytes(H, W, L)), dtype=torch.uint8, device=d_seg.device)
@@ -256,12 +275,14 @@ def _track_segment(frames_rgb, d_seg, acfg, max_bytes):
         f = torch.from_numpy(np.stack(frames_rgb[b:b + B])).to(d_seg.device)
         align_hip.pyramid(f, d_seg[b:b + B], L, out=pyr[b:b + B])
     track_t = align_hip.track(pyr, H, W, L, acfg.radius, acfg.min_overlap, acfg.max_residual)
+    if keep is not None:
+        keep.append(pyr)
     return track_t, track_t.cpu().numpy()
 
 
-def _plan_alignment(frames_rgb, d_seg, boxes, pcfg, acfg):
+def _plan_alignment(frames_rgb, d_seg, boxes, pcfg, acfg, keep=None):
     """Steps 1 - 4 and 6 of DESIGN.md §17 for one segment -> (track on the device or None, track [T,8] on the host, the canvas box or None,
-    the path: see PlateAlignReport)."""
+    the path: see PlateAlignReport).  keep: _track_segment's."""
     T, H, W = d_seg.shape
     track = np.zeros((T, 8), np.int32)
     track[:, 3] = 1
@@ -269,7 +290,7 @@ def _plan_alignment(frames_rgb, d_seg, boxes, pcfg, acfg):
         return None, track, None, "empty"
     if not platealign.trackable(T, H, W):
         return None, track, None, "untracked"
-    track_t, track = _track_segment(frames_rgb, d_seg, acfg, pcfg.max_bytes)
+    track_t, track = _track_segment(frames_rgb, d_seg, acfg, pcfg.max_bytes) if keep is None else _track_segment(frames_rgb, d_seg, acfg, pcfg.max_bytes, keep)
     ok = track[:, 3] == 1
     if ok.all() and not track[:, :2].any():
         return track_t, track, None, "static"
@@ -390,7 +411,55 @@ def _fill_on_canvas(frames_rgb, d_seg, track_t, track, box, pcfg, gcfg=None):
     return new, align_hip.unplace_mask(d2, d_seg, track_t, box), c, steady
 
 
-def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None, gcfg=None, grain_out=None, tcfg=None, tone_out=None):
+def _plan_warp(pyr, d_seg, track_t, track, boxes, pcfg, acfg, wcfg):
+    """Steps 1 and 2 of DESIGN.md §28 for one tracked segment: vvw_search on the resident pyramid, the read-back of its records, the exact fit
+    and the tables on the host -> (the platewarp.Plan, the search's stats [T,4], the canvas box or None, the path "warp" / "translation" /
+    "fallback")."""
+    T, H, W = d_seg.shape
+    rec, stats = platewarp_bind.search(pyr, track_t, H, W, wcfg, acfg.max_residual)
+    plan = platewarp.plan_segment(track, rec.cpu().numpy(), wcfg, H, W, boxes)
+    stats = stats.cpu().numpy()
+    if plan.translation:
+        return plan, stats, None, "translation"
+    cbox = platewarp.canvas_box(boxes, plan.fwd, plan.tracked)
+    return plan, stats, cbox, "fallback" if cbox is None or platewarp.canvas_bytes(T, cbox) > pcfg.max_bytes else "warp"
+
+
+def _fill_on_warp(frames_rgb, d_seg, plan, cbox, pbox, pcfg, gcfg=None):
+    """Step 3 of DESIGN.md §28 for one segment: the frames cross in batches of at most max_bytes and vvw_place builds the canvas through the
+    inverse maps, the unchanged vvp_ kernels run on it, vvw_unplace brings the filled bytes back as a patch over pbox (the union box of the
+    frames' masks), and only the filled pixels go into copies of their frames -> ({frame index: new frame}, dil' [T,H,W] or None when nothing
+    was filled, counts [T,3] = (frame pixels filled, frame pixels left, rotated) on the host, steady)."""
+    T, H, W = d_seg.shape
+    dev = d_seg.device
+    y0, x0, y1, x1 = cbox
+    inv_t, fwd_t, flags = platewarp_bind.tables(plan.inv, dev), platewarp_bind.tables(plan.fwd, dev), platewarp_bind.flags(plan.tracked, dev)
+    f = torch.empty((T, y1 - y0, x1 - x0, 3), dtype=torch.uint8, device=dev)
+    d, invalid = torch.empty((T, y1 - y0, x1 - x0), dtype=torch.uint8, device=dev), torch.empty((T, y1 - y0, x1 - x0), dtype=torch.uint8, device=dev)
+    B = max(1, pcfg.max_bytes // (H * W * 3))
+    for b in range(0, T, B):
+        up = torch.from_numpy(np.stack(frames_rgb[b:b + B])).to(dev)
+        platewarp_bind.place(up, d_seg[b:b + B], inv_t[b:b + B], flags[b:b + B], cbox, out=(f[b:b + B], d[b:b + B], invalid[b:b + B]))
+    d2, c, steady = _fill_device(f, d, invalid, pcfg, gcfg)
+    patch, dil2 = platewarp_bind.unplace(f, d, d2, d_seg, fwd_t, flags, cbox, pbox)
+    went = (d_seg != 0) & (dil2 == 0)
+    counts = torch.stack([went.flatten(1).sum(1), (dil2 != 0).flatten(1).sum(1)], 1).cpu().numpy()
+    c = np.concatenate([counts, c[:, 2:3]], 1)
+    idx = np.nonzero(c[:, 0])[0]
+    new = {}
+    if not len(idx):
+        return new, None, c, steady
+    sel = torch.from_numpy(idx).to(dev)
+    py0, px0, py1, px1 = pbox
+    got, m = patch[sel].cpu().numpy(), went[sel][:, py0:py1, px0:px1].cpu().numpy()
+    for j, i in enumerate(idx):
+        fr = np.array(frames_rgb[i], copy=True)
+        fr[py0:py1, px0:px1][m[j]] = got[j][m[j]]                           # only the filled pixels; the slice is a view
+        new[int(i)] = fr
+    return new, dil2, c, steady
+
+
+def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None, wcfg=None, warp_out=None, gcfg=None, grain_out=None, tcfg=None, tone_out=None):
     """The clean-plate fill (platefill.py; rules: include/vvplate.h): frames_rgb = the T host frames [H,W,3] u8, dil_t = the masks
     [T,H,W] u8 on the device, pcfg = a PlateFillConfig, cuts = frame indices or None (one segment).  Per segment of spans.segments: the crop of
     the union box of its masks (platefill.crop_box) crosses to the device and is filled in place (_fill_device); only the crops of frames
@@ -412,7 +481,15 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None, gc
     on the normalised crop and maps every filled pixel back to its frame's exposure (_fill_matched); an unfilled pixel keeps its bytes.  A
     segment without enough support, or whose frames all fit the identity, takes the path above as it is; a segment on the canvas is not
     matched; one whose widened crop exceeds max_bytes or 2^24 pixels is flagged "skipped" and filled as without the option.  tone_out = a list
-    that receives the call's PlateToneReport."""
+    that receives the call's PlateToneReport.
+    wcfg = a platewarp.PlateWarpConfig (rules: include/platewarp.h), opt-in, needs acfg: a segment the tracker would fill on its
+    canvas is first searched block by block against the held keys (vvw_search on the pyramid the tracker built), one affine map per frame is
+    fitted exactly on the host (platewarp.plan_segment), and the canvas is built and read back through these maps with nearest-neighbour
+    gathers (_fill_on_warp), so that the fill follows zoom and roll; a frame whose fit fails keeps its translation.  When every map is the
+    tracker's translation the segment takes the tracker's canvas path unchanged ("translation"); a warped canvas over max_bytes does too
+    ("fallback").  warp_out = a list that receives the call's PlateWarpReport."""
+    if wcfg is not None and acfg is None:
+        raise ValueError("plate_fill: wcfg (plate_warp) needs acfg (plate_align)")
     T, H, W = dil_t.shape
     cuts = tuple(int(c) for c in (cuts or ()))
     segs = tuple(span_planner.segments(T, cuts))
@@ -421,16 +498,34 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None, gc
     filled, left, rotated = np.zeros(T, np.int64), np.zeros(T, np.int64), np.zeros(T, np.int64)
     steady, skipped = [], []
     arep = [[] for _ in range(6)]
+    wrep = [[] for _ in range(8)]
     tgain, toff, tident, tn, tpath = np.ones((T, 3)), np.zeros((T, 3)), np.ones(T, bool), [], []
     for s, e in segs:
         # the segment's plan: "crop" / "canvas" fill; "empty" (no mask pixel), "skipped" (the crop is too large), "none" (no tracked frame has a mask pixel) do not
         plan, d, at = "crop", dil_t[s:e], ()
         if acfg is not None:
-            track_t, track, cbox, path = _plan_alignment(frames_rgb[s:e], d, boxes[s:e], pcfg, acfg)
+            pyr = [] if wcfg is not None else None
+            track_t, track, cbox, path = _plan_alignment(frames_rgb[s:e], d, boxes[s:e], pcfg, acfg) if pyr is None else \
+                _plan_alignment(frames_rgb[s:e], d, boxes[s:e], pcfg, acfg, pyr)
             for k, v in enumerate((track[:, :2].copy(), track[:, 2].copy(), track[:, 3] == 1, _residual(track), cbox, path)):
                 arep[k].append(v)
             if path in ("none", "canvas"):
                 plan = path
+            if wcfg is not None:
+                n, wpath, wbox, wplan = e - s, path, None, None
+                nan, zero = np.full((n, 6), np.nan), np.zeros(n, np.int64)
+                w = [nan, zero, zero, zero, np.zeros(n), np.zeros(n, bool)]
+                if path == "canvas" and platewarp.searchable(n, H, W):
+                    wplan, stats, wbox, wpath = _plan_warp(pyr[0], d, track_t, track, boxes[s:e], pcfg, acfg, wcfg)
+                    fits = wplan.fits
+                    w = [np.array([[float(v) for row in m for v in row] if m is not None else [np.nan] * 6 for m in wplan.maps]).reshape(n, 6),
+                         stats[:, 0].copy(), stats[:, 1].copy(), np.array([len(f.kept) if f is not None else 0 for f in fits], np.int64),
+                         np.array([float(f.mse) ** 0.5 if f is not None else 0.0 for f in fits]), np.array([f is not None and not f.ok for f in fits], bool)]
+                    if wpath == "warp":
+                        plan = "warp"
+                pyr = None
+                for k, v in enumerate(w + [wbox, wpath]):
+                    wrep[k].append(v)
         if plan == "crop":
             box = platefill.crop_box(boxes[s:e], H, W)
             if box is None:
@@ -443,12 +538,15 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None, gc
         steady.append(0)
         skipped.append(plan == "skipped")
         tn.append(0)
-        tpath.append("canvas" if plan == "canvas" else "skipped")
+        tpath.append("canvas" if plan in ("canvas", "warp") else "skipped")
         if plan in ("none", "skipped", "canvas"):       # the masked pixels as they are; the canvas fill replaces those of its tracked frames
             left[s:e] = (d != 0).flatten(1).sum(1).cpu().numpy()
-        if plan not in ("crop", "canvas"):
+        if plan not in ("crop", "canvas", "warp"):
             continue
-        if plan == "canvas":
+        if plan == "warp":
+            new, d2, c, steady[-1] = _fill_on_warp(frames_rgb[s:e], d, wplan, wbox, platefill.crop_box(boxes[s:e], H, W), pcfg, gcfg)
+            left[s:e] = c[:, 1]
+        elif plan == "canvas":
             new, d2, c, steady[-1] = _fill_on_canvas(frames_rgb[s:e], d, track_t, track, cbox, pcfg, gcfg)
             left[s:e] = np.where(track[:, 3] == 1, c[:, 1], left[s:e])
         else:
@@ -477,6 +575,8 @@ def plate_fill(frames_rgb, dil_t, pcfg, cuts=None, acfg=None, align_out=None, gc
             dil[(slice(s, e),) + at] = d2
     if acfg is not None and align_out is not None:
         align_out.append(PlateAlignReport(*(tuple(v) for v in arep), segs))
+    if wcfg is not None and warp_out is not None:
+        warp_out.append(PlateWarpReport(*(tuple(v) for v in wrep), segs))
     if gcfg is not None and grain_out is not None:
         grain_out.append(PlateGrainReport(rotated, filled.copy(), segs))
     if tcfg is not None and tone_out is not None:
